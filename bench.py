@@ -16,12 +16,22 @@ timed as a secondary leg in the same run and is the size the parity tests valida
 With N > 1 every rank analyses its own month (months are independent work units, as in the
 reference's one-job-per-month launch, run/job_submitter_sbatch.py:45-68): the shared grid is
 broadcast once from rank 0 and the analysis fields are gathered every step over RCCL -- weak scaling.
-Every run, at every N, additionally times the FIXED 12-month (month x tile) workload of configs[3]
-(`config4_strong`): seconds(1) / seconds(N) is the strong-scaling curve.
+Prints ONE JSON line (rank 0).  A plain run does only what that line's headline needs: it sets up, runs
+`--warmup` untimed and `--steps` timed steps, writes the last step's outputs if `--dump-outputs DIR` is
+given, and prints the line (`ms_per_step` = milliseconds of one timed step).
 
-Prints ONE JSON line (rank 0).  Extra legs, N = 1 only: per-kernel HIP-event timing on the launch
-stream for the roofline object, the element-wise (reference-parity) OI on the same grid, and a
-bounded CPU run of the float64 oracle for cpu_baseline.
+    python bench.py --gpus 1 --steps K --warmup W --full
+
+adds everything else, as before: a checked (positive-definiteness, refinement residuals) pass ahead of
+the timed steps; at every N the FIXED 12-month (month x tile) workload of configs[3] (`config4_strong`:
+seconds(1) / seconds(N) is the strong-scaling curve) and the three species of configs[4]
+(`config5_strong`); at N = 1 per-kernel HIP-event timing on the launch stream for the roofline object,
+the secondary size, the localised (tiled) analysis, the element-wise (reference-parity) OI on the same
+grid and a bounded CPU run of the float64 oracle for cpu_baseline.
+
+--dump-outputs DIR: after the timed steps, the fields the analysis hands its caller in the last step --
+DIR/xa.npy (analysis) and DIR/inc.npy (increment), float32 as computed; with N > 1 rank 0 writes the
+gathered (rank, ny, nx) fields.  Inputs are seeded, so the same arguments give the same inputs on every run.
 """
 import argparse
 import glob
@@ -62,6 +72,11 @@ def parse():
     ap.add_argument("--refine", type=int, default=None)
     ap.add_argument("--species", default="NO2", choices=["NO2", "HCHO", "O3"],
                     help="parameter set of the synthetic month (BASELINE configs[4]: control_omino2/omihcho/omio3.yml shapes)")
+    ap.add_argument("--full", action="store_true", help="also the checked pass and every leg besides the headline (roofline, "
+                    "secondary, tiled, Tier-A, PCIe, regrid, config4/5 strong scaling, cpu_baseline); the --no-* options "
+                    "below drop legs of a --full run")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the last timed step's output fields as DIR/<name>.npy (float32/float64, at most 64 MB)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-roofline", action="store_true")
     ap.add_argument("--no-secondary", action="store_true")
@@ -114,6 +129,25 @@ def time_steps(fn, steps, warmup, sync, barrier=None):
         barrier()
     sync()
     return time.perf_counter() - t0
+
+
+DUMP_BUDGET_BYTES = 60 * 10 ** 6                  # the .npy files of --dump-outputs stay under 64 MB, headers included
+
+
+def dump_outputs(path, fields):
+    """--dump-outputs: one DIR/<name>.npy per output array, in the dtype it was computed in (float32 / float64).  When the
+    arrays together exceed DUMP_BUDGET_BYTES, every one is cut to the same fixed sample of its flattened elements
+    (ascending positions drawn by default_rng(0)), so that two runs with the same arguments stay comparable element for
+    element."""
+    os.makedirs(path, exist_ok=True)
+    total = sum(a.nbytes for a in fields.values())
+    for name, a in fields.items():
+        a = np.ascontiguousarray(a)
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        if total > DUMP_BUDGET_BYTES:
+            keep = a.size * DUMP_BUDGET_BYTES // total
+            a = a.ravel()[np.sort(np.random.default_rng(0).choice(a.size, keep, replace=False))]
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def roofline_leg(ctx, plan, L, refine, psteps):
@@ -878,12 +912,23 @@ def main():
         if gather is not None:
             gather.run()
 
-    resid = plan.run(L, refine=refine, check_pd=True, want_resid=True)      # checked pass, untimed
+    resid = None
+    if args.full:
+        resid = plan.run(L, refine=refine, check_pd=True, want_resid=True)  # checked pass, untimed
     elapsed = time_steps(step, args.steps, args.warmup, sync, barrier)
     if world > 1:
         tt = torch.tensor([elapsed], device="cuda", dtype=torch.float64)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         elapsed = float(tt.item())
+    else:
+        plan.check()                                       # the timed solves met no non-positive pivot
+    if args.dump_outputs and rank == 0:
+        if world > 1:
+            f = gather.fields()                            # (rank, xa | inc, ny, nx) of the last gather
+            dump_outputs(args.dump_outputs, {"xa": f[:, 0], "inc": f[:, 1]})
+        else:
+            xa, inc = plan.download()
+            dump_outputs(args.dump_outputs, {"xa": xa, "inc": inc})
 
     out = None
     if rank == 0:
@@ -904,18 +949,20 @@ def main():
                        "refine": refine, "months_per_step": world,
                        "parallelism": "one month per GPU; RCCL broadcast of the grid, gather of the fields to rank 0"},
             "solve_tflops_end_to_end": world * flops / (elapsed / args.steps) / 1e12,
-            "refinement_residuals": resid,
             "n_ranks_seen_by_backend": ranks_seen,
             "backend": {"name": dist.get_backend() if world > 1 else None, "world_size": dist.get_world_size() if world > 1 else 1,
                         "device_of_rank": devices_seen, "self_launched": os.environ.get("OISAT_BENCH_SELF_LAUNCHED") == "1"},
             "parity_anchor": "dense Gaussian-B path: no reference code exists (SURVEY 8 a-ext); oracle = float64 SciPy Cholesky of the "
                              "same definition, reference-anchored only in the L -> 0 limit against OI() golden outputs (DESIGN section 2)",
         }
-    if rank == 0 and world > 1 and not args.no_roofline:
+        if resid is not None:
+            out["refinement_residuals"] = resid
+    # ---- everything below is --full only -----------------------------------------------------------
+    if args.full and rank == 0 and world > 1 and not args.no_roofline:
         # the dominant kernel's roofline on rank 0 of a multi-GPU run too (the other ranks wait at the next leg's barrier): the
         # launch is per GPU, so the fraction is this GPU's -- the other legs below stay single-GPU extras
         out["roofline"], out["kernel_ms_per_step"] = roofline_leg(ctx, plan, L, refine, 2 if m > 30000 else 5)
-    if rank == 0 and world == 1:
+    if args.full and rank == 0 and world == 1:
         if not args.no_roofline:
             out["roofline"], out["kernel_ms_per_step"] = roofline_leg(ctx, plan, L, refine, 2 if m > 30000 else 5)
         del plan
@@ -998,7 +1045,7 @@ def main():
             out["tier_a_kernels"] = tier_a_kernels_leg(ctx, sync)
             out["pcie_inclusive"] = pcie_leg(sync)
             out["regrid"] = regrid_leg(ctx, sync)
-    if not args.no_config4:
+    if args.full and not args.no_config4:
         del gather
         if world > 1:
             del plan                                       # its 40 GB factor goes back before the tile lanes allocate theirs
@@ -1007,7 +1054,7 @@ def main():
         if rank == 0:
             out["config4_strong"] = c4
             out["config5_strong"] = c5
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:      # last: its BLAS threads keep spinning for a while
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:      # last: its BLAS threads keep spinning for a while
         out["cpu_baseline"] = cpu_baseline(args.workload)
     if rank == 0:
         print(json.dumps(out))

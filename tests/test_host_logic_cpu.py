@@ -292,6 +292,25 @@ def test_bench_launcher_propagates_a_failing_rank_and_refuses_a_mismatched_launc
     assert r.returncode != 0 and "must agree" in (r.stderr + r.stdout)
 
 
+def test_bench_dump_outputs_keeps_dtype_and_samples_a_fixed_subset_over_budget(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: arrays under the budget are written whole in their own dtype; over it, every array is cut to
+    the same seeded sample of its elements, identical from run to run, and the files stay under the budget."""
+    import bench
+    rng = np.random.default_rng(7)
+    xa, inc = rng.standard_normal((3, 40, 50)).astype(np.float32), rng.standard_normal((3, 40, 50))
+    bench.dump_outputs(str(tmp_path / "whole"), {"xa": xa, "inc": inc})
+    got = np.load(tmp_path / "whole" / "xa.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, xa)
+    assert np.array_equal(np.load(tmp_path / "whole" / "inc.npy"), inc)
+    monkeypatch.setattr(bench, "DUMP_BUDGET_BYTES", 9000)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), {"xa": xa, "inc": inc})
+    a, b = np.load(tmp_path / "a" / "xa.npy"), np.load(tmp_path / "b" / "xa.npy")
+    assert np.array_equal(a, b) and a.dtype == np.float32 and 0 < a.size < xa.size
+    assert np.isin(a, xa).all()
+    assert a.nbytes + np.load(tmp_path / "a" / "inc.npy").nbytes <= 9000
+
+
 def test_triangulation_worker_protocol_tells_a_failure_from_a_death():
     """interpolator_many's child processes (oisatgmi/_qhull_worker.py): a triangulation comes back with its lazily computed
     members, points qhull refuses come back as ``None`` (the reference skips such a granule, interpolator.py:151-155), stray
