@@ -116,6 +116,21 @@ int oisat_nanmean_stack(oisat_ctx* h, int dtype, const void* stack, int k, int64
  * count 0 -> NaN.  square_input != 0: stack holds sigma and is squared first (averaging.py:101). */
 int oisat_error_average(oisat_ctx* h, int dtype, const void* stack, int k, int64_t n, int square_input, void* out);
 
+/* Device-resident month (oisatgmi/month.py): the two reductions above, granule by granule.  acc: dev block of
+ * 5*n elements of acc_dtype (running sums) followed by 5*n uint32 (counts), zeroed before the first granule, for
+ * the fields vcd (mean, inf -> NaN), uncertainty (error kind, squared), ctm_vcd, new_amf, old_amf (plain means).
+ * One launch per granule folds its five n-element fields into acc in the order of the launches; bit f of
+ * f32_mask says field f is float32 (else float64); it is converted to acc_dtype in registers.  kept: dev int32,
+ * the launch does nothing when *kept == 0.  Summing granule by granule from 0 gives the bits of the stack kernels. */
+int oisat_month_accumulate(oisat_ctx* h, int acc_dtype, const void* vcd, const void* uncertainty, const void* ctm_vcd,
+                           const void* new_amf, const void* old_amf, int f32_mask, int64_t n, const int32_t* kept, void* acc);
+/* out: dev [5][n] of acc_dtype, the finished means (and the error average for field 1) of acc. */
+int oisat_month_finish(oisat_ctx* h, int acc_dtype, const void* acc, int64_t n, void* out);
+/* *kept = 0 when every element of x is NaN, else 1 (interpolator.py's `np.isnan(vcd).all()` skip test). */
+int oisat_all_nan(oisat_ctx* h, int dtype, const void* x, int64_t n, int32_t* kept);
+/* out[i] = (double)x[i] (exact; NumPy's astype(float64) of a float32 array). */
+int oisat_widen(oisat_ctx* h, const float* x, int64_t n, double* out);
+
 /* out = (x - offset) / slope  (bias_correct, driver.py:65-106) or x / divisor with offset 0
  * (O3 unit conversion, driver.py:62-63). */
 int oisat_affine(oisat_ctx* h, int dtype, const void* x, int64_t n, double offset, double slope, void* out);

@@ -53,6 +53,10 @@ SIGNATURES = {
                                  _ptr, _ptr, _ptr, _ptr, _ptr, _ptr]),
     "oisat_nanmean_stack": (C.c_int, [_c_ctx, C.c_int, _ptr, C.c_int, _i64, C.c_int, _ptr]),
     "oisat_error_average": (C.c_int, [_c_ctx, C.c_int, _ptr, C.c_int, _i64, C.c_int, _ptr]),
+    "oisat_month_accumulate": (C.c_int, [_c_ctx, C.c_int, _ptr, _ptr, _ptr, _ptr, _ptr, C.c_int, _i64, _ptr, _ptr]),
+    "oisat_month_finish": (C.c_int, [_c_ctx, C.c_int, _ptr, _i64, _ptr]),
+    "oisat_all_nan": (C.c_int, [_c_ctx, C.c_int, _ptr, _i64, _ptr]),
+    "oisat_widen": (C.c_int, [_c_ctx, _ptr, _i64, _ptr]),
     "oisat_affine": (C.c_int, [_c_ctx, C.c_int, _ptr, _i64, C.c_double, C.c_double, _ptr]),
     "oisat_oi_variances": (C.c_int, [_c_ctx, C.c_int, _ptr, _ptr, _i64, C.c_double, _ptr, _ptr]),
     "oisat_scaling_factor": (C.c_int, [_c_ctx, C.c_int, _ptr, _ptr, _i64, _ptr]),

@@ -55,54 +55,63 @@ def error_averager(error_X: np.ndarray):
     return _reduce_stack(ctx, list(error_X), dt, "err", False)
 
 
+def _parse_date(s):
+    return datetime.date(int(s[0:4]), int(s[5:7]), int(s[8:10]))
+
+
+def _window(startdate: str, enddate: str, times):
+    """Which granules ``averaging()`` reduces into which output slot (averaging.py:40-108).  ``times``: one datetime per
+    granule, ``None`` for a skipped one.  Returns ``(nm, nyr, slots, time_idx)``: the output is (ny, nx, nm, nyr) before the
+    squeeze; ``slots`` lists ``(mi, yi, granule indices in order)``, one per year of the window; ``time_idx`` are the
+    granules whose times make ``avg_datetime``.
+
+    The reference rebuilds its lists for every month and reduces AFTER the month loop, so only the last month (m1) of
+    each year's range is averaged -- a December-to-January window averages December only, and its ``avg_datetime``
+    comes from the (usually empty) December of the second year."""
+    start_date, end_date = _parse_date(startdate), _parse_date(enddate)
+    months = np.array([d.month for d in _daterange(start_date, end_date)])
+    years = np.array([d.year for d in _daterange(start_date, end_date)])
+    m0, m1 = int(np.min(months)), int(np.max(months))
+    y0, y1 = int(np.min(years)), int(np.max(years))
+    slots = []
+    chosen = []
+    for year in range(y0, y1 + 1):
+        chosen = [i for i, t in enumerate(times) if t is not None and t.year == year and t.month == m1]
+        slots.append((m1 - m0, year - y0, chosen))
+    return m1 - m0 + 1, y1 - y0 + 1, slots, chosen
+
+
 def averaging(startdate: str, enddate: str, reader_obj):
     """Drop-in for ``averaging`` (averaging.py:26-120): the per-granule satellite and model columns of ``reader_obj`` between
     the two dates (``'YYYY-mm-dd'`` strings, the end exclusive) reduced to monthly means on the model grid: ``nanmean`` of the
     columns and auxiliaries, ``error_averager`` of the errors.  The stacks are reduced on the device (csrc/averaging.hip)."""
     ctx = _hip.context()
-    start_date = datetime.date(int(startdate[0:4]), int(startdate[5:7]), int(startdate[8:10]))
-    end_date = datetime.date(int(enddate[0:4]), int(enddate[5:7]), int(enddate[8:10]))
-    months = np.array([d.month for d in _daterange(start_date, end_date)])
-    years = np.array([d.year for d in _daterange(start_date, end_date)])
-    m0, m1 = int(np.min(months)), int(np.max(months))
-    y0, y1 = int(np.min(years)), int(np.max(years))
+    sat_data = reader_obj.sat_data
+    nm, nyr, slots, time_idx = _window(startdate, enddate, [None if g is None else g.time for g in sat_data])
 
-    first = next(g for g in reader_obj.sat_data if g is not None)
+    first = next(g for g in sat_data if g is not None)
     ny, nx = np.shape(first.latitude_center)[0], np.shape(first.latitude_center)[1]
-    nm, nyr = m1 - m0 + 1, y1 - y0 + 1
     sat_averaged_vcd = np.zeros((ny, nx, nm, nyr))        # zeros, not NaN (averaging.py:53-58)
     sat_averaged_error = np.full((ny, nx, nm, nyr), np.nan)
     ctm_averaged_vcd = np.full((ny, nx, nm, nyr), np.nan)
     sat_aux1 = np.full((ny, nx, nm, nyr), np.nan)
     sat_aux2 = np.full((ny, nx, nm, nyr), np.nan)
 
-    time_chosen = []
-    for year in range(y0, y1 + 1):
+    for mi, yi, idx in slots:
         chosen = {"vcd": [], "err": [], "ctm": [], "a1": [], "a2": []}
-        month = m0
-        for month in range(m0, m1 + 1):
-            # the reference rebuilds its lists per month and reduces AFTER the month loop
-            # (averaging.py:66-108): only the last month of a multi-month window is averaged
-            chosen = {"vcd": [], "err": [], "ctm": [], "a1": [], "a2": []}
-            time_chosen = []
-            for g in reader_obj.sat_data:
-                if g is None:
-                    continue
-                if g.time.year == year and g.time.month == month:
-                    time_chosen.append(g.time)
-                    chosen["vcd"].append(g.vcd)
-                    chosen["err"].append(g.uncertainty)
-                    chosen["ctm"].append(g.ctm_vcd)
-                    if isinstance(g, satellite_amf):
-                        chosen["a1"].append(g.new_amf)
-                        chosen["a2"].append(g.old_amf)
-                    elif isinstance(g, satellite_opt):
-                        chosen["a1"].append(g.x_col)
-                        chosen["a2"].append(g.ctm_xcol)
-                    else:
-                        chosen["a1"].append(np.nan * g.vcd)
-                        chosen["a2"].append(np.nan * g.vcd)
-        mi, yi = month - m0, year - y0
+        for g in (sat_data[i] for i in idx):
+            chosen["vcd"].append(g.vcd)
+            chosen["err"].append(g.uncertainty)
+            chosen["ctm"].append(g.ctm_vcd)
+            if isinstance(g, satellite_amf):
+                chosen["a1"].append(g.new_amf)
+                chosen["a2"].append(g.old_amf)
+            elif isinstance(g, satellite_opt):
+                chosen["a1"].append(g.x_col)
+                chosen["a2"].append(g.ctm_xcol)
+            else:
+                chosen["a1"].append(np.nan * g.vcd)
+                chosen["a2"].append(np.nan * g.vcd)
         if len(chosen["vcd"]) != 0 and np.size(chosen["vcd"][0]) != 0:
             # every granule counts, as np.array(list) would promote: one float64 granule makes the stack float64
             dt = _hip.compute_dtype(*chosen["vcd"], *chosen["err"], *chosen["ctm"])
@@ -119,7 +128,7 @@ def averaging(startdate: str, enddate: str, reader_obj):
     ctm_averaged_vcd = ctm_averaged_vcd.squeeze()
     sat_aux1 = sat_aux1.squeeze()
     sat_aux2 = sat_aux2.squeeze()
-    timestamps = [t.timestamp() for t in time_chosen]
+    timestamps = [sat_data[i].time.timestamp() for i in time_idx]
     avg_datetime = datetime.datetime.fromtimestamp(sum(timestamps) / len(timestamps))
     print(avg_datetime)
     return sat_averaged_vcd, sat_averaged_error, ctm_averaged_vcd, sat_aux1, sat_aux2, avg_datetime

@@ -41,8 +41,35 @@ class oisatgmi(object):
         additionally converts the model column to Dobson units."""
         (self.sat_averaged_vcd, self.sat_averaged_error, self.ctm_averaged_vcd, self.aux1, self.aux2,
          self.avg_time) = averaging(startdate, enddate, self.reader_obj)
+        self._granule_grid = None
         if gasname == 'O3':
             self.ctm_averaged_vcd = self.ctm_averaged_vcd / O3_DIVISOR
+
+    def average_granules(self, startdate: str, enddate: str, granules, interpolator_type, grid_size, flag_thresh=0.75,
+                         gasname=None, keep_daily=False):
+        """``average`` straight from a month of RAW granules (``oisatgmi.month.month_average``): regrid, AMF recalculation
+        against ``reader_obj.ctm_data`` and averaging without the regridded granules ever leaving the device.  Sets the
+        attributes ``average`` sets, bit for bit those of regridding with ``interpolator_many``, ``recal_amf`` and
+        ``average``.  ``keep_daily=True`` also fills ``reader_obj.sat_data`` with slim per-granule records for
+        ``savedaily``."""
+        from .month import _month_average
+        ctm_data = self.reader_obj.ctm_data
+        coord = {"Latitude": ctm_data[0].latitude, "Longitude": ctm_data[0].longitude}      # reader.py:1519-1520
+        res, daily, self._granule_grid = _month_average(startdate, enddate, granules, ctm_data, coord, interpolator_type,
+                                                        grid_size, flag_thresh, None, keep_daily)
+        if keep_daily:
+            self.reader_obj.sat_data = daily
+        (self.sat_averaged_vcd, self.sat_averaged_error, self.ctm_averaged_vcd, self.aux1, self.aux2, self.avg_time) = res
+        if gasname == 'O3':
+            self.ctm_averaged_vcd = self.ctm_averaged_vcd / O3_DIVISOR
+
+    def _first_granule_grid(self):
+        """(lon, lat) of the averaged grid: the first granule record's, or the grid ``average_granules`` averaged onto."""
+        grid = getattr(self, "_granule_grid", None)
+        if grid is not None:
+            return grid
+        first = next(g for g in self.reader_obj.sat_data if g is not None)
+        return first.longitude_center, first.latitude_center
 
     def bias_correct(self, sat_type, gasname):
         # apply bias correction based on several validation studies
@@ -72,8 +99,7 @@ class oisatgmi(object):
     def _oi_grid(self):
         lat, lon = getattr(self, "grid_lat", None), getattr(self, "grid_lon", None)
         if lat is None or lon is None:
-            first = next(g for g in self.reader_obj.sat_data if g is not None)
-            lat, lon = first.latitude_center, first.longitude_center
+            lon, lat = self._first_granule_grid()
         return np.asarray(lat, dtype=np.float64), np.asarray(lon, dtype=np.float64)
 
     def oi(self, sensor: str, error_ctm=50.0):
@@ -177,13 +203,13 @@ class oisatgmi(object):
 
     def output_fields(self):
         """The variables of the reference's output file, in its order and as float32 (driver.py:179-225)."""
-        first = next(g for g in self.reader_obj.sat_data if g is not None)
+        lon, lat = self._first_granule_grid()
         f32 = lambda a: np.asarray(a, dtype=np.float32)       # noqa: E731
         return {
             "sat_averaged_vcd": f32(self.sat_averaged_vcd), "ctm_averaged_vcd_prior": f32(self.ctm_averaged_vcd),
             "ctm_averaged_vcd_posterior": f32(self.ctm_averaged_vcd_corrected), "sat_averaged_error": f32(self.sat_averaged_error),
             "ak_OI": f32(self.ak_OI), "error_OI": f32(self.error_OI), "scaling_factor": f32(self.scaling_factor()),
-            "lon": f32(first.longitude_center), "lat": f32(first.latitude_center), "aux1": f32(self.aux1), "aux2": f32(self.aux2),
+            "lon": f32(lon), "lat": f32(lat), "aux1": f32(self.aux1), "aux2": f32(self.aux2),
         }
 
     def write_to_nc(self, output_file, output_folder='diag'):

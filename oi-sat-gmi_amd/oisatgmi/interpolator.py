@@ -562,9 +562,10 @@ class _GranuleRegridder:
             b = self._flag_bufs[dt] = self.ctx.upload(np.ravel(self.qflag_host), dtype=dt)
         return b
 
-    def regrid(self, fields, error=False):
+    def regrid(self, fields, error=False, device=False):
         """``fields``: list of swath-shaped arrays.  Returns (X, Y, Z, upscaled_ctm_needed) with Z of shape (fields, ny, nx),
-        Z[f] = _upscaler(.., _interpolosis(tri, field*mask, ..), .., error=error)[2]."""
+        Z[f] = _upscaler(.., _interpolosis(tri, field*mask, ..), .., error=error)[2].  ``device=True``: Z stays in HBM and
+        comes back as ``(DeviceBuffer of fields*ny*nx elements of _regrid_dtype(), (ny, nx))`` instead (oisatgmi.month)."""
         ctx = self.ctx
         nf = len(fields)
         dt = _regrid_dtype()
@@ -591,13 +592,17 @@ class _GranuleRegridder:
             fine = _gather(ctx, dt, masked, self.P, nf, self.idx_fine, self.Tfine)
         if self.plan.needed:
             out = self.plan.run(fine, nf, dt, error)
-            Z = ctx.download(out.ptr, (nf,) + tuple(self.plan.out_shape), dt)
+            shape = tuple(self.plan.out_shape)
             X, Y = self.plan.ctm_longitude, self.plan.ctm_latitude
             need = False
         else:
-            Z = ctx.download(fine.ptr, (nf,) + tuple(self.fine_shape), dt)
+            out = fine
+            shape = tuple(self.fine_shape)
             X, Y = self.lons_grid, self.lats_grid
             need = True
+        if device:
+            return X, Y, (out, shape), need
+        Z = ctx.download(out.ptr, (nf,) + shape, dt)
         return X, Y, Z, need            # Z[f] = field f (one array: consecutive fields are a cube without a copy)
 
 
@@ -611,9 +616,19 @@ def interpolator_many(interpolator_type: int, grid_size: float, granules, ctm_mo
     30 ms).  Same triangulations, same order of evaluation: the outputs are those of the serial calls bit for bit (``None``
     entries and ``None`` results as there).  The workers are child processes (``oisatgmi._qhull_worker``, pipes) that never
     touch the device; only this process holds the handle (INTEGRATION.md "Threading / processes")."""
-    granules = list(granules)
+    return [None if g is None else _interpolate_granule(interpolator_type, grid_size, g, ctm_models_coordinate, flag_thresh, tri)
+            for g, tri in _with_triangulations(interpolator_type, list(granules), workers)]
+
+
+def _with_triangulations(interpolator_type, granules, workers=None):
+    """Yields ``(granule, triangulation)`` for every entry of ``granules`` in order.  Type 1: the ``scipy.spatial.Delaunay``
+    of the granule (None where qhull failed), built ahead by the worker processes of ``interpolator_many``; other types, and
+    a single granule: ``_NOT_GIVEN`` (the regridder builds what it needs).  ``None`` entries are passed through and never
+    triangulated -- which is how a caller skips granules it does not want regridded."""
     if interpolator_type != 1 or len(granules) < 2:
-        return [None if g is None else interpolator(interpolator_type, grid_size, g, ctm_models_coordinate, flag_thresh) for g in granules]
+        for g in granules:
+            yield g, _NOT_GIVEN
+        return
     from concurrent.futures import ThreadPoolExecutor
     if workers is None:
         try:
@@ -622,7 +637,6 @@ def interpolator_many(interpolator_type: int, grid_size: float, granules, ctm_mo
             ncpu = os.cpu_count() or 1
         workers = max(1, min(8, ncpu - 1, len(granules)))
     ahead = 2 * int(workers)                              # triangulations in flight / waiting: bounded (each holds ~25 MB)
-    out = []
     procs = _QhullWorkers(workers)
     try:
         with ThreadPoolExecutor(max_workers=int(workers), thread_name_prefix="oisat-qhull") as feeders:
@@ -639,13 +653,11 @@ def interpolator_many(interpolator_type: int, grid_size: float, granules, ctm_mo
                 if k + ahead < len(granules):
                     submit(k + ahead)
                 if g is None:
-                    out.append(None)
+                    yield None, None
                     continue
-                tri = futures.pop(k).result()
-                out.append(_interpolate_granule(interpolator_type, grid_size, g, ctm_models_coordinate, flag_thresh, tri))
+                yield g, futures.pop(k).result()
     finally:
         procs.close()
-    return out
 
 
 def interpolator(interpolator_type: int, grid_size: float, sat_data, ctm_models_coordinate: dict, flag_thresh=0.75):
