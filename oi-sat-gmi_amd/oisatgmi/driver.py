@@ -48,10 +48,11 @@ class oisatgmi(object):
     def average_granules(self, startdate: str, enddate: str, granules, interpolator_type, grid_size, flag_thresh=0.75,
                          gasname=None, keep_daily=False):
         """``average`` straight from a month of RAW granules (``oisatgmi.month.month_average``): regrid, AMF recalculation
-        against ``reader_obj.ctm_data`` and averaging without the regridded granules ever leaving the device.  Sets the
-        attributes ``average`` sets, bit for bit those of regridding with ``interpolator_many``, ``recal_amf`` and
-        ``average``.  ``keep_daily=True`` also fills ``reader_obj.sat_data`` with slim per-granule records for
-        ``savedaily``."""
+        (``satellite_amf``) or averaging-kernel convolution (``satellite_opt``; the sensor, MOPITT or GOSAT, comes from the
+        records) against ``reader_obj.ctm_data`` and averaging without the regridded granules ever leaving the device.
+        Sets the attributes ``average`` sets, bit for bit those of regridding with ``interpolator_many``, ``recal_amf`` or
+        ``conv_ak`` and ``average``, so ``oi('GOSAT')`` reads aux1 / aux2 as it does after ``average``.
+        ``keep_daily=True`` also fills ``reader_obj.sat_data`` with slim per-granule records for ``savedaily``."""
         from .month import _month_average
         ctm_data = self.reader_obj.ctm_data
         coord = {"Latitude": ctm_data[0].latitude, "Longitude": ctm_data[0].longitude}      # reader.py:1519-1520

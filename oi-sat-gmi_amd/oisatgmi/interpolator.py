@@ -672,6 +672,62 @@ def interpolator(interpolator_type: int, grid_size: float, sat_data, ctm_models_
     return _interpolate_granule(interpolator_type, grid_size, sat_data, ctm_models_coordinate, flag_thresh, _NOT_GIVEN)
 
 
+_OPT_SINGLES = (("aprior_column", "apriori column"), ("surface_pressure", "surface pressure"),
+                ("apriori_surface", "apriori surface"))
+
+
+def _add_levels(names, fields, levels, name, cube, count):
+    """Append the ``count`` levels of ``cube`` as consecutive fields; ``levels[name] = (first index, count)``."""
+    levels[name] = (len(fields), count)
+    for z in range(count):
+        names.append(f"{name}[{z}]")
+        fields.append(np.squeeze(np.asarray(cube)[z]))
+
+
+def _opt_fields(sat_data, log=lambda msg: None):
+    """The fields ``interpolator()`` regrids for a ``satellite_opt`` granule, in its order (interpolator.py:191-283): vcd,
+    [tropopause], those of the a-priori column, surface pressure and a-priori surface that are not all zero, x_col, the
+    averaging kernels (nz + 1 rows for MOPITT, nz for GOSAT, none for another sensor), the pressure weights (GOSAT), the
+    pressure levels and the a-priori profile.  -> (names, fields, levels): ``levels[name] = (first index, count)`` for every
+    field, a single one with count 0; the rows of a cube are consecutive."""
+    nz = np.shape(sat_data.pressure_mid)[0]
+    names, fields, levels = [], [], {}
+
+    def single(name, a):
+        levels[name] = (len(fields), 0)
+        names.append(name)
+        fields.append(a)
+
+    log('....................... vcd')
+    single("vcd", sat_data.vcd)
+    log('....................... tropopause')
+    if np.size(sat_data.tropopause) != 1:
+        single("tropopause", sat_data.tropopause)
+    for nm, msg in _OPT_SINGLES:
+        if getattr(sat_data, nm).any():
+            log('....................... ' + msg)
+            single(nm, getattr(sat_data, nm))
+    log('....................... Xcol')
+    single("x_col", sat_data.x_col)
+    if sat_data.sensor == 'MOPITT':
+        _add_levels(names, fields, levels, "averaging_kernels", sat_data.averaging_kernels, nz + 1)
+    if sat_data.sensor == 'GOSAT':
+        _add_levels(names, fields, levels, "averaging_kernels", sat_data.averaging_kernels, nz)
+        _add_levels(names, fields, levels, "pressure_weight", sat_data.pressure_weight, nz)
+    _add_levels(names, fields, levels, "pressure_mid", sat_data.pressure_mid, nz)
+    _add_levels(names, fields, levels, "apriori_profile", sat_data.apriori_profile, nz)
+    return names, fields, levels
+
+
+def _opt_check(sat_data, levels):
+    """The NameErrors a regridded, not all-NaN ``satellite_opt`` granule meets in the reference (interpolator.py:285-287)."""
+    missing = [nm for nm, _ in _OPT_SINGLES if nm not in levels]
+    if missing:                          # the reference leaves these names unbound and dies at :285-287
+        raise NameError(f"satellite_opt record has all-zero {missing}; the reference cannot rebuild it either")
+    if sat_data.sensor not in ('MOPITT', 'GOSAT'):
+        raise NameError("averaging_kernels are only regridded for sensor 'MOPITT' or 'GOSAT'")
+
+
 def _interpolate_granule(interpolator_type, grid_size, sat_data, ctm_models_coordinate, flag_thresh, triangulation):
     if interpolator_type not in (1, 2, 3, 4):
         raise Exception("other type of interpolation methods has not been implemented yet")
@@ -682,51 +738,28 @@ def _interpolate_granule(interpolator_type, grid_size, sat_data, ctm_models_coor
     is_opt = isinstance(sat_data, satellite_opt)
 
     # ---- one stacked pass for every mean-kernel field of the granule
-    names, fields = ["vcd"], [sat_data.vcd]
-    print('....................... vcd')
-    if is_amf:
-        print('....................... amf')
-        names.append("amf")
-        fields.append(sat_data.amf)
-    print('....................... tropopause')
-    has_trop = np.size(sat_data.tropopause) != 1
-    if has_trop:
-        names.append("tropopause")
-        fields.append(sat_data.tropopause)
     nz = np.shape(sat_data.pressure_mid)[0]
-    levels = {}                                           # name -> (first index, count)
-
-    def add_levels(name, cube, count):
-        levels[name] = (len(fields), count)
-        for z in range(count):
-            names.append(f"{name}[{z}]")
-            fields.append(np.squeeze(np.asarray(cube)[z]))
-
-    if is_amf and np.size(sat_data.scattering_weights) != 1:
-        print('....................... SWs [' + str(nz) + ' levels]')
-        add_levels("scattering_weights", sat_data.scattering_weights, nz)
-        print('....................... pmids [' + str(nz) + ' levels]')
-        add_levels("pressure_mid", sat_data.pressure_mid, nz)
     if is_opt:
-        singles = {}
-        for nm, msg in (("aprior_column", "apriori column"), ("surface_pressure", "surface pressure"),
-                        ("apriori_surface", "apriori surface")):
-            if getattr(sat_data, nm).any():
-                print('....................... ' + msg)
-                singles[nm] = len(fields)
-                names.append(nm)
-                fields.append(getattr(sat_data, nm))
-        print('....................... Xcol')
-        singles["x_col"] = len(fields)
-        names.append("x_col")
-        fields.append(sat_data.x_col)
-        if sat_data.sensor == 'MOPITT':
-            add_levels("averaging_kernels", sat_data.averaging_kernels, nz + 1)
-        if sat_data.sensor == 'GOSAT':
-            add_levels("averaging_kernels", sat_data.averaging_kernels, nz)
-            add_levels("pressure_weight", sat_data.pressure_weight, nz)
-        add_levels("pressure_mid", sat_data.pressure_mid, nz)
-        add_levels("apriori_profile", sat_data.apriori_profile, nz)
+        names, fields, levels = _opt_fields(sat_data, log=print)
+        has_trop = "tropopause" in levels
+    else:
+        names, fields = ["vcd"], [sat_data.vcd]
+        print('....................... vcd')
+        if is_amf:
+            print('....................... amf')
+            names.append("amf")
+            fields.append(sat_data.amf)
+        print('....................... tropopause')
+        has_trop = np.size(sat_data.tropopause) != 1
+        if has_trop:
+            names.append("tropopause")
+            fields.append(sat_data.tropopause)
+        levels = {}                                       # name -> (first index, count)
+        if is_amf and np.size(sat_data.scattering_weights) != 1:
+            print('....................... SWs [' + str(nz) + ' levels]')
+            _add_levels(names, fields, levels, "scattering_weights", sat_data.scattering_weights, nz)
+            print('....................... pmids [' + str(nz) + ' levels]')
+            _add_levels(names, fields, levels, "pressure_mid", sat_data.pressure_mid, nz)
 
     upscaled_X, upscaled_Y, Z, upscaled_ctm_needed = rg.regrid(fields)
     vcd = Z[0]
@@ -757,15 +790,8 @@ def _interpolate_granule(interpolator_type, grid_size, sat_data, ctm_models_coor
         return satellite_amf(vcd, by_name["amf"], sat_data.time, tropopause, latitude_center, longitude_center, [], [],
                              uncertainty, [], pressure_mid, scattering_weights, upscaled_ctm_needed, [], [], [], [])
     if is_opt:
-        missing = [nm for nm in ("aprior_column", "surface_pressure", "apriori_surface") if nm not in singles]
-        if missing:                      # the reference leaves these names unbound and dies at :285-287
-            raise NameError(f"satellite_opt record has all-zero {missing}; the reference cannot rebuild it either")
-        if sat_data.sensor == 'MOPITT':
-            pressure_weights = np.empty((1))
-        elif sat_data.sensor == 'GOSAT':
-            pressure_weights = cube("pressure_weight")
-        else:
-            raise NameError("averaging_kernels are only regridded for sensor 'MOPITT' or 'GOSAT'")
+        _opt_check(sat_data, levels)
+        pressure_weights = cube("pressure_weight") if sat_data.sensor == 'GOSAT' else np.empty((1))
         return satellite_opt(vcd, sat_data.time, [], tropopause, latitude_center, longitude_center, [], [],
                              uncertainty, [], cube("pressure_mid"), cube("averaging_kernels"), upscaled_ctm_needed,
                              [], [], [], by_name["aprior_column"], cube("apriori_profile"), by_name["surface_pressure"],
