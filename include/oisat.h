@@ -355,6 +355,39 @@ int oisat_gemm_nt(oisat_ctx* h, float* C, int64_t ldc, const float* A, int64_t l
  * trailing updates.  info_host: 0 ok, j>0 = first non-positive pivot column (1-based). */
 int oisat_potrf(oisat_ctx* h, float* S, int64_t m, int64_t ld, int* info_host);
 
+/* ---- the covariance's latitude envelope ---------------------------------------------------------------------
+ * With the observations in ASCENDING latitude order S is a band: a pair whose latitudes differ by more than the
+ * angle of the library's cut-off chord (correlation below 2^-52, the cut-off of oisat_cov_residual and
+ * oisat_apply_increment) contributes nothing, and a Cholesky factor has no fill outside the envelope of its matrix.
+ *
+ * oisat_envelope (host only, no device call): lat_sorted = host double[m], ascending, degrees.  Writes
+ * env_out[0 .. nb) = first[i], the first 128-row tile column of tile row i that can hold a pair inside the cut-off
+ * (tile k is outside when lat_max(tile k) < lat_min(tile i) - angle; non-decreasing; first[i] <= max(i - 1, 0)), and
+ * env_out[nb .. 2 nb) = last[b] = max{ j : first[j] <= b };  nb = roundup(m, 128) / 128.  The caller keeps this
+ * table on the host and a copy of all 2 nb words on the device.
+ *
+ * oisat_cov_build_env: oisat_cov_build for such a system.  env_dev = the DEVICE copy.  Tiles inside the envelope are
+ * evaluated, the lower tiles outside it are FILLED WITH EXACT ZEROS (never left as they were).
+ *
+ * oisat_potrf_env: oisat_potrf of a matrix built by oisat_cov_build_env with the same table.  first = the HOST
+ * table (checked: range, order), env_dev = its device copy (must stay valid and unchanged while the factor is in
+ * use).  The task graph has tile tasks inside the envelope only and starts every K-loop at the envelope; inside the
+ * envelope the factor has the bits of oisat_potrf's task-graph factor of the same zero-filled matrix, outside it
+ * the zeros stay.  Systems the task graph does not take (under three block rows, OISAT_DAG=0) are factored densely.
+ * The handle remembers the envelope with the factor: oisat_gain_solve and oisat_potrs sweep inside it (same bits: the
+ * skipped blocks are zeros).  Who reads an enveloped factor, per function:
+ *   oisat_gain_solve, oisat_potrs                          walk the envelope only
+ *   oisat_trsm_rows, oisat_posterior_error, oisat_gain_diag, a download of S
+ *                                                          read densely and find the zeros of the build
+ *   oisat_potrf, oisat_factor_adopt                        forget the envelope (dense sweeps from then on)
+ * OISAT_ENVELOPE=0 in the environment (read at every call) makes both entry points behave exactly as oisat_cov_build /
+ * oisat_potrf: the dense path, for A/B timing and tests. */
+int oisat_envelope(const double* lat_sorted, int64_t m, double g, int32_t* env_out);
+int oisat_cov_build_env(oisat_ctx* h, const double* oxyz, const double* osig, const double* ovar, int64_t m,
+                        double g, float* S, int64_t ld, const int32_t* env_dev);
+int oisat_potrf_env(oisat_ctx* h, float* S, int64_t m, int64_t ld, const int32_t* first, const int32_t* env_dev,
+                    int* info_host);
+
 /* z <- L^-T L^-1 z  (dev double[m], fp32 factor, double accumulation). */
 int oisat_potrs(oisat_ctx* h, const float* L, int64_t m, int64_t ld, double* z_inout);
 

@@ -1351,8 +1351,10 @@ __device__ __forceinline__ bool wait_payload(const double* src, double* vec, Trs
 // DAG: the row is a task of the task-graph launch (dense_dag.inc) -- the vectors are then shared with workgroups of the SAME
 // launch across sweeps, so every store to them is an agent-scope (write-through) store and every load of a word another
 // workgroup wrote an agent-scope load (cdna_hip_programming.md Guideline 16); between launches plain accesses do.
+// step0: the first producer step that is walked (0 <= step0 <= tk).  Above 0 only for an ENVELOPED factor (oisat_potrf_env):
+// the blocks of the skipped producers are exact zeros, whose products would add 0.0 to the double accumulator.
 template <int TRANSPOSE, bool DAG>
-__device__ __forceinline__ bool trsv_row(const float* __restrict__ L, int64_t ld, const float* __restrict__ tinv, int nb, int tk,
+__device__ __forceinline__ bool trsv_row(const float* __restrict__ L, int64_t ld, const float* __restrict__ tinv, int nb, int tk, int step0,
                                          double* __restrict__ rhs, double* __restrict__ sol, TrsvCtl* __restrict__ ctl,
                                          unsigned* __restrict__ err_total, int two_tiles, double* __restrict__ zout, int64_t m,
                                          int accumulate, float* __restrict__ tile, double* __restrict__ vec, double* __restrict__ part,
@@ -1387,8 +1389,8 @@ __device__ __forceinline__ bool trsv_row(const float* __restrict__ L, int64_t ld
         float* tile = tileT;                                // TILE_STORE writes to the `tile` in scope
         TILE_STORE()
     }
-    if (nsteps > 0) { TILE_PREFETCH(base, ld) } else if (!two_tiles) { TILE_PREFETCH(Tb, NB) }
-    for (int step = 0; step <= nsteps; ++step) {
+    if (nsteps > step0) { const float* b0 = base + (int64_t)step0 * hop; TILE_PREFETCH(b0, ld) } else if (!two_tiles) { TILE_PREFETCH(Tb, NB) }
+    for (int step = step0; step <= nsteps; ++step) {
         const bool last = step == nsteps;                   // last pass: multiply by the inverted diagonal block
         if (!(last && two_tiles)) TILE_STORE()              // this step's block: in LDS before the wait, off the critical path
         if (!last) {
@@ -1446,7 +1448,9 @@ __global__ __launch_bounds__(256) void trsv_pipe_kernel(const float* __restrict_
                                                          double* __restrict__ rhs, double* __restrict__ sol,
                                                          TrsvCtl* __restrict__ ctl, unsigned* __restrict__ err_total, int two_tiles,
                                                          const SolveState* __restrict__ st, double* __restrict__ zout, int64_t m,
-                                                         int accumulate) {
+                                                         int accumulate, const int* __restrict__ env) {
+    // env (or nullptr): first[nb] | last[nb] of an enveloped factor -- forward, row b's producers start at first[b]; backward,
+    // column b's at last[b] = max{ j : first[j] <= b }.  Clamped into [0, tk]: no table content can move a read out of L.
     extern __shared__ __attribute__((aligned(16))) float tile[];        // [128][TLD]  (+ a second one for T_b if two_tiles)
     __shared__ double vec[NB], part[NB];
     __shared__ unsigned s_ticket, s_ok;
@@ -1461,7 +1465,12 @@ __global__ __launch_bounds__(256) void trsv_pipe_kernel(const float* __restrict_
         __syncthreads();
         const int tk = (int)s_ticket;                    // 0 .. nb-1 in claim order
         if (tk >= nb) break;
-        if (!trsv_row<TRANSPOSE, false>(L, ld, tinv, nb, tk, rhs, sol, ctl, err_total, two_tiles, zout, m, accumulate, tile, vec, part, &s_ok))
+        int step0 = 0;
+        if (env != nullptr) {
+            step0 = TRANSPOSE ? nb - 1 - env[nb + (nb - 1 - tk)] : env[tk];
+            step0 = step0 < 0 ? 0 : (step0 > tk ? tk : step0);
+        }
+        if (!trsv_row<TRANSPOSE, false>(L, ld, tinv, nb, tk, step0, rhs, sol, ctl, err_total, two_tiles, zout, m, accumulate, tile, vec, part, &s_ok))
             break;
     }
     if (tid == 0) trsv_leave(ctl);
@@ -1494,7 +1503,7 @@ __global__ __launch_bounds__(256) void trsv_batched_kernel(const SolveMember* __
         if (!first_solve && mb->st->conv != 0) continue;             // this system needs no further correction
         double* in = TRANSPOSE ? mb->fwd : mb->rhs;
         double* out = TRANSPOSE ? mb->rhs : mb->fwd;
-        if (!trsv_row<TRANSPOSE, false>(mb->S, mb->ld, mb->tinv, mb->mpb, tk, in, out, ctl, err_total, 0, TRANSPOSE ? mb->z : (double*)nullptr,
+        if (!trsv_row<TRANSPOSE, false>(mb->S, mb->ld, mb->tinv, mb->mpb, tk, 0, in, out, ctl, err_total, 0, TRANSPOSE ? mb->z : (double*)nullptr,
                                  mb->m, accumulate, tile, vec, part, &s_ok))
             break;
     }
@@ -2081,9 +2090,9 @@ int trsv_solve(oisat_ctx* h, const ChFactor& f, double* rhs_pad, double* fwd, co
     const int two = allow_two && grid <= h->cu_count ? 1 : 0;
     const size_t shm = sizeof(float) * NB * TLD * (two ? 2 : 1);
     OISAT_LAUNCH(h, "trsv_fwd", (trsv_pipe_kernel<0>), dim3(grid), dim3(256), shm, f.S, f.ld, (const float*)f.tinv, nb, rhs_pad, fwd,
-                 (TrsvCtl*)ctl, err_total, two, st, (double*)nullptr, (int64_t)0, 0);
+                 (TrsvCtl*)ctl, err_total, two, st, (double*)nullptr, (int64_t)0, 0, f.env);
     OISAT_LAUNCH(h, "trsv_bwd", (trsv_pipe_kernel<1>), dim3(grid), dim3(256), shm, f.S, f.ld, (const float*)f.tinv, nb, fwd, rhs_pad,
-                 (TrsvCtl*)(ctl + ctl_bytes), err_total, two, st, zout, f.m, accumulate);
+                 (TrsvCtl*)(ctl + ctl_bytes), err_total, two, st, zout, f.m, accumulate, f.env);
     return OISAT_OK;
 }
 
@@ -2192,7 +2201,8 @@ extern "C" int oisat_gemm_nt(oisat_ctx* h, float* C, int64_t ldc, const float* A
     return launch_gemm(h, "gemm_nt", C, ldc, A, lda, B, ldb, M, N, (int)K, mode, lower);
 }
 
-extern "C" int oisat_potrf(oisat_ctx* h, float* S, int64_t m, int64_t ld, int* info_host) {
+// first / env_dev: nullptr (dense), or the envelope of S (host: first[mpb]; device: first[mpb] | last[mpb], oisat_envelope)
+static int potrf_impl(oisat_ctx* h, float* S, int64_t m, int64_t ld, int* info_host, const int32_t* first, const int32_t* env_dev) {
     ARG_CHECK(h && S && m > 0);
     const int64_t mp = cdiv(m, NB) * NB;
     ARG_CHECK(ld >= mp && (ld % 4) == 0 && ((uintptr_t)S % 16) == 0);
@@ -2222,11 +2232,17 @@ extern "C" int oisat_potrf(oisat_ctx* h, float* S, int64_t m, int64_t ld, int* i
     }
     int rc;
     if (!lookahead && !getenv("OISAT_POTRF") && dag_wanted(h, mpb, 1) && dag_fits(1, dag_slots(h))) {
-        // the plan of this (S, tinv, ld, block rows) -- a handle keeps the last few (a lane that factors its tiles one after
-        // the other in ONE shared buffer meets the same few sizes month after month)
+        // the plan of this (S, tinv, ld, block rows, enveloped or not) -- a handle keeps the last few (a lane that factors its
+        // tiles one after the other in ONE shared buffer meets the same few sizes month after month).  An enveloped plan's
+        // ticket list belongs to ONE envelope: the table itself is compared, and another envelope refills the plan's buffers.
         DagSingle* hit = nullptr;
         for (DagSingle& c : h->dag_cache)
-            if (c.plan && c.S == S && c.tinv == tinv && c.ld == ld && c.mpb == mpb) hit = &c;
+            if (c.plan && c.S == S && c.tinv == tinv && c.ld == ld && c.mpb == mpb && c.enveloped == (first != nullptr)) hit = &c;
+        if (hit && first) {
+            DagPlan& pl = *(DagPlan*)hit->plan;
+            if (memcmp(pl.first.data(), first, sizeof(int) * (size_t)mpb) != 0)
+                if (int rf = dag_plan_refill(pl, first, h->stream)) return rf;
+        }
         if (!hit) {
             DagSingle* slot = nullptr;
             for (DagSingle& c : h->dag_cache)
@@ -2239,9 +2255,9 @@ extern "C" int oisat_potrf(oisat_ctx* h, float* S, int64_t m, int64_t ld, int* i
                 oisat_dag_plan_release(slot->plan);
                 slot->plan = nullptr;
             }
-            slot->plan = dag_plan_create(std::vector<BatchMat>{BatchMat{S, tinv, ld, m, (int)mpb, 0}}, h->stream);
+            slot->plan = dag_plan_create(std::vector<BatchMat>{BatchMat{S, tinv, ld, m, (int)mpb, 0}}, h->stream, DagSolveShape(), first);
             if (!slot->plan) return OISAT_ENOMEM;
-            slot->S = S; slot->tinv = tinv; slot->ld = ld; slot->mpb = mpb;
+            slot->S = S; slot->tinv = tinv; slot->ld = ld; slot->mpb = mpb; slot->enveloped = first != nullptr;
             hit = slot;
         }
         hit->stamp = ++h->dag_clock;
@@ -2255,6 +2271,7 @@ extern "C" int oisat_potrf(oisat_ctx* h, float* S, int64_t m, int64_t ld, int* i
     h->factor.mp = mp;
     h->factor.ld = ld;
     h->factor.tinv = tinv;
+    h->factor.env = env_dev;
     if (info_host) {
         int* pin = (int*)oisat_pinned(h, 64);
         if (!pin) return OISAT_ENOMEM;
@@ -2274,6 +2291,49 @@ extern "C" int oisat_potrf(oisat_ctx* h, float* S, int64_t m, int64_t ld, int* i
         }
     }
     return OISAT_OK;
+}
+
+extern "C" int oisat_potrf(oisat_ctx* h, float* S, int64_t m, int64_t ld, int* info_host) {
+    return potrf_impl(h, S, m, ld, info_host, nullptr, nullptr);
+}
+
+// OISAT_ENVELOPE=0: the enveloped entry points behave as their dense counterparts (A/B timing, tests); read at every call
+bool oisat_envelope_off() {
+    const char* e = getenv("OISAT_ENVELOPE");
+    return e != nullptr && atoi(e) == 0;
+}
+
+static bool envelope_table_ok(const int32_t* first, int64_t nb) {
+    for (int64_t i = 0; i < nb; ++i)
+        if (first[i] < 0 || first[i] > (i > 0 ? i - 1 : 0) || (i > 0 && first[i] < first[i - 1])) return false;
+    return true;
+}
+
+extern "C" int oisat_envelope(const double* lat_sorted, int64_t m, double g, int32_t* env_out) {
+    ARG_CHECK(lat_sorted && env_out && m > 0 && g >= 0.0);
+    const int64_t nb = cdiv(m, NB);
+    // the same cut-off as the float64 residual and the increment: great-circle distance >= latitude difference
+    const double angle = g > 0.0 ? lat_window_deg(g * (double)kLog2e) : 1e9;
+    for (int64_t i = 1; i < m; ++i) ARG_CHECK(lat_sorted[i] >= lat_sorted[i - 1]);
+    int64_t k = 0;
+    for (int64_t i = 0; i < nb; ++i) {
+        const double lo = lat_sorted[i * NB] - angle;           // tile k is outside when lat_max(tile k) < lat_min(tile i) - angle
+        while (k < i && lat_sorted[std::min((k + 1) * NB, m) - 1] < lo) ++k;
+        env_out[i] = (int32_t)std::min<int64_t>(k, i > 0 ? i - 1 : 0);
+    }
+    for (int64_t b = 0, j = 0; b < nb; ++b) {                   // last[b] = max{ j : first[j] <= b }
+        while (j + 1 < nb && env_out[j + 1] <= b) ++j;
+        env_out[nb + b] = (int32_t)j;
+    }
+    return OISAT_OK;
+}
+
+extern "C" int oisat_potrf_env(oisat_ctx* h, float* S, int64_t m, int64_t ld, const int32_t* first, const int32_t* env_dev,
+                               int* info_host) {
+    ARG_CHECK(h && first && env_dev && m > 0);
+    ARG_CHECK(envelope_table_ok(first, cdiv(m, NB)));
+    if (oisat_envelope_off()) return potrf_impl(h, S, m, ld, info_host, nullptr, nullptr);
+    return potrf_impl(h, S, m, ld, info_host, first, env_dev);
 }
 
 extern "C" int oisat_potrs(oisat_ctx* h, const float* L, int64_t m, int64_t ld, double* z_inout) {
@@ -2813,6 +2873,7 @@ extern "C" int oisat_factor_adopt(oisat_ctx* h, const float* L, int64_t m, int64
     h->factor.mp = mp;
     h->factor.ld = ld;
     h->factor.tinv = tinv;
+    h->factor.env = nullptr;                                // (adopted without an envelope: swept densely)
     return OISAT_OK;
 }
 

@@ -15,9 +15,13 @@
 namespace {
 
 // ---- S = sig sig^T .* C + diag(var), lower 64x64 tiles (diagonal tiles complete) ----------------
+// ENV: first[mp/128] (device) is the block envelope of a latitude-sorted system (oisat_envelope).  A tile left of its row's
+// envelope holds correlations below the library's cut-off only: it is not evaluated but filled with exact zeros, so that every
+// reader of S or of its factor that does not know the envelope finds zeros there (never what an earlier system left).
+template <bool ENV>
 __global__ __launch_bounds__(256) void cov_build_kernel(const double* __restrict__ oxyz, const double* __restrict__ osig,
                                                          const double* __restrict__ ovar, int64_t m, int64_t mp, float g2,
-                                                         float* __restrict__ S, int64_t ld, int ntile) {
+                                                         float* __restrict__ S, int64_t ld, int ntile, const int* __restrict__ first) {
     // triangular tile index -> (ti >= tj)
     const int64_t b = blockIdx.x;
     int ti = (int)((sqrt(8.0 * (double)b + 1.0) - 1.0) * 0.5);
@@ -26,6 +30,14 @@ __global__ __launch_bounds__(256) void cov_build_kernel(const double* __restrict
     const int tj = (int)(b - (int64_t)ti * (ti + 1) / 2);
     __shared__ float4 pa[64], pb[64];            // x, y, z, sig
     const int t = threadIdx.x;
+    if (ENV && (tj >> 1) < first[ti >> 1]) {     // (block-uniform)
+#pragma unroll
+        for (int rr = 0; rr < 4; ++rr) {
+            const int64_t grow = (int64_t)ti * 64 + (t >> 4) + rr * 16;
+            if (grow < mp) *reinterpret_cast<float4*>(&S[grow * ld + (int64_t)tj * 64 + (t & 15) * 4]) = make_float4(0.f, 0.f, 0.f, 0.f);
+        }
+        return;
+    }
     if (t < 128) {
         const int64_t row = (t < 64 ? (int64_t)ti * 64 + t : (int64_t)tj * 64 + (t - 64));
         float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -179,8 +191,23 @@ extern "C" int oisat_cov_build(oisat_ctx* h, const double* oxyz, const double* o
     const int ntile = (int)(mp / 64);
     const int64_t nblk = (int64_t)ntile * (ntile + 1) / 2;
     ARG_CHECK(nblk < (int64_t)INT32_MAX);
-    OISAT_LAUNCH(h, "cov_build", cov_build_kernel, dim3((unsigned)nblk), dim3(256), 0, oxyz, osig, ovar, m, mp,
-                 (float)(g * (double)kLog2e), S, ld, ntile);
+    OISAT_LAUNCH(h, "cov_build", cov_build_kernel<false>, dim3((unsigned)nblk), dim3(256), 0, oxyz, osig, ovar, m, mp,
+                 (float)(g * (double)kLog2e), S, ld, ntile, (const int*)nullptr);
+    return OISAT_OK;
+}
+
+extern "C" int oisat_cov_build_env(oisat_ctx* h, const double* oxyz, const double* osig, const double* ovar, int64_t m, double g,
+                                   float* S, int64_t ld, const int32_t* env_dev) {
+    ARG_CHECK(env_dev != nullptr);
+    if (oisat_envelope_off()) return oisat_cov_build(h, oxyz, osig, ovar, m, g, S, ld);
+    ARG_CHECK(h && oxyz && osig && ovar && S && m > 0 && g >= 0.0);
+    const int64_t mp = cdiv(m, 128) * 128;
+    ARG_CHECK(ld >= mp && (ld % 4) == 0 && ((uintptr_t)S % 16) == 0);
+    const int ntile = (int)(mp / 64);
+    const int64_t nblk = (int64_t)ntile * (ntile + 1) / 2;
+    ARG_CHECK(nblk < (int64_t)INT32_MAX);
+    OISAT_LAUNCH(h, "cov_build", cov_build_kernel<true>, dim3((unsigned)nblk), dim3(256), 0, oxyz, osig, ovar, m, mp,
+                 (float)(g * (double)kLog2e), S, ld, ntile, (const int*)env_dev);
     return OISAT_OK;
 }
 

@@ -244,8 +244,10 @@ __device__ __forceinline__ const float* dag_src(const float* tile0, int64_t ld, 
 }
 
 // bulk task on tile (i, j) of system sy: kind DAG_TILE (i >= j + 2: k < j, then the panel product, publishes rowfin[i] = j + 1),
-// DAG_SUB (i = j + 1: k < j, leaves the updated tile, publishes sub[j]), DAG_PRE (i = j: k < j - 1, publishes pre[j])
-__device__ __forceinline__ bool dag_tile_task(const DagSys& sy, int kind, int i, int j, DagCtl* ctl, float* lds, const DagLane& L, int* s_flag,
+// DAG_SUB (i = j + 1: k < j, leaves the updated tile, publishes sub[j]), DAG_PRE (i = j: k < j - 1, publishes pre[j]).
+// k0 (wave-uniform, from the ticket): the K-loop's first block column -- 0, or first[i] of an ENVELOPED system ("Envelope" at
+// dag_task_order): the blocks left of it are exact zeros that nobody wrote or reads, final by definition.
+__device__ __forceinline__ bool dag_tile_task(const DagSys& sy, int kind, int k0, int i, int j, DagCtl* ctl, float* lds, const DagLane& L, int* s_flag,
                                               int* s_kav, long long* tr /* thread 0, tracing: [2] += time spent polling */) {
     const int t = threadIdx.x;
     const int kend = kind == DAG_PRE ? j - 1 : j;
@@ -255,7 +257,7 @@ __device__ __forceinline__ bool dag_tile_task(const DagSys& sy, int kind, int i,
     const float* Arow = sy.S + (int64_t)i * NB * sy.ld;
     const float* Brow = sy.S + (int64_t)j * NB * sy.ld;
     f32x16 acc00 = {0}, acc01 = {0}, acc10 = {0}, acc11 = {0};
-    int k = 0;
+    int k = k0;
     while (k < kend) {
         bool ok = true;
         if (t == 0) {                                           // how far are the two row panels final?
@@ -288,7 +290,7 @@ __device__ __forceinline__ bool dag_tile_task(const DagSys& sy, int kind, int i,
         }
         return true;
     }
-    if (kend > 0) {                                             // X = S(i,j) - acc back to the tile: the panel product reads it as an operand
+    if (kend > k0) {                                            // X = S(i,j) - acc back to the tile: the panel product reads it as an operand
         dag_epilogue<true>(Cq, sy.ld, L, acc00, acc01, acc10, acc11);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     }
@@ -595,7 +597,7 @@ __device__ __forceinline__ bool dag_sweep_task(const DagSys& sy, const SolveMemb
     __syncthreads();
     double* in = TRANSPOSE ? mb.fwd : mb.rhs;
     double* out = TRANSPOSE ? mb.rhs : mb.fwd;
-    if (!trsv_row<TRANSPOSE, true>(mb.S, mb.ld, mb.tinv, nb, tk, in, out, reinterpret_cast<TrsvCtl*>(ctl), sv.trsv_timeouts, 0,
+    if (!trsv_row<TRANSPOSE, true>(mb.S, mb.ld, mb.tinv, nb, tk, 0, in, out, reinterpret_cast<TrsvCtl*>(ctl), sv.trsv_timeouts, 0,
                                    TRANSPOSE ? mb.z : (double*)nullptr, mb.m, round > 0 ? 1 : 0, tile, vec, part, s_ok)) {
         __builtin_amdgcn_s_setprio(0);
         return false;
@@ -862,11 +864,11 @@ __global__ __launch_bounds__(256, 2) void potrf_dag_kernel(const DagSys* __restr
             else if (task.x == DAG_RES) ok = dag_res_task(sy, mb, task.y, task.z, task.w, sv, ctl, info, lds, &s_kav, L.spin);
             else if (sv.dtype == OISAT_F32) ok = dag_inc_task<float>(sy, mb, task.z, task.w, sv, ctl, lds);
             else ok = dag_inc_task<double>(sy, mb, task.z, task.w, sv, ctl, lds);
-        } else if (task.x == DAG_CHAIN) {
+        } else if ((task.x & 255) == DAG_CHAIN) {
             ok = dag_chain_task(sy, ctl, info, lds, L, &s_flag, trace ? trace + 4 * (int64_t)(ntasks + (SOLVE ? sv.qcap : 0)) + 8 * (int64_t)task.z : nullptr,
                                 SOLVE ? &sv : (const DagSolve*)nullptr);
         } else {
-            ok = dag_tile_task(sy, task.x, task.z, task.w, ctl, lds, L, &s_flag, &s_kav, tr);
+            ok = dag_tile_task(sy, task.x & 255, task.x >> 8, task.z, task.w, ctl, lds, L, &s_flag, &s_kav, tr);      // (kind | k0 << 8)
         }
         if (tr && t == 0) {
             tr[1] = wall_clock64();
@@ -929,6 +931,8 @@ struct DagPlan {
     unsigned long long* queue_dev = nullptr;
     std::vector<DagSys> sys_host;
     std::vector<int4> tasks_host;
+    std::vector<int> first;                                     // the envelope this single-system plan's ticket list was made for (empty: dense)
+    size_t tasks_cap = 0;                                       // tickets tasks_dev holds (an enveloped plan: the dense list's, so a new envelope refills it)
     long long* trace_dev = nullptr;                             // OISAT_DAG_TRACE: [ntasks][4] + [chain_rows][8] stamps of the last launch
 };
 
@@ -950,8 +954,16 @@ struct DagOrder {
     int chain_rows = 0, reserve_chains = 0, max_wave_chains = 0;
 };
 constexpr int kDagWave = 8;                                     // systems per wave of small systems (12, 16, 24 and 48 measure the same to 0.2 ms of a month's 48.7)
+constexpr double kDagEnvLead = 0.1;                             // enveloped systems: columns a task is drawn early per block of its K-loop (below)
 constexpr int kDagWave0Max = 64;                                // wave 0 holds at most this many chains
-void dag_task_order(const std::vector<int>& nb_of, int wave_arg, DagOrder& out) {
+// Envelope (first != nullptr: ONE system whose rows are in an order that makes it a band, first[i] = first block column of
+// block row i that can be non-zero, non-decreasing, first[i] <= max(i - 1, 0)).  A Cholesky factor has no fill left of its
+// matrix's envelope, so T(i, j) exists only for first[i] <= j and every K-loop of row i starts at k0 = first[i] (>= first[j]
+// of the other operand row, j < i), which rides in the ticket's first word (kind | k0 << 8).  rowfin[i] keeps its meaning:
+// the row's first task publishes first[i] + 1 and every wait is for rowfin >= k + 1 with k >= k0.  PRE(j) and SUB(j) are
+// always emitted (the sub-diagonal tile is inside every envelope), so the chain is unchanged; the order -- column-major with the
+// deep tasks drawn early, "Enveloped" below -- stays topological.
+void dag_task_order(const std::vector<int>& nb_of, int wave_arg, DagOrder& out, const int* first = nullptr) {
     const int nsys = (int)nb_of.size();
     // Ticket order.  Systems are taken in WAVES.  The BIG systems -- those with at least half the block rows of the largest
     // (a month's polar caps; at most 64) -- go two at a time, the others (table order, largest first) eight at a time.  A
@@ -1013,13 +1025,23 @@ void dag_task_order(const std::vector<int>& nb_of, int wave_arg, DagOrder& out) 
             const int nb = nb_of[s];
             for (int j = 0; j < nb; ++j) {
                 const double key = (double)j / (double)nb;
+                // Enveloped: the K-depth of a task, d = j - first[i], varies within a column from 0 (the band's far edge) to the
+                // band's width (SUB(j), PRE(j) and the rows next to the diagonal: 110 blocks = 1.4 ms of K-loop in the headline
+                // system), while a column passes in ~0.2 ms: drawn column by column, the deep tasks -- the chain's own inputs
+                // first of all -- start far too late (traced: the chain waited 354 us of every step for sub(j), tile tasks
+                // polled 37 % of the time they held a slot) and the shallow ones hold slots polling.  So a task is drawn
+                // kDagEnvLead x d columns early.  Still topological: a task's inputs have a smaller column AND no larger first[],
+                // hence a smaller key for any lead < 1; and no tile of a later column gets in front of SUB(j) / PRE(j + 1), which
+                // is what the drain condition needs.  Headline step: lead 0 / 0.05 / 0.1 / 0.2 / 0.4 = 217.9 / 186.7 / 180.3 / 180.9 / 184.3 ms.
+                auto ekey = [&](int i, int jj) { return ((double)jj - kDagEnvLead * (double)(jj - first[i])) / (double)nb; };
                 // PRE(j) reads row j up to column j - 2 only (the chain adds column j - 1 itself), so it is drawn ONE COLUMN EARLY,
                 // in front of column j - 1's tasks: drawn with column j it was what a small system's chain waited for at every
                 // step (58 us of a 141-us step; the tile tasks of column j then polled for T_j: 37 -> 16 us per task).  The
                 // wait moves to SUB(j), which cannot start its last block before column j - 1 is out; a month: 48.9 -> 48.5 ms.
-                if (j >= 2) items.push_back(Item{(double)(j - 1) / (double)nb - 1e-9, int4{DAG_PRE, s, j, j}});
-                if (j >= 1 && j + 1 < nb) items.push_back(Item{key, int4{DAG_SUB, s, j + 1, j}});
-                for (int i = j + 2; i < nb; ++i) items.push_back(Item{key, int4{DAG_TILE, s, i, j}});
+                if (j >= 2) items.push_back(Item{(first ? ekey(j, j - 1) : (double)(j - 1) / (double)nb) - 1e-9, int4{DAG_PRE | (first ? first[j] << 8 : 0), s, j, j}});
+                if (j >= 1 && j + 1 < nb) items.push_back(Item{first ? ekey(j + 1, j) : key, int4{DAG_SUB | (first ? first[j + 1] << 8 : 0), s, j + 1, j}});
+                for (int i = j + 2; i < nb && (!first || first[i] <= j); ++i)
+                    items.push_back(Item{first ? ekey(i, j) : key, int4{DAG_TILE | (first ? first[i] << 8 : 0), s, i, j}});
             }
         }
         std::stable_sort(items.begin(), items.end(), [](const Item& a, const Item& b) { return a.key < b.key; });
@@ -1059,7 +1081,9 @@ static inline int dag_slots(const oisat_ctx* h) { return 2 * (h->cu_count > 0 ? 
 // The progress words and the control block are zeroed ON `stream` (the stream the plan's launches go to): a plain hipMemset is
 // ordered in the NULL stream only, which the handles' non-blocking streams do not wait for -- a launch could start on
 // uninitialised words (wrong tickets, flags that read "ready").
-DagPlan* dag_plan_create(const std::vector<BatchMat>& table, hipStream_t stream, const DagSolveShape& shape = DagSolveShape()) {
+// first (single system only): its envelope; the ticket buffer is then sized for the dense list of these block rows
+DagPlan* dag_plan_create(const std::vector<BatchMat>& table, hipStream_t stream, const DagSolveShape& shape = DagSolveShape(),
+                         const int* first = nullptr) {
     DagPlan* p = new DagPlan();
     const int nsys = (int)table.size();
     p->nsys = nsys;
@@ -1076,7 +1100,8 @@ DagPlan* dag_plan_create(const std::vector<BatchMat>& table, hipStream_t stream,
     {
         std::vector<int> nb_of(nsys);
         for (int s = 0; s < nsys; ++s) nb_of[s] = table[s].mpb;
-        dag_task_order(nb_of, 0, order);
+        dag_task_order(nb_of, 0, order, nsys == 1 ? first : nullptr);
+        if (first && nsys == 1) p->first.assign(first, first + nb_of[0]);
         if (shape.refine >= 0) {
             int64_t rows = 0, valu = 0;
             dag_queue_entries(nb_of, shape, &rows, &valu);
@@ -1091,8 +1116,13 @@ DagPlan* dag_plan_create(const std::vector<BatchMat>& table, hipStream_t stream,
     p->reserve_chains = order.reserve_chains;
     p->ntasks = (int)tasks.size();
     p->tasks_host = tasks;
+    p->tasks_cap = tasks.size();
+    if (!p->first.empty()) {                                    // chain + PRE + SUB + every lower tile two or more below the diagonal
+        const size_t nb = (size_t)table[0].mpb;
+        p->tasks_cap = 1 + 2 * nb + nb * (nb + 1) / 2;
+    }
     bool ok = hipMalloc((void**)&p->sys_dev, sizeof(DagSys) * nsys) == hipSuccess &&
-              hipMalloc((void**)&p->tasks_dev, sizeof(int4) * tasks.size()) == hipSuccess &&
+              hipMalloc((void**)&p->tasks_dev, sizeof(int4) * p->tasks_cap) == hipSuccess &&
               hipMalloc((void**)&p->state_dev, sizeof(int) * words) == hipSuccess &&
               hipMalloc((void**)&p->ctl_dev, sizeof(DagCtl)) == hipSuccess &&
               (p->qcap == 0 || (p->qcap < (int64_t)INT32_MAX / 4 && hipMalloc((void**)&p->queue_dev, 16 * (size_t)p->qcap) == hipSuccess));
@@ -1111,6 +1141,28 @@ DagPlan* dag_plan_create(const std::vector<BatchMat>& table, hipStream_t stream,
         return nullptr;
     }
     return p;
+}
+
+// A cached enveloped plan meets another envelope (same matrix, same block rows): new ticket list into the SAME buffers.  The
+// copy is enqueued on `stream`, behind the launches that still read the old list.
+int dag_plan_refill(DagPlan& p, const int* first, hipStream_t stream) {
+    const int nb = p.sys_host[0].nb;
+    DagOrder order;
+    dag_task_order(std::vector<int>{nb}, 0, order, first);
+    if (order.tasks.size() > p.tasks_cap) {
+        oisat_set_error("task-graph factorization: %zu tickets do not fit the plan's %zu", order.tasks.size(), p.tasks_cap);
+        return OISAT_EINVAL;
+    }
+    HIP_TRY(hipStreamSynchronize(stream));                      // (the host list is the source of a copy that may still be in flight)
+    p.tasks_host = order.tasks;
+    p.ntasks = (int)order.tasks.size();
+    p.first.assign(first, first + nb);
+    p.max_wave_chains = order.max_wave_chains;
+    p.chain_rows = order.chain_rows;
+    p.reserve_chains = order.reserve_chains;
+    if (p.trace_dev) { (void)hipFree(p.trace_dev); p.trace_dev = nullptr; }      // (profiling aid: sized by the ticket count)
+    HIP_TRY(hipMemcpyAsync(p.tasks_dev, p.tasks_host.data(), sizeof(int4) * p.tasks_host.size(), hipMemcpyHostToDevice, stream));
+    return OISAT_OK;
 }
 
 // OISAT_DAG_TRACE=file (profiling aid): the launch is followed by a synchronisation and its stamps are written to `file`:

@@ -32,6 +32,7 @@ struct ChFactor {                // what the triangular solves need besides L: t
     const float* S = nullptr;
     int64_t m = 0, mp = 0, ld = 0;
     float* tinv = nullptr;       // [mp/128][128][128]: inverted diagonal blocks, row-major
+    const int* env = nullptr;    // device, first[mp/128] | last[mp/128]: the factor's block envelope (oisat_potrf_env), or nullptr = dense
 };
 
 struct BatchMat {                // one matrix of a batched factorization (device table entry)
@@ -99,6 +100,7 @@ struct DagSingle {               // a cached single-system task-graph plan (oisa
     const float* S = nullptr;
     const float* tinv = nullptr;
     int64_t ld = 0, mpb = 0;
+    bool enveloped = false;      // its ticket list follows an envelope (the plan keeps the table it was made for)
     uint64_t stamp = 0;
 };
 
@@ -165,6 +167,7 @@ struct oisat_ctx {
 // workspace slot `slot` of at least `bytes` (grow-only); returns nullptr + error on failure
 void* oisat_ws(oisat_ctx* h, int slot, size_t bytes);
 void* oisat_pinned(oisat_ctx* h, size_t bytes);
+bool oisat_envelope_off();                              // dense_chol.hip: OISAT_ENVELOPE=0 -- the enveloped entry points run dense
 void oisat_dag_plan_release(void* plan);                // dense_chol.hip: frees a task-graph plan (nullptr allowed)
 
 int oisat_prof_begin(oisat_ctx* h, const char* name);   // returns pending index or -1

@@ -12,7 +12,9 @@ it the check is the float64 restatement in ``oracle/`` ("parity unpinned", DESIG
 Pipeline (all in HBM, csrc/dense_cov.hip + csrc/dense_chol.hip):
 ``oisat_innovation`` -> ``oisat_cov_build`` (S, fp32) -> ``oisat_potrf`` (MFMA fp32 Cholesky) ->
 ``oisat_gain_solve`` (triangular solves + float64-residual refinement) -> ``oisat_apply_increment``
-(B H^T z generated on the fly, never stored).
+(B H^T z generated on the fly, never stored).  ``DenseAnalysis.run()`` owns the latitude sort of its observations and
+therefore builds and factors only the covariance's latitude envelope (``oisat_envelope`` -> ``oisat_cov_build_env`` ->
+``oisat_potrf_env``).
 """
 from __future__ import annotations
 
@@ -129,6 +131,9 @@ class DenseAnalysis:
         self.perm = c.alloc(self.max_obs * 4)
         if batched:
             self.perm.shared_with_other_streams()
+        # the block envelope of the latitude-sorted system (``oisat_envelope``): first | last, 2 x mp_max / 128 words
+        self.env = c.alloc(2 * (self.mp_max // NB) * 4)
+        self._env_host, self._env_g = None, None
         self.m = 0
         self._direct_innovation = False
         # every internal workspace of the solve is sized here, so that run() never allocates (include/oisat.h)
@@ -165,13 +170,26 @@ class DenseAnalysis:
         (``download_z``, ``gain_diag``) are handed back in the caller's order."""
         lat = np.ravel(np.asarray(obs_lat, dtype=np.float64))
         self._order = np.argsort(lat, kind="stable")
-        self.ctx.upload_into(self.olat.ptr, lat[self._order], dtype=np.float64)
+        self._lat_sorted = np.ascontiguousarray(lat[self._order])
+        self._env_host = None                                  # (belongs to these observations and one L: made by run())
+        self.ctx.upload_into(self.olat.ptr, self._lat_sorted, dtype=np.float64)
         # ... and the float64 residual takes its blocks of 64 rows along a space-filling curve through them (Morton order of
         # latitude x longitude, as a permutation of the latitude order): neighbours in space, a small bounding sphere
         # (``oisat_set_obs_blocks``)
         lon = np.ravel(np.asarray(obs_lon, dtype=np.float64))[self._order]
         self.ctx.upload_into(self.perm.ptr, morton_order(lat[self._order], lon))
         return self._order
+
+    def _envelope(self, g):
+        """Host table ``first`` of this plan's observations at decay constant ``g`` (the library's rule and cut-off:
+        ``oisat_envelope``); its device copy ``first | last`` is in ``self.env``.  Made once per (observations, L)."""
+        if self._env_host is None or self._env_g != g:
+            nb = self.mp // NB
+            env = np.empty(2 * nb, dtype=np.int32)
+            self.ctx.check(self.ctx.lib.oisat_envelope(self._lat_sorted.ctypes.data, self.m, g, env.ctypes.data))
+            self.ctx.upload_into(self.env.ptr, env)
+            self._env_host, self._env_g = env, g
+        return self._env_host
 
     def _unsort(self, per_obs):
         out = np.empty_like(per_obs)
@@ -206,9 +224,12 @@ class DenseAnalysis:
         xb, xa, inc = self.xb_ptr, self.out_ptr, self.out_ptr + self.n * item
         if not self._direct_innovation:
             c.check(lib.oisat_innovation(h, self.code, xb, self.ocell.ptr, self.oy.ptr, m, self.d.ptr))
-        c.check(lib.oisat_cov_build(h, self.oxyz.ptr, self.osig.ptr, self.ovar.ptr, m, g, self.S.ptr, ld))
+        # this plan owns the latitude sort, so it may use the covariance's envelope: only the tiles inside it are evaluated
+        # and factored, the sweeps of the gain solve walk inside it (OISAT_ENVELOPE=0: the dense path, in the library)
+        first = self._envelope(g)
+        c.check(lib.oisat_cov_build_env(h, self.oxyz.ptr, self.osig.ptr, self.ovar.ptr, m, g, self.S.ptr, ld, self.env.ptr))
         info = C.c_int(0)
-        c.check(lib.oisat_potrf(h, self.S.ptr, m, ld, C.byref(info) if check_pd else None))
+        c.check(lib.oisat_potrf_env(h, self.S.ptr, m, ld, first.ctypes.data, self.env.ptr, C.byref(info) if check_pd else None))
         resid = (C.c_double * (refine + 1))() if want_resid else None
         c.check(lib.oisat_set_obs_blocks(h, self.perm.ptr, m))                                  # per run: handles are shared
         c.check(lib.oisat_gain_solve(h, self.S.ptr, self.oxyz.ptr, self.osig.ptr, self.ovar.ptr, m, ld, g, self.d.ptr,

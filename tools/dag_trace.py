@@ -11,7 +11,8 @@ import numpy as np
 def parse(path):
     raw = open(path, "rb").read()
     nt, cr = np.frombuffer(raw, np.int32, 2)
-    tasks = np.frombuffer(raw, np.int32, 4 * nt, 8).reshape(nt, 4)
+    tasks = np.frombuffer(raw, np.int32, 4 * nt, 8).reshape(nt, 4).copy()
+    tasks[tasks[:, 0] >= 0, 0] &= 255                    # (an enveloped plan's tickets carry the K-loop's first block column above the kind)
     st = np.frombuffer(raw, np.int64, 4 * nt + 8 * cr, 8 + 16 * nt)
     return tasks, st[:4 * nt].reshape(nt, 4), st[4 * nt:].reshape(cr, 8)
 
@@ -40,7 +41,8 @@ def report(path):
     for c in np.where(tasks[:, 0] == 0)[0]:
         sysid, r0 = tasks[c, 1], tasks[c, 2]
         nxt = [tasks[d, 2] for d in np.where(tasks[:, 0] == 0)[0] if tasks[d, 2] > r0]
-        r1 = min(nxt) if nxt else len(ch)
+        own = (tasks[:, 1] == sysid) & (tasks[:, 0] > 0)
+        r1 = min(nxt) if nxt else (r0 + tasks[own, 2].max() + 1 if own.any() else len(ch))      # (behind the chains' rows: one row per workgroup)
         s = ch[r0:r1]
         nb = len(s)
         if nb < 3:
