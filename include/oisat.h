@@ -381,8 +381,18 @@ int oisat_potrf(oisat_ctx* h, float* S, int64_t m, int64_t ld, int* info_host);
  *                                                          read densely and find the zeros of the build
  *   oisat_potrf, oisat_factor_adopt                        forget the envelope (dense sweeps from then on)
  * OISAT_ENVELOPE=0 in the environment (read at every call) makes both entry points behave exactly as oisat_cov_build /
- * oisat_potrf: the dense path, for A/B timing and tests. */
+ * oisat_potrf: the dense path, for A/B timing and tests.
+ *
+ * oisat_factor_envelope (host only): the same table for the fp32 FACTOR, which oisat_gain_solve uses as a
+ * preconditioner only (it refines against the float64 residual of the full S, cut off at 2^-52 as before).  Where the
+ * factorization is bound by tile work (more than ~1 500 K-loop steps per block row inside the narrow table) the
+ * table is cut at the factor's own, larger correlation (kFactorCutBits, csrc/dense_chol.hip); for every smaller
+ * system, whose factorization is its chain, it is oisat_envelope's table word for word.  first[] is nowhere smaller
+ * than oisat_envelope's.  This is the table DenseAnalysis.run() builds, factors and sweeps with.
+ * OISAT_FACTOR_CUT_BITS=<n> in the environment (read at every call; 1 <= n <= 52, anything else is OISAT_EINVAL) forces
+ * the cut-off 2^-n for every size; 52 reproduces oisat_envelope's table exactly. */
 int oisat_envelope(const double* lat_sorted, int64_t m, double g, int32_t* env_out);
+int oisat_factor_envelope(const double* lat_sorted, int64_t m, double g, int32_t* env_out);
 int oisat_cov_build_env(oisat_ctx* h, const double* oxyz, const double* osig, const double* ovar, int64_t m,
                         double g, float* S, int64_t ld, const int32_t* env_dev);
 int oisat_potrf_env(oisat_ctx* h, float* S, int64_t m, int64_t ld, const int32_t* first, const int32_t* env_dev,

@@ -2309,12 +2309,26 @@ static bool envelope_table_ok(const int32_t* first, int64_t nb) {
     return true;
 }
 
-extern "C" int oisat_envelope(const double* lat_sorted, int64_t m, double g, int32_t* env_out) {
-    ARG_CHECK(lat_sorted && env_out && m > 0 && g >= 0.0);
+// The fp32 factor's own cut-off.  The factor is only the preconditioner of oisat_gain_solve, which refines against the
+// float64 residual of the true S (that residual keeps kCutBits): entries of S far below what an fp32 factorization loses by
+// itself (first residual 3e-6 .. 2.4e-5) are work the result does not need.  Chosen by a sweep on MI355X over the headline
+// month in three species and the month of test_dense_config3_full_size_properties (profiles/EXPERIMENTS.md, "The factor's
+// own cut-off"): 40 .. 24 bits leave the first residual within 0.7 %, the number of solves and the
+// last residual (within 6 %) where 52 bits have them on all four months, 20 bits raise the first residual by 6 - 8 %.  Kept:
+// the smallest admissible value, 24, plus 4 bits of headroom for a month denser than the benchmark's (the dropped row sums
+// of a 1e5-observation month lie ~4 bits above those of a 2e4-observation month).  Headline: 2 520 648 of 4 549 882 K-steps.
+constexpr double kFactorCutBits = 28.0;
+// The narrow table is used only where it buys time: a step of the factorization's chain costs ~47 us, a 128-deep K-block
+// ~15.9 us of one of 512 workgroup slots, so tile work outlasts the chain once a block row holds more than
+// 47 x 512 / 15.9 ~ 1 500 K-steps.  Below that (config 2: 228, a 2e4-observation swath month: 251) the launch IS its chain,
+// fewer K-steps win nothing, and the factor keeps the 2^-52 table and with it the bits it has always had.
+constexpr double kFactorMinKstepsPerRow = 1500.0;
+
+// first | last for the pairs whose correlation can reach 2^-bits (lat_sorted checked by the caller): their latitudes differ
+// by at most the angle of that cut-off's chord, great-circle distance >= latitude difference
+static void envelope_table(const double* lat_sorted, int64_t m, double g, double bits, int32_t* env_out) {
     const int64_t nb = cdiv(m, NB);
-    // the same cut-off as the float64 residual and the increment: great-circle distance >= latitude difference
-    const double angle = g > 0.0 ? lat_window_deg(g * (double)kLog2e) : 1e9;
-    for (int64_t i = 1; i < m; ++i) ARG_CHECK(lat_sorted[i] >= lat_sorted[i - 1]);
+    const double angle = g > 0.0 ? lat_window_deg(g * (double)kLog2e, bits) : 1e9;
     int64_t k = 0;
     for (int64_t i = 0; i < nb; ++i) {
         const double lo = lat_sorted[i * NB] - angle;           // tile k is outside when lat_max(tile k) < lat_min(tile i) - angle
@@ -2325,6 +2339,39 @@ extern "C" int oisat_envelope(const double* lat_sorted, int64_t m, double g, int
         while (j + 1 < nb && env_out[j + 1] <= b) ++j;
         env_out[nb + b] = (int32_t)j;
     }
+}
+
+// K-loop steps of the enveloped factorization: sum over the tiles (i, j) inside the table of j - max(first[i], first[j])
+static int64_t envelope_ksteps(const int32_t* first, int64_t nb) {
+    int64_t k = 0;
+    for (int64_t i = 0; i < nb; ++i)
+        for (int64_t j = first[i]; j <= i; ++j) k += j - std::max(first[i], first[j]);
+    return k;
+}
+
+extern "C" int oisat_envelope(const double* lat_sorted, int64_t m, double g, int32_t* env_out) {
+    ARG_CHECK(lat_sorted && env_out && m > 0 && g >= 0.0);
+    for (int64_t i = 1; i < m; ++i) ARG_CHECK(lat_sorted[i] >= lat_sorted[i - 1]);
+    envelope_table(lat_sorted, m, g, kCutBits, env_out);       // the same cut-off as the float64 residual and the increment
+    return OISAT_OK;
+}
+
+extern "C" int oisat_factor_envelope(const double* lat_sorted, int64_t m, double g, int32_t* env_out) {
+    ARG_CHECK(lat_sorted && env_out && m > 0 && g >= 0.0);
+    for (int64_t i = 1; i < m; ++i) ARG_CHECK(lat_sorted[i] >= lat_sorted[i - 1]);
+    double bits = kFactorCutBits;
+    bool forced = false;
+    const char* e = getenv("OISAT_FACTOR_CUT_BITS");            // read at every call, like OISAT_ENVELOPE
+    if (e && *e) {
+        char* end = nullptr;
+        bits = strtod(e, &end);
+        ARG_CHECK(end != e && *end == '\0' && bits >= 1.0 && bits <= kCutBits);
+        forced = true;
+    }
+    const int64_t nb = cdiv(m, NB);
+    envelope_table(lat_sorted, m, g, bits, env_out);
+    if (!forced && (double)envelope_ksteps(env_out, nb) <= kFactorMinKstepsPerRow * (double)nb)
+        envelope_table(lat_sorted, m, g, kCutBits, env_out);   // chain-bound: nothing to win, keep the float64 sums' table
     return OISAT_OK;
 }
 

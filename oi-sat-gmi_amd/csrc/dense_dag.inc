@@ -954,7 +954,7 @@ struct DagOrder {
     int chain_rows = 0, reserve_chains = 0, max_wave_chains = 0;
 };
 constexpr int kDagWave = 8;                                     // systems per wave of small systems (12, 16, 24 and 48 measure the same to 0.2 ms of a month's 48.7)
-constexpr double kDagEnvLead = 0.1;                             // enveloped systems: columns a task is drawn early per block of its K-loop (below)
+constexpr double kDagEnvLead = 0.15;                            // enveloped systems: columns a task is drawn early per block of its K-loop (below)
 constexpr int kDagWave0Max = 64;                                // wave 0 holds at most this many chains
 // Envelope (first != nullptr: ONE system whose rows are in an order that makes it a band, first[i] = first block column of
 // block row i that can be non-zero, non-decreasing, first[i] <= max(i - 1, 0)).  A Cholesky factor has no fill left of its
@@ -1033,6 +1033,11 @@ void dag_task_order(const std::vector<int>& nb_of, int wave_arg, DagOrder& out, 
                 // kDagEnvLead x d columns early.  Still topological: a task's inputs have a smaller column AND no larger first[],
                 // hence a smaller key for any lead < 1; and no tile of a later column gets in front of SUB(j) / PRE(j + 1), which
                 // is what the drain condition needs.  Headline step: lead 0 / 0.05 / 0.1 / 0.2 / 0.4 = 217.9 / 186.7 / 180.3 / 180.9 / 184.3 ms.
+                // That sweep was at the 2^-52 band.  With the factor's own band (2^-28, oisat_factor_envelope: deepest K-loop 80 blocks,
+                // tasks of 41 blocks on average) 0.1 leaves tile tasks polling 130 us of the 700 they hold a slot, 413 of 512 workgroups
+                // computing: lead 0.05 / 0.1 / 0.15 / 0.2 / 0.25 / 0.3 = 128.8 / 116.2 / 111.0 / 110.7 / 111.3 / 111.3 ms per step (0.15 .. 0.3
+                // within the spread between calls); 0.15 is kept, the smallest of the flat stretch -- at the 2^-52 band (override
+                // only) it costs 0.4 % (181.1 -> 181.9 ms).
                 auto ekey = [&](int i, int jj) { return ((double)jj - kDagEnvLead * (double)(jj - first[i])) / (double)nb; };
                 // PRE(j) reads row j up to column j - 2 only (the chain adds column j - 1 itself), so it is drawn ONE COLUMN EARLY,
                 // in front of column j - 1's tasks: drawn with column j it was what a small system's chain waited for at every

@@ -15,8 +15,8 @@ constexpr double kCutBits = 52.0;
 // last bit times the cancellation factor, and two points whose latitudes differ by more than the matching angle are
 // at least that far apart.  With the observations sorted by latitude the pairs worth evaluating for a block of rows /
 // cells are therefore one contiguous index range, found by two binary searches.  (3.6x fewer pairs at L = 300 km.)
-__host__ __device__ inline double lat_window_deg(double g2) {
-    const double chord = sqrt(kCutBits / g2);
+__host__ __device__ inline double lat_window_deg(double g2, double bits = kCutBits) {
+    const double chord = sqrt(bits / g2);
     return chord >= 2.0 ? 1e9 : 2.0 * asin(0.5 * chord) * 57.29577951308232;
 }
 

@@ -97,6 +97,7 @@ SIGNATURES = {
     "oisat_gemm_nt": (C.c_int, [_c_ctx, _ptr, _i64, _ptr, _i64, _ptr, _i64, _i64, _i64, _i64, C.c_int, C.c_int]),
     "oisat_potrf": (C.c_int, [_c_ctx, _ptr, _i64, _i64, C.POINTER(C.c_int)]),
     "oisat_envelope": (C.c_int, [_ptr, _i64, C.c_double, _ptr]),
+    "oisat_factor_envelope": (C.c_int, [_ptr, _i64, C.c_double, _ptr]),
     "oisat_cov_build_env": (C.c_int, [_c_ctx, _ptr, _ptr, _ptr, _i64, C.c_double, _ptr, _i64, _ptr]),
     "oisat_potrf_env": (C.c_int, [_c_ctx, _ptr, _i64, _i64, _ptr, _ptr, C.POINTER(C.c_int)]),
     "oisat_potrs": (C.c_int, [_c_ctx, _ptr, _i64, _i64, _ptr]),

@@ -13,8 +13,8 @@ Pipeline (all in HBM, csrc/dense_cov.hip + csrc/dense_chol.hip):
 ``oisat_innovation`` -> ``oisat_cov_build`` (S, fp32) -> ``oisat_potrf`` (MFMA fp32 Cholesky) ->
 ``oisat_gain_solve`` (triangular solves + float64-residual refinement) -> ``oisat_apply_increment``
 (B H^T z generated on the fly, never stored).  ``DenseAnalysis.run()`` owns the latitude sort of its observations and
-therefore builds and factors only the covariance's latitude envelope (``oisat_envelope`` -> ``oisat_cov_build_env`` ->
-``oisat_potrf_env``).
+therefore builds and factors only the covariance's latitude envelope (``oisat_factor_envelope`` -> ``oisat_cov_build_env``
+-> ``oisat_potrf_env``; DESIGN.md section 4.2a: the fp32 factor, a preconditioner, has a cut-off of its own).
 """
 from __future__ import annotations
 
@@ -131,7 +131,7 @@ class DenseAnalysis:
         self.perm = c.alloc(self.max_obs * 4)
         if batched:
             self.perm.shared_with_other_streams()
-        # the block envelope of the latitude-sorted system (``oisat_envelope``): first | last, 2 x mp_max / 128 words
+        # the block envelope of the latitude-sorted system (``oisat_factor_envelope``): first | last, 2 x mp_max / 128 words
         self.env = c.alloc(2 * (self.mp_max // NB) * 4)
         self._env_host, self._env_g = None, None
         self.m = 0
@@ -181,12 +181,12 @@ class DenseAnalysis:
         return self._order
 
     def _envelope(self, g):
-        """Host table ``first`` of this plan's observations at decay constant ``g`` (the library's rule and cut-off:
-        ``oisat_envelope``); its device copy ``first | last`` is in ``self.env``.  Made once per (observations, L)."""
+        """Host table ``first`` of this plan's observations at decay constant ``g`` (the library's rule and the fp32 factor's
+        cut-off: ``oisat_factor_envelope``); its device copy ``first | last`` is in ``self.env``.  Made once per (observations, L)."""
         if self._env_host is None or self._env_g != g:
             nb = self.mp // NB
             env = np.empty(2 * nb, dtype=np.int32)
-            self.ctx.check(self.ctx.lib.oisat_envelope(self._lat_sorted.ctypes.data, self.m, g, env.ctypes.data))
+            self.ctx.check(self.ctx.lib.oisat_factor_envelope(self._lat_sorted.ctypes.data, self.m, g, env.ctypes.data))
             self.ctx.upload_into(self.env.ptr, env)
             self._env_host, self._env_g = env, g
         return self._env_host
