@@ -398,6 +398,42 @@ int oisat_cov_build_env(oisat_ctx* h, const double* oxyz, const double* osig, co
 int oisat_potrf_env(oisat_ctx* h, float* S, int64_t m, int64_t ld, const int32_t* first, const int32_t* env_dev,
                     int* info_host);
 
+/* ---- the build and the factorization of DenseAnalysis.run(): no stores, no sweep the result does not need -----------
+ * oisat_cov_build_env_zeroed: oisat_cov_build_env for a caller that KNOWS what the buffer holds.  first = the host
+ * table, env_dev = its device copy; zero_first / zero_first_dev (host / device int32[nb], both or neither) = the
+ * caller's statement that in block row i every lower tile left of block column zero_first[i] holds exact zeros
+ * (NULL: no such statement).  Tiles inside the envelope are evaluated; only the tiles in [zero_first[i], first[i]) are
+ * zero-filled; the launch covers those two sets (tile rows x the widest row), not the triangle.  The statement is
+ * true after a build and an enveloped task-graph factorization with the table zero_first (neither writes outside the
+ * envelope: schedule_out below) as long as nothing else has written to the buffer and ld is the same; a caller that
+ * cannot vouch for it passes NULL or calls oisat_cov_build_env, which fills every tile outside the envelope.
+ * enveloped_out (optional): 1 = built as described, 0 = OISAT_ENVELOPE=0 made this the dense oisat_cov_build -- the
+ * zeros left of the envelope are then correlations: the caller drops its statement.
+ * oisat_cov_build_cover (host only): what that launch touches.  from_out[i] = the first block column of block row i
+ * it writes (zero-fill up to first[i], evaluation from there), width_out = the most 64 x 64 tiles of one tile row,
+ * zero_tiles_out = 128 x 128 tiles that are zero-filled.  Any out pointer may be NULL.
+ *
+ * oisat_potrf_env_fwd: oisat_potrf_env which also runs the FIRST FORWARD SWEEP of the gain solve of d (device
+ * double[m], unchanged until that solve) inside the task-graph launch: row j of the sweep becomes a task when diagonal
+ * block j is out and streams its blocks beside the tile tasks, instead of a chain of nb exposed hand-overs behind the
+ * launch.  The handle records the forward vector with the factor; the next oisat_gain_solve on this factor with the
+ * same d takes it (once), skips its own preparation and forward sweep and starts with the backward sweep -- same
+ * arithmetic, same bits.  Any other factorization, oisat_factor_adopt, oisat_potrs or a gain solve of another d drops
+ * the record.  Where the factorization does not run as the task graph (OISAT_DAG=0, OISAT_POTRF, under three block rows)
+ * or OISAT_FWD_IN_LAUNCH=0 is set (read at every call), this is oisat_potrf_env and the gain solve does all its work.
+ * schedule_out (optional): which schedule factored -- OISAT_SCHEDULE_ENV_DAG / _ENV_DAG_FWD (the enveloped task graph,
+ * without / with the sweep: nothing outside the envelope was written) or OISAT_SCHEDULE_OTHER (anything else). */
+#define OISAT_SCHEDULE_OTHER 0
+#define OISAT_SCHEDULE_ENV_DAG 1
+#define OISAT_SCHEDULE_ENV_DAG_FWD 2
+int oisat_cov_build_env_zeroed(oisat_ctx* h, const double* oxyz, const double* osig, const double* ovar, int64_t m,
+                               double g, float* S, int64_t ld, const int32_t* first, const int32_t* env_dev,
+                               const int32_t* zero_first, const int32_t* zero_first_dev, int* enveloped_out);
+int oisat_cov_build_cover(const int32_t* first, const int32_t* zero_first, int64_t nb, int32_t* from_out,
+                          int64_t* width_out, int64_t* zero_tiles_out);
+int oisat_potrf_env_fwd(oisat_ctx* h, float* S, int64_t m, int64_t ld, const int32_t* first, const int32_t* env_dev,
+                        const double* d, int* info_host, int* schedule_out);
+
 /* z <- L^-T L^-1 z  (dev double[m], fp32 factor, double accumulation). */
 int oisat_potrs(oisat_ctx* h, const float* L, int64_t m, int64_t ld, double* z_inout);
 

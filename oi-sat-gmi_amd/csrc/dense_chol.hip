@@ -1359,7 +1359,10 @@ __device__ __forceinline__ bool trsv_row(const float* __restrict__ L, int64_t ld
                                          unsigned* __restrict__ err_total, int two_tiles, double* __restrict__ zout, int64_t m,
                                          int accumulate, float* __restrict__ tile, double* __restrict__ vec, double* __restrict__ part,
                                          unsigned* __restrict__ s_ok) {
-    const int tid = threadIdx.x;
+    int tid = threadIdx.x;
+    // (a task of the persistent launch: everything this row derives from its lane number is THIS call's value -- left to itself
+    // the compiler forms the staging addresses in front of the launch's task loop and keeps them live across the K-loops)
+    if (DAG) asm volatile("" : "+v"(tid));
     const int row = tid & (NB - 1), hf = tid >> 7;       // two threads per row: columns [64*hf, 64*hf+64)
     float* const tileT = tile + NB * TLD;
     const int b = TRANSPOSE ? nb - 1 - tk : tk;             // my block row (fwd) / block column (bwd)
@@ -2074,8 +2077,10 @@ __global__ __launch_bounds__(1024) void resid_check_batched_kernel(const SolveMe
 // "not yet published" pattern (solve_prep_kernel, or the previous solve's backward sweep, which leaves it behind); each
 // sweep re-arms the vector it has consumed for the sweep that follows, and the last workgroup of a sweep zeroes its
 // control block, so a solve is exactly two launches.  st: skip both when the refinement has converged.  zout (m entries):
-// where the solution is to be written (accumulate = 0) or added (1) besides rhs.
-int trsv_solve(oisat_ctx* h, const ChFactor& f, double* rhs_pad, double* fwd, const SolveState* st, double* zout, int accumulate) {
+// where the solution is to be written (accumulate = 0) or added (1) besides rhs.  fwd_done: the forward sweep of this right-
+// hand side ran inside the factorization launch (oisat_potrf_env_fwd) and left both vectors as trsv_fwd would: backward only.
+int trsv_solve(oisat_ctx* h, const ChFactor& f, double* rhs_pad, double* fwd, const SolveState* st, double* zout, int accumulate,
+               bool fwd_done = false) {
     const int nb = (int)(f.mp / NB);
     const size_t ctl_bytes = kCtlBytes;
     char* base = nullptr;
@@ -2083,14 +2088,18 @@ int trsv_solve(oisat_ctx* h, const ChFactor& f, double* rhs_pad, double* fwd, co
     unsigned* err_total = (unsigned*)base;
     char* ctl = base + 16;
     // a second LDS tile per workgroup (132 KB: one workgroup per CU) when every block row still gets its own CU at once;
-    // larger systems keep two workgroups per CU in flight (they are bound by streaming L, not by the hop latency)
+    // larger systems keep two workgroups per CU in flight.  (Dense, they are bound by streaming L.  An ENVELOPED sweep of the
+    // headline size streams 4 GB and is a chain of hand-overs again, 5.1 us each against 3.1 with the second tile; extending
+    // the rule to narrow bands is the open experiment of DESIGN.md section 9.)
     constexpr bool allow_two = true;
     constexpr int rows_per_wg = 1;                       // (four rows per workgroup: 0.54 vs 0.25 ms per sweep at 1e4 observations)
     const int grid = (int)cdiv(nb, rows_per_wg);
     const int two = allow_two && grid <= h->cu_count ? 1 : 0;
     const size_t shm = sizeof(float) * NB * TLD * (two ? 2 : 1);
-    OISAT_LAUNCH(h, "trsv_fwd", (trsv_pipe_kernel<0>), dim3(grid), dim3(256), shm, f.S, f.ld, (const float*)f.tinv, nb, rhs_pad, fwd,
-                 (TrsvCtl*)ctl, err_total, two, st, (double*)nullptr, (int64_t)0, 0, f.env);
+    if (!fwd_done) {
+        OISAT_LAUNCH(h, "trsv_fwd", (trsv_pipe_kernel<0>), dim3(grid), dim3(256), shm, f.S, f.ld, (const float*)f.tinv, nb, rhs_pad, fwd,
+                     (TrsvCtl*)ctl, err_total, two, st, (double*)nullptr, (int64_t)0, 0, f.env);
+    }
     OISAT_LAUNCH(h, "trsv_bwd", (trsv_pipe_kernel<1>), dim3(grid), dim3(256), shm, f.S, f.ld, (const float*)f.tinv, nb, fwd, rhs_pad,
                  (TrsvCtl*)(ctl + ctl_bytes), err_total, two, st, zout, f.m, accumulate, f.env);
     return OISAT_OK;
@@ -2201,9 +2210,21 @@ extern "C" int oisat_gemm_nt(oisat_ctx* h, float* C, int64_t ldc, const float* A
     return launch_gemm(h, "gemm_nt", C, ldc, A, lda, B, ldb, M, N, (int)K, mode, lower);
 }
 
+// OISAT_FWD_IN_LAUNCH=0: oisat_potrf_env_fwd factors as oisat_potrf_env and leaves the whole first solve to oisat_gain_solve
+// (A/B timing, tests); read at every call
+static bool fwd_in_launch_off() {
+    const char* e = getenv("OISAT_FWD_IN_LAUNCH");
+    return e != nullptr && atoi(e) == 0;
+}
+
 // first / env_dev: nullptr (dense), or the envelope of S (host: first[mpb]; device: first[mpb] | last[mpb], oisat_envelope)
-static int potrf_impl(oisat_ctx* h, float* S, int64_t m, int64_t ld, int* info_host, const int32_t* first, const int32_t* env_dev) {
+// fwd_d (device double[m]) or nullptr: the right-hand side whose first forward sweep rides in the task-graph launch
+// (oisat_potrf_env_fwd).  schedule_out (optional): OISAT_SCHEDULE_* of what ran.
+static int potrf_impl(oisat_ctx* h, float* S, int64_t m, int64_t ld, int* info_host, const int32_t* first, const int32_t* env_dev,
+                      const double* fwd_d = nullptr, int* schedule_out = nullptr) {
     ARG_CHECK(h && S && m > 0);
+    h->factor.fwd_d = nullptr;                                  // whatever comes of this call, the last factor's forward vector is history
+    if (schedule_out) *schedule_out = OISAT_SCHEDULE_OTHER;
     const int64_t mp = cdiv(m, NB) * NB;
     ARG_CHECK(ld >= mp && (ld % 4) == 0 && ((uintptr_t)S % 16) == 0);
     const int64_t mpb = mp / NB;
@@ -2235,9 +2256,10 @@ static int potrf_impl(oisat_ctx* h, float* S, int64_t m, int64_t ld, int* info_h
         // the plan of this (S, tinv, ld, block rows, enveloped or not) -- a handle keeps the last few (a lane that factors its
         // tiles one after the other in ONE shared buffer meets the same few sizes month after month).  An enveloped plan's
         // ticket list belongs to ONE envelope: the table itself is compared, and another envelope refills the plan's buffers.
+        const bool ride = fwd_d != nullptr && !fwd_in_launch_off();
         DagSingle* hit = nullptr;
         for (DagSingle& c : h->dag_cache)
-            if (c.plan && c.S == S && c.tinv == tinv && c.ld == ld && c.mpb == mpb && c.enveloped == (first != nullptr)) hit = &c;
+            if (c.plan && c.S == S && c.tinv == tinv && c.ld == ld && c.mpb == mpb && c.enveloped == (first != nullptr) && c.fwd == ride) hit = &c;
         if (hit && first) {
             DagPlan& pl = *(DagPlan*)hit->plan;
             if (memcmp(pl.first.data(), first, sizeof(int) * (size_t)mpb) != 0)
@@ -2255,17 +2277,49 @@ static int potrf_impl(oisat_ctx* h, float* S, int64_t m, int64_t ld, int* info_h
                 oisat_dag_plan_release(slot->plan);
                 slot->plan = nullptr;
             }
-            slot->plan = dag_plan_create(std::vector<BatchMat>{BatchMat{S, tinv, ld, m, (int)mpb, 0}}, h->stream, DagSolveShape(), first);
+            DagSolveShape shape;
+            if (ride) {                                         // the plan's shape: its ready queue holds the block rows of one forward sweep
+                shape.refine = 0;
+                shape.fwd_only = true;
+            }
+            slot->plan = dag_plan_create(std::vector<BatchMat>{BatchMat{S, tinv, ld, m, (int)mpb, 0}}, h->stream, shape, first);
             if (!slot->plan) return OISAT_ENOMEM;
-            slot->S = S; slot->tinv = tinv; slot->ld = ld; slot->mpb = mpb; slot->enveloped = first != nullptr;
+            slot->S = S; slot->tinv = tinv; slot->ld = ld; slot->mpb = mpb; slot->enveloped = first != nullptr; slot->fwd = ride;
             hit = slot;
         }
         hit->stamp = ++h->dag_clock;
-        rc = dag_launch(h, *(DagPlan*)hit->plan, info_dev, (unsigned*)(info_dev + kInfoDagTimeouts));
+        DagPlan& pl = *(DagPlan*)hit->plan;
+        if (ride) {
+            // what oisat_gain_solve does in front of its first solve: the padded right-hand side, the forward vector "not yet
+            // published", the solve state reset -- then the launch, whose chain pushes row j of the sweep behind diagonal block j
+            double* w = (double*)oisat_ws(h, 5, sizeof(double) * (2 + 8) * mp);
+            SolveState* st = solve_state(h);
+            char* base = nullptr;
+            if (!w || !st) return OISAT_ENOMEM;
+            if (int rs = status_ws(h, nullptr, &base)) return rs;
+            OISAT_LAUNCH(h, "copy_pad", solve_prep_kernel, dim3(stream_grid(mp, 256)), dim3(256), 0, fwd_d, m, mp, w, w + mp, st);
+            DagSolve sv{};
+            sv.queue = pl.queue_dev;
+            sv.qcap = (int)pl.qcap;
+            sv.qcap0 = (int)pl.qcap0;
+            sv.nsys = 1;
+            sv.trsv_timeouts = (unsigned*)base;
+            sv.fwd_rhs = w;
+            sv.fwd_sol = w + mp;
+            sv.env = first ? env_dev : nullptr;
+            rc = dag_launch(h, pl, info_dev, (unsigned*)(info_dev + kInfoDagTimeouts), &sv);
+            if (rc == OISAT_OK) h->factor.fwd_d = fwd_d;
+        } else {
+            rc = dag_launch(h, pl, info_dev, (unsigned*)(info_dev + kInfoDagTimeouts));
+        }
+        if (schedule_out) *schedule_out = !first ? OISAT_SCHEDULE_OTHER : ride ? OISAT_SCHEDULE_ENV_DAG_FWD : OISAT_SCHEDULE_ENV_DAG;
     } else {
         rc = lookahead ? potrf_lookahead(h, S, ld, mpb, tinv, info_dev, pw) : potrf_rec(h, S, ld, mpb, 0, mpb, tinv, info_dev);
     }
-    if (rc) return rc;
+    if (rc) {
+        h->factor.fwd_d = nullptr;
+        return rc;
+    }
     h->factor.S = S;
     h->factor.m = m;
     h->factor.mp = mp;
@@ -2383,9 +2437,18 @@ extern "C" int oisat_potrf_env(oisat_ctx* h, float* S, int64_t m, int64_t ld, co
     return potrf_impl(h, S, m, ld, info_host, first, env_dev);
 }
 
+extern "C" int oisat_potrf_env_fwd(oisat_ctx* h, float* S, int64_t m, int64_t ld, const int32_t* first, const int32_t* env_dev,
+                                   const double* d, int* info_host, int* schedule_out) {
+    ARG_CHECK(h && first && env_dev && d && m > 0);
+    ARG_CHECK(envelope_table_ok(first, cdiv(m, NB)));
+    if (oisat_envelope_off()) return potrf_impl(h, S, m, ld, info_host, nullptr, nullptr, d, schedule_out);
+    return potrf_impl(h, S, m, ld, info_host, first, env_dev, d, schedule_out);
+}
+
 extern "C" int oisat_potrs(oisat_ctx* h, const float* L, int64_t m, int64_t ld, double* z_inout) {
     ARG_CHECK(h && L && z_inout && m > 0);
     ARG_CHECK(h->factor.S == L && h->factor.m == m && h->factor.ld == ld);     // must follow oisat_potrf of this matrix
+    h->factor.fwd_d = nullptr;                                  // (the work vectors are about to be reused)
     double* w = (double*)oisat_ws(h, 5, sizeof(double) * (2 + 8) * h->factor.mp);
     if (!w) return OISAT_ENOMEM;
     double* rhs = w;
@@ -2413,6 +2476,9 @@ extern "C" int oisat_gain_solve(oisat_ctx* h, const float* L, const double* oxyz
                                 const double* olat_sorted) {
     ARG_CHECK(h != nullptr);
     const int* perm = oisat_take_obs_perm(h, m);               // one-shot, whatever this call's outcome
+    // the forward vector of this very d, left by oisat_potrf_env_fwd's launch: consumed once, whatever this call's outcome
+    const bool fwd_done = h->factor.fwd_d != nullptr && h->factor.fwd_d == d;
+    h->factor.fwd_d = nullptr;
     ARG_CHECK(L && oxyz && osig && ovar && d && z_out && m > 0 && refine >= 0 && refine <= 8);
     ARG_CHECK(h->factor.S == L && h->factor.m == m && h->factor.ld == ld);
     const double tol = h->refine_tol;
@@ -2422,8 +2488,10 @@ extern "C" int oisat_gain_solve(oisat_ctx* h, const float* L, const double* oxyz
     if (!w || !st) return OISAT_ENOMEM;
     double* rhs = w;
     double* fwd = w + mp;
-    OISAT_LAUNCH(h, "copy_pad", solve_prep_kernel, dim3(stream_grid(mp, 256)), dim3(256), 0, d, m, mp, rhs, fwd, st);
-    int rc = trsv_solve(h, h->factor, rhs, fwd, nullptr, z_out, 0);
+    if (!fwd_done) {
+        OISAT_LAUNCH(h, "copy_pad", solve_prep_kernel, dim3(stream_grid(mp, 256)), dim3(256), 0, d, m, mp, rhs, fwd, st);
+    }
+    int rc = trsv_solve(h, h->factor, rhs, fwd, nullptr, z_out, 0, fwd_done);
     if (rc) return rc;
     // the residual is evaluated once more behind the last allowed correction: a converged solve skips it (no-op launches), one
     // that is still above the tolerance there is recorded in the handle's status (oisat_solve_status_ex)
@@ -2811,7 +2879,7 @@ extern "C" int oisat_batch_analyse(oisat_ctx* h, int batch_id, int dtype, double
     HIP_TRY(dense_kernel_attributes());
     const int nmem = (int)bt.table.size();
     const double g2 = g * (double)kLog2e;
-    DagSolve sv;
+    DagSolve sv{};
     sv.mem = bt.solve_dev;
     sv.g = g;
     sv.g2 = g2;
@@ -2921,6 +2989,7 @@ extern "C" int oisat_factor_adopt(oisat_ctx* h, const float* L, int64_t m, int64
     h->factor.ld = ld;
     h->factor.tinv = tinv;
     h->factor.env = nullptr;                                // (adopted without an envelope: swept densely)
+    h->factor.fwd_d = nullptr;
     return OISAT_OK;
 }
 

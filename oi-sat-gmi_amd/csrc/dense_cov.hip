@@ -18,16 +18,35 @@ namespace {
 // ENV: first[mp/128] (device) is the block envelope of a latitude-sorted system (oisat_envelope).  A tile left of its row's
 // envelope holds correlations below the library's cut-off only: it is not evaluated but filled with exact zeros, so that every
 // reader of S or of its factor that does not know the envelope finds zeros there (never what an earlier system left).
-template <bool ENV>
+// BAND (oisat_cov_build_env_zeroed): the grid is tile rows x the widest row's tiles instead of the whole triangle.  Row ti
+// starts at the 128-column block from = min(first, zero_first) of its block row (zero_first = nullptr: 0): tiles in
+// [from, first) are zero-filled, tiles from first on evaluated, and the caller vouches for the zeros left of `from`.
+template <bool ENV, bool BAND>
 __global__ __launch_bounds__(256) void cov_build_kernel(const double* __restrict__ oxyz, const double* __restrict__ osig,
                                                          const double* __restrict__ ovar, int64_t m, int64_t mp, float g2,
-                                                         float* __restrict__ S, int64_t ld, int ntile, const int* __restrict__ first) {
-    // triangular tile index -> (ti >= tj)
-    const int64_t b = blockIdx.x;
-    int ti = (int)((sqrt(8.0 * (double)b + 1.0) - 1.0) * 0.5);
-    while ((int64_t)ti * (ti + 1) / 2 > b) --ti;
-    while ((int64_t)(ti + 1) * (ti + 2) / 2 <= b) ++ti;
-    const int tj = (int)(b - (int64_t)ti * (ti + 1) / 2);
+                                                         float* __restrict__ S, int64_t ld, int ntile, const int* __restrict__ first,
+                                                         const int* __restrict__ zero_first) {
+    int ti, tj;
+    if (BAND) {
+        ti = (int)blockIdx.y;
+        int from = first[ti >> 1];
+        if (zero_first != nullptr) {
+            const int zf = zero_first[ti >> 1];
+            from = zf < from ? (zf < 0 ? 0 : zf) : from;
+        } else {
+            from = 0;
+        }
+        from = from < 0 ? 0 : from;
+        tj = 2 * from + (int)blockIdx.x;
+        if (tj > ti) return;                     // (block-uniform; tj >= 0: no table content moves a store out of the lower triangle)
+    } else {
+        // triangular tile index -> (ti >= tj)
+        const int64_t b = blockIdx.x;
+        ti = (int)((sqrt(8.0 * (double)b + 1.0) - 1.0) * 0.5);
+        while ((int64_t)ti * (ti + 1) / 2 > b) --ti;
+        while ((int64_t)(ti + 1) * (ti + 2) / 2 <= b) ++ti;
+        tj = (int)(b - (int64_t)ti * (ti + 1) / 2);
+    }
     __shared__ float4 pa[64], pb[64];            // x, y, z, sig
     const int t = threadIdx.x;
     if (ENV && (tj >> 1) < first[ti >> 1]) {     // (block-uniform)
@@ -191,8 +210,8 @@ extern "C" int oisat_cov_build(oisat_ctx* h, const double* oxyz, const double* o
     const int ntile = (int)(mp / 64);
     const int64_t nblk = (int64_t)ntile * (ntile + 1) / 2;
     ARG_CHECK(nblk < (int64_t)INT32_MAX);
-    OISAT_LAUNCH(h, "cov_build", cov_build_kernel<false>, dim3((unsigned)nblk), dim3(256), 0, oxyz, osig, ovar, m, mp,
-                 (float)(g * (double)kLog2e), S, ld, ntile, (const int*)nullptr);
+    OISAT_LAUNCH(h, "cov_build", (cov_build_kernel<false, false>), dim3((unsigned)nblk), dim3(256), 0, oxyz, osig, ovar, m, mp,
+                 (float)(g * (double)kLog2e), S, ld, ntile, (const int*)nullptr, (const int*)nullptr);
     return OISAT_OK;
 }
 
@@ -206,8 +225,52 @@ extern "C" int oisat_cov_build_env(oisat_ctx* h, const double* oxyz, const doubl
     const int ntile = (int)(mp / 64);
     const int64_t nblk = (int64_t)ntile * (ntile + 1) / 2;
     ARG_CHECK(nblk < (int64_t)INT32_MAX);
-    OISAT_LAUNCH(h, "cov_build", cov_build_kernel<true>, dim3((unsigned)nblk), dim3(256), 0, oxyz, osig, ovar, m, mp,
-                 (float)(g * (double)kLog2e), S, ld, ntile, (const int*)env_dev);
+    OISAT_LAUNCH(h, "cov_build", (cov_build_kernel<true, false>), dim3((unsigned)nblk), dim3(256), 0, oxyz, osig, ovar, m, mp,
+                 (float)(g * (double)kLog2e), S, ld, ntile, (const int*)env_dev, (const int*)nullptr);
+    return OISAT_OK;
+}
+
+// Which tiles the banded build touches (host only: the launch below sizes its grid with it, tests restate it).  Block row i
+// is zero-filled in [from[i], first[i]) and evaluated in [first[i], i], from[i] = min(first[i], max(zero_first[i], 0)) or 0
+// without a claim; width = the most 64 x 64 tiles any tile row touches (row 2 i + 1: 2 (i - from[i]) + 2).
+extern "C" int oisat_cov_build_cover(const int32_t* first, const int32_t* zero_first, int64_t nb, int32_t* from_out,
+                                     int64_t* width_out, int64_t* zero_tiles_out) {
+    ARG_CHECK(first && nb > 0);
+    int64_t width = 0, zeros = 0;
+    for (int64_t i = 0; i < nb; ++i) {
+        ARG_CHECK(first[i] >= 0 && first[i] <= i);
+        const int32_t zf = zero_first ? (zero_first[i] < 0 ? 0 : zero_first[i]) : 0;
+        const int32_t from = zf < first[i] ? zf : first[i];
+        if (from_out) from_out[i] = from;
+        width = std::max<int64_t>(width, 2 * (i - from) + 2);
+        zeros += first[i] - from;
+    }
+    if (width_out) *width_out = width;
+    if (zero_tiles_out) *zero_tiles_out = zeros;               // (128 x 128 tiles)
+    return OISAT_OK;
+}
+
+extern "C" int oisat_cov_build_env_zeroed(oisat_ctx* h, const double* oxyz, const double* osig, const double* ovar, int64_t m, double g,
+                                          float* S, int64_t ld, const int32_t* first, const int32_t* env_dev,
+                                          const int32_t* zero_first, const int32_t* zero_first_dev, int* enveloped_out) {
+    ARG_CHECK(first != nullptr && env_dev != nullptr && (zero_first == nullptr) == (zero_first_dev == nullptr));
+    if (enveloped_out) *enveloped_out = 0;
+    if (oisat_envelope_off()) return oisat_cov_build(h, oxyz, osig, ovar, m, g, S, ld);       // dense: the caller drops its claim
+    ARG_CHECK(h && oxyz && osig && ovar && S && m > 0 && g >= 0.0);
+    const int64_t mp = cdiv(m, 128) * 128;
+    ARG_CHECK(ld >= mp && (ld % 4) == 0 && ((uintptr_t)S % 16) == 0);
+    const int ntile = (int)(mp / 64);
+    int64_t width = 0;
+    if (int rc = oisat_cov_build_cover(first, zero_first, mp / 128, nullptr, &width, nullptr)) return rc;
+    ARG_CHECK(width <= ntile);
+    if (ntile > 65535) {                                        // (beyond a grid's second dimension: the triangular launch, which fills every tile)
+        if (int rc = oisat_cov_build_env(h, oxyz, osig, ovar, m, g, S, ld, env_dev)) return rc;
+        if (enveloped_out) *enveloped_out = 1;
+        return OISAT_OK;
+    }
+    OISAT_LAUNCH(h, "cov_build", (cov_build_kernel<true, true>), dim3((unsigned)width, (unsigned)ntile), dim3(256), 0, oxyz, osig, ovar, m,
+                 mp, (float)(g * (double)kLog2e), S, ld, ntile, (const int*)env_dev, (const int*)zero_first_dev);
+    if (enveloped_out) *enveloped_out = 1;
     return OISAT_OK;
 }
 

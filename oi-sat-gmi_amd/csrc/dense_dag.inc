@@ -433,6 +433,11 @@ struct DagSolve {
     int refine, dtype, cells, blocks;       // blocks: residual on compact blocks of rows (every member has its permutation)
     int nsys, qcap, qcap0;                  // entries [0, qcap0) belong to queue 0 (sweep rows), [qcap0, qcap) to queue 1
     unsigned* trsv_timeouts;                // status slot 7
+    // the launch that factors ONE system and runs its first forward sweep (DAG_SOLVE_FWD, oisat_potrf_env_fwd): the padded
+    // right-hand side, the forward vector ("not yet published") and the factor's envelope first[nb] | last[nb] (or nullptr)
+    double* fwd_rhs;
+    double* fwd_sol;
+    const int* env;
 };
 
 __device__ __forceinline__ int dag_ld(const int* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
@@ -619,6 +624,40 @@ __device__ __forceinline__ bool dag_sweep_task(const DagSys& sy, const SolveMemb
     return true;
 }
 
+// Row `row` of the FIRST forward sweep in the launch that factors one system and does nothing else of its solve
+// (DAG_SOLVE_FWD).  Why this one sweep and nothing more: it needs only d, known before the launch, and row `row` of L, final
+// when diagonal block `row` is out -- the chain pushes it then -- and it is HBM streaming, not VALU work: a row costs ~0.1 ms of
+// one workgroup slot where the sweep as a launch of its own is a fully exposed chain of nb hand-overs (4 ms of the headline step).
+// The float64 residual and the increment stay outside (they do not overlap with the K-loop: "WHAT IT BOUGHT" above), and the
+// other sweeps wait for them.  An enveloped row starts at first[row] like trsv_pipe_kernel's (clamped the same way): the
+// blocks left of it are the build's zeros.  The arithmetic is trsv_row's: the bits of the stand-alone sweep.  The last row to
+// finish counts the system as done; nothing is pushed behind it.
+__device__ __forceinline__ bool dag_fwd_row_task(const DagSys& sy, int row, const DagSolve& sv, DagCtl* ctl, float* lds) {
+    dag_task_acquire();
+    __builtin_amdgcn_s_setprio(2);
+    float* tile = lds;
+    double* vec = reinterpret_cast<double*>(lds + NB * TLD);
+    double* part = vec + NB;
+    unsigned* s_ok = reinterpret_cast<unsigned*>(part + NB);
+    if (threadIdx.x == 0) *s_ok = 1u;
+    __syncthreads();
+    int step0 = 0;
+    if (sv.env != nullptr) {
+        step0 = sv.env[row];
+        step0 = step0 < 0 ? 0 : (step0 > row ? row : step0);
+    }
+    const bool ok = trsv_row<0, true>(sy.S, sy.ld, sy.tinv, sy.nb, row, step0, sv.fwd_rhs, sv.fwd_sol, reinterpret_cast<TrsvCtl*>(ctl),
+                                      sv.trsv_timeouts, 0, (double*)nullptr, (int64_t)0, 0, tile, vec, part, s_ok);
+    __builtin_amdgcn_s_setprio(0);
+    if (!ok) return false;
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");            // this row's stores (solution, re-armed right-hand side) are out ...
+    __syncthreads();
+    if (threadIdx.x == 0 &&                                     // ... before it counts as through
+        __hip_atomic_fetch_add(sy.state + DAG_ST_FWD, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == sy.nb - 1)
+        __hip_atomic_fetch_add(&ctl->sys_done, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    return true;
+}
+
 // block c (64 rows) of residual evaluation e: r = d - S z into the padded right-hand side; the LAST block of an evaluation
 // to finish forms |r|^2 (and |d|^2) in the order of resid_check_batched_kernel, publishes the verdict and pushes what follows
 __device__ __forceinline__ bool dag_res_task(const DagSys& sy, const SolveMember& mb, int sys, int c, int e, const DagSolve& sv, DagCtl* ctl, int* info,
@@ -724,13 +763,34 @@ __device__ __forceinline__ bool dag_inc_task(const DagSys& sy, const SolveMember
     return true;
 }
 
-// SOLVE: the ticket list also holds the systems' solve tasks (oisat_batch_analyse); the workgroup's LDS then also serves a
-// sweep row's 128 x 129 block image + vectors (68 KB instead of 64: still two workgroups per CU)
+__device__ __forceinline__ void dag_lane_coords(DagLane& L, int t) {      // (the kernel's own first lines, for DAG_SOLVE_FWD's task loop)
+    L.lane = t & 63;
+    L.wid = __builtin_amdgcn_readfirstlane(t >> 6);
+    L.wr = L.wid >> 1;
+    L.wc = L.wid & 1;
+    L.rl = L.lane >> 3;
+    L.lc = (L.lane & 7) ^ L.rl;
+    L.frow = L.lane & 31;
+    L.fh = L.lane >> 5;
+    L.sw = L.frow & 7;
+    L.arow = (L.wr * 64 + L.frow) * BK;
+    L.brow = (L.wc * 64 + L.frow) * BK;
+}
+
+// SOLVE = DAG_SOLVE_ALL: the launch also runs the systems' solve tasks (oisat_batch_analyse); the workgroup's LDS then also
+// serves a sweep row's 128 x 129 block image + vectors (68 KB instead of 64: still two workgroups per CU).
+// SOLVE = DAG_SOLVE_FWD: ONE system, and of its solve only the rows of the first forward sweep (dag_fwd_row_task) -- an
+// instantiation of its own because the residual and increment bodies cost the K-loop its registers (DAG_SOLVE_ALL: 256 VGPRs
+// and spills, this one none).  Its workgroups leave when the tickets are gone, except the first kDagFwdStayers, which serve
+// the rows the chain still pushes: a few hundred idle workgroups polling the queue's counters would be memory-side traffic in
+// the way of the chain's own polls, and one row per ~100 us of chain step needs a handful of workgroups.
+constexpr int DAG_SOLVE_NONE = 0, DAG_SOLVE_ALL = 1, DAG_SOLVE_FWD = 2;
+constexpr unsigned kDagFwdStayers = 16;
 constexpr int kDagLdsFloats = 2 * 2 * NB * BK;                                  // the GEMM image, 65,536 B
 constexpr int kDagSolveLdsFloats = NB * TLD + 4 * NB + 16;                      // block image | vec, part (doubles) | flag
 static_assert(kDagSolveLdsFloats >= kDagLdsFloats && (size_t)kDagSolveLdsFloats * 4 >= 32768 + 2 * 1024 * sizeof(double) &&
               kSolveLdsBytes <= 32768, "solve tasks' LDS fits");
-template <bool SOLVE>
+template <int SOLVE>
 __global__ __launch_bounds__(256, 2) void potrf_dag_kernel(const DagSys* __restrict__ systems, const int4* __restrict__ tasks, int ntasks,
                                                            DagCtl* __restrict__ ctl, int* __restrict__ info, unsigned* __restrict__ err_total,
                                                            int* __restrict__ state_all, int state_words, int reserve_chains, int flags,
@@ -761,7 +821,7 @@ __global__ __launch_bounds__(256, 2) void potrf_dag_kernel(const DagSys* __restr
     // gone, so that chains land on first arrivals -- and leaves at once if its CU belongs to a chain.  A chain alone on its
     // CU runs its diagonal blocks and 128^3 products at the rate of the stand-alone kernels (measured: 47 vs 60 us per block).
     int cu_key = -1, first_on_cu = 1;
-    if (reserve_chains > 0 || SOLVE) {                          // (a solving launch wants to know first from second too: above dag_queue_of)
+    if (reserve_chains > 0 || SOLVE == DAG_SOLVE_ALL) {         // (a solving launch wants to know first from second too: above dag_queue_of)
         if (t == 0) {
             unsigned xcc, hw;
             asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
@@ -803,8 +863,9 @@ __global__ __launch_bounds__(256, 2) void potrf_dag_kernel(const DagSys* __restr
             s_flag = 0;
             // a ready sweep row first (short, and a chain of others waits for it); a residual block / increment patch if this
             // workgroup is its CU's second one, or once the tickets are gone; else a ticket
-            if (SOLVE && (dag_queue_pop(sv, ctl, 0, &s_task, &slot, trace ? wg_pop : (long long*)nullptr) ||
-                          ((second_on_cu || tickets_gone) && dag_queue_pop(sv, ctl, 1, &s_task, &slot, trace ? wg_pop : (long long*)nullptr)))) {
+            // (DAG_SOLVE_FWD does not time its claims: the array behind that pointer would be its only scratch)
+            if (SOLVE && (dag_queue_pop(sv, ctl, 0, &s_task, &slot, trace && SOLVE == DAG_SOLVE_ALL ? wg_pop : (long long*)nullptr) ||
+                          (SOLVE == DAG_SOLVE_ALL && (second_on_cu || tickets_gone) && dag_queue_pop(sv, ctl, 1, &s_task, &slot, trace ? wg_pop : (long long*)nullptr)))) {
                 s_flag = 1;
                 s_ticket = ntasks + slot;                                // (its row of the trace)
             } else if (!tickets_gone) {
@@ -825,6 +886,7 @@ __global__ __launch_bounds__(256, 2) void potrf_dag_kernel(const DagSys* __restr
         if (!ready_task && tk >= ntasks) {
             if (!SOLVE) break;
             // the tickets are gone; ready tasks may still come (the last systems' solves): until every system is done
+            if (SOLVE == DAG_SOLVE_FWD && blockIdx.x >= kDagFwdStayers) break;      // (the stayers, or a smaller grid's every workgroup, serve the rows)
             tickets_gone = true;
             __syncthreads();
             if (t == 0) {
@@ -838,7 +900,7 @@ __global__ __launch_bounds__(256, 2) void potrf_dag_kernel(const DagSys* __restr
             }
             __syncthreads();
             if (s_flag != 0) break;
-            __builtin_amdgcn_s_sleep(8);
+            __builtin_amdgcn_s_sleep(SOLVE == DAG_SOLVE_FWD ? 64 : 8);
             continue;
         }
         idle = 0;
@@ -857,7 +919,17 @@ __global__ __launch_bounds__(256, 2) void potrf_dag_kernel(const DagSys* __restr
             tr[3] = ready_task ? ((long long)task.x | ((long long)task.w << 4) | ((long long)task.y << 8) | ((long long)task.z << 24)) : 0;
         }
         bool ok;
-        if (ready_task) {
+        if constexpr (SOLVE == DAG_SOLVE_FWD) {
+            // the lane's GEMM coordinates are formed per task, from a lane number the compiler cannot see through: kept across
+            // the loop they are a dozen registers live through a sweep row, which then spills
+            int tt = t;
+            asm volatile("" : "+v"(tt));
+            dag_lane_coords(L, tt);
+            if (ready_task) ok = dag_fwd_row_task(sy, task.z, sv, ctl, lds);
+            else if ((task.x & 255) == DAG_CHAIN)
+                ok = dag_chain_task(sy, ctl, info, lds, L, &s_flag, trace ? trace + 4 * (int64_t)(ntasks + sv.qcap) + 8 * (int64_t)task.z : nullptr, &sv);
+            else ok = dag_tile_task(sy, task.x & 255, task.x >> 8, task.z, task.w, ctl, lds, L, &s_flag, &s_kav, tr);
+        } else if (ready_task) {
             const SolveMember mb = sv.mem[task.y];
             if (task.x == DAG_FWD) ok = dag_sweep_task<0>(sy, mb, task.y, task.z, task.w, sv, ctl, lds, &s_kav, L.spin);
             else if (task.x == DAG_BWD) ok = dag_sweep_task<1>(sy, mb, task.y, task.z, task.w, sv, ctl, lds, &s_kav, L.spin);
@@ -891,7 +963,7 @@ __global__ __launch_bounds__(256, 2) void potrf_dag_kernel(const DagSys* __restr
     __syncthreads();
     if (s_flag) {
         for (int w = t; w < state_words; w += 256) __hip_atomic_store(&state_all[w], 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (reserve_chains > 0 || SOLVE)
+        if (reserve_chains > 0 || SOLVE == DAG_SOLVE_ALL)
             for (int w = t; w < DAG_CU_KEYS; w += 256) {
                 __hip_atomic_store(&ctl->cu_arrivals[w], 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 __hip_atomic_store(&ctl->cu_role[w], 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -927,6 +999,7 @@ struct DagPlan {
     int reserve_chains = 0;                                     // leading chain tickets that get a CU to themselves
     int max_wave_chains = 0;                                    // most chain tickets of ONE wave: each holds a workgroup until its system is through
     int solve_refine = -1;                                      // >= 0: the launch also solves (ready queue), at most that many refinement rounds
+    bool fwd_only = false;                                      // ... only the first forward sweep of its one system (DAG_SOLVE_FWD)
     int64_t qcap = 0, qcap0 = 0;                                // entries of its ready queues (all | the sweep rows' share)
     unsigned long long* queue_dev = nullptr;
     std::vector<DagSys> sys_host;
@@ -1068,10 +1141,15 @@ void dag_task_order(const std::vector<int>& nb_of, int wave_arg, DagOrder& out, 
 struct DagSolveShape {                                          // refine < 0: a factorization-only launch
     int refine = -1;
     std::vector<int> nres, ninc;                                // per system: residual blocks (m / 64), increment patches
+    bool fwd_only = false;                                      // DAG_SOLVE_FWD: the rows of the first forward sweep and nothing else (refine = 0)
 };
 static inline void dag_queue_entries(const std::vector<int>& nb_of, const DagSolveShape& sh, int64_t* sweep_rows, int64_t* valu_tasks) {
     *sweep_rows = *valu_tasks = 0;
     for (size_t s = 0; s < nb_of.size(); ++s) {
+        if (sh.fwd_only) {
+            *sweep_rows += nb_of[s];
+            continue;
+        }
         *sweep_rows += (int64_t)(sh.refine + 1) * 2 * nb_of[s];
         *valu_tasks += (int64_t)(sh.refine + 1) * ((sh.refine > 0 ? sh.nres[s] : 0) + sh.ninc[s]);
     }
@@ -1115,6 +1193,7 @@ DagPlan* dag_plan_create(const std::vector<BatchMat>& table, hipStream_t stream,
         }
     }
     p->solve_refine = shape.refine;
+    p->fwd_only = shape.fwd_only;
     std::vector<int4>& tasks = order.tasks;
     p->max_wave_chains = order.max_wave_chains;
     p->chain_rows = order.chain_rows;
@@ -1192,16 +1271,26 @@ int dag_launch(oisat_ctx* h, DagPlan& p, int* info_dev, unsigned* dag_timeouts, 
 #ifdef OISAT_TEST_HOOKS
     if (getenv("OISAT_DAG_FLAGS")) flags = atoi(getenv("OISAT_DAG_FLAGS"));
 #endif
+    if (p.fwd_only && (p.nsys != 1 || !solve || !solve->fwd_rhs || !solve->fwd_sol || solve->nsys != 1)) {
+        oisat_set_error("task-graph launch: the forward-sweep plan takes one system and its two work vectors");
+        return OISAT_EINVAL;
+    }
     if (solve) {
         if (solve->queue != p.queue_dev || solve->qcap != (int)p.qcap || solve->qcap0 != (int)p.qcap0) {
             oisat_set_error("task-graph launch: the solve arguments carry another plan's ready queue");
             return OISAT_EINVAL;
         }
-        OISAT_LAUNCH(h, "analyse_dag", potrf_dag_kernel<true>, dim3((unsigned)grid), dim3(256), 0, (const DagSys*)p.sys_dev,
-                     (const int4*)p.tasks_dev, p.ntasks, p.ctl_dev, info_dev, dag_timeouts, p.state_dev, p.state_words, p.reserve_chains, flags,
-                     trace_file ? p.trace_dev : (long long*)nullptr, p.chain_rows, *solve);
+        if (p.fwd_only) {
+            OISAT_LAUNCH(h, "potrf_dag", potrf_dag_kernel<DAG_SOLVE_FWD>, dim3((unsigned)grid), dim3(256), 0, (const DagSys*)p.sys_dev,
+                         (const int4*)p.tasks_dev, p.ntasks, p.ctl_dev, info_dev, dag_timeouts, p.state_dev, p.state_words, p.reserve_chains, flags,
+                         trace_file ? p.trace_dev : (long long*)nullptr, p.chain_rows, *solve);
+        } else {
+            OISAT_LAUNCH(h, "analyse_dag", potrf_dag_kernel<DAG_SOLVE_ALL>, dim3((unsigned)grid), dim3(256), 0, (const DagSys*)p.sys_dev,
+                         (const int4*)p.tasks_dev, p.ntasks, p.ctl_dev, info_dev, dag_timeouts, p.state_dev, p.state_words, p.reserve_chains, flags,
+                         trace_file ? p.trace_dev : (long long*)nullptr, p.chain_rows, *solve);
+        }
     } else {
-        OISAT_LAUNCH(h, "potrf_dag", potrf_dag_kernel<false>, dim3((unsigned)grid), dim3(256), 0, (const DagSys*)p.sys_dev,
+        OISAT_LAUNCH(h, "potrf_dag", potrf_dag_kernel<DAG_SOLVE_NONE>, dim3((unsigned)grid), dim3(256), 0, (const DagSys*)p.sys_dev,
                      (const int4*)p.tasks_dev, p.ntasks, p.ctl_dev, info_dev, dag_timeouts, p.state_dev, p.state_words, p.reserve_chains, flags,
                      trace_file ? p.trace_dev : (long long*)nullptr, p.chain_rows, DagSolve{});
     }

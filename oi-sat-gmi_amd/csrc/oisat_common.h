@@ -33,6 +33,9 @@ struct ChFactor {                // what the triangular solves need besides L: t
     int64_t m = 0, mp = 0, ld = 0;
     float* tinv = nullptr;       // [mp/128][128][128]: inverted diagonal blocks, row-major
     const int* env = nullptr;    // device, first[mp/128] | last[mp/128]: the factor's block envelope (oisat_potrf_env), or nullptr = dense
+    // oisat_potrf_env_fwd: the right-hand side whose forward vector the factorization launch left in workspace 5 (with the
+    // right-hand side re-armed and the solve state reset), or nullptr.  oisat_gain_solve of the same d takes it, once.
+    const double* fwd_d = nullptr;
 };
 
 struct BatchMat {                // one matrix of a batched factorization (device table entry)
@@ -101,6 +104,7 @@ struct DagSingle {               // a cached single-system task-graph plan (oisa
     const float* tinv = nullptr;
     int64_t ld = 0, mpb = 0;
     bool enveloped = false;      // its ticket list follows an envelope (the plan keeps the table it was made for)
+    bool fwd = false;            // its launch also runs the first forward sweep (a ready queue of mpb rows)
     uint64_t stamp = 0;
 };
 

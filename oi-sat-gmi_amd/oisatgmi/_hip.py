@@ -100,6 +100,10 @@ SIGNATURES = {
     "oisat_factor_envelope": (C.c_int, [_ptr, _i64, C.c_double, _ptr]),
     "oisat_cov_build_env": (C.c_int, [_c_ctx, _ptr, _ptr, _ptr, _i64, C.c_double, _ptr, _i64, _ptr]),
     "oisat_potrf_env": (C.c_int, [_c_ctx, _ptr, _i64, _i64, _ptr, _ptr, C.POINTER(C.c_int)]),
+    "oisat_cov_build_env_zeroed": (C.c_int, [_c_ctx, _ptr, _ptr, _ptr, _i64, C.c_double, _ptr, _i64, _ptr, _ptr, _ptr, _ptr,
+                                             C.POINTER(C.c_int)]),
+    "oisat_cov_build_cover": (C.c_int, [_ptr, _ptr, _i64, _ptr, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "oisat_potrf_env_fwd": (C.c_int, [_c_ctx, _ptr, _i64, _i64, _ptr, _ptr, _ptr, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "oisat_potrs": (C.c_int, [_c_ctx, _ptr, _i64, _i64, _ptr]),
     "oisat_cov_residual": (C.c_int, [_c_ctx, _ptr, _ptr, _ptr, _i64, C.c_double, _ptr, _ptr, _ptr, _ptr]),
     "oisat_gain_solve": (C.c_int, [_c_ctx, _ptr, _ptr, _ptr, _ptr, _i64, _i64, C.c_double, _ptr, C.c_int, _ptr,

@@ -13,8 +13,9 @@ Pipeline (all in HBM, csrc/dense_cov.hip + csrc/dense_chol.hip):
 ``oisat_innovation`` -> ``oisat_cov_build`` (S, fp32) -> ``oisat_potrf`` (MFMA fp32 Cholesky) ->
 ``oisat_gain_solve`` (triangular solves + float64-residual refinement) -> ``oisat_apply_increment``
 (B H^T z generated on the fly, never stored).  ``DenseAnalysis.run()`` owns the latitude sort of its observations and
-therefore builds and factors only the covariance's latitude envelope (``oisat_factor_envelope`` -> ``oisat_cov_build_env``
--> ``oisat_potrf_env``; DESIGN.md section 4.2a: the fp32 factor, a preconditioner, has a cut-off of its own).
+therefore builds and factors only the covariance's latitude envelope (``oisat_factor_envelope`` ->
+``oisat_cov_build_env_zeroed`` -> ``oisat_potrf_env_fwd``; DESIGN.md section 4.2a: the fp32 factor, a preconditioner, has a
+cut-off of its own; the build does not re-zero what is zero, the factorization launch carries the first forward sweep).
 """
 from __future__ import annotations
 
@@ -28,6 +29,7 @@ from . import _hip
 
 EARTH_RADIUS_KM = 6371.0
 NB = 128                      # Cholesky block edge (csrc/dense_chol.hip)
+SCHEDULE_ENV_DAG, SCHEDULE_ENV_DAG_FWD = 1, 2      # oisat_potrf_env_fwd's schedule_out: the enveloped task graph factored (include/oisat.h)
 # relative float64 residual |d - S z| / |d| at which the gain solve stops refining (oisat_gain_solve): the increment is K r
 # away from the exact one and |K| <= 1, so the fields are then within 1e-6 |d| -- a tenth of the 1e-5 bar
 REFINE_TOL = float(os.environ.get("OISAT_REFINE_TOL", "1e-6"))
@@ -134,6 +136,13 @@ class DenseAnalysis:
         # the block envelope of the latitude-sorted system (``oisat_factor_envelope``): first | last, 2 x mp_max / 128 words
         self.env = c.alloc(2 * (self.mp_max // NB) * 4)
         self._env_host, self._env_g = None, None
+        # What this plan knows about its S between runs (``oisat_cov_build_env_zeroed``): after a build and an enveloped
+        # task-graph factorization with table T nothing outside T has been written, so every lower tile left of T is still the
+        # exact zero of the fill.  Kept only by a plan that owns its S (a shared or batched buffer is written by others), as
+        # (leading dimension, host table, device copy); dropped by anything that writes S any other way.
+        self._owns_S = shared_S is None and not batched
+        self._zero_claim = None
+        self._zero_dev = c.alloc((self.mp_max // NB) * 4) if self._owns_S else None
         self.m = 0
         self._direct_innovation = False
         # every internal workspace of the solve is sized here, so that run() never allocates (include/oisat.h)
@@ -227,21 +236,39 @@ class DenseAnalysis:
         # this plan owns the latitude sort, so it may use the covariance's envelope: only the tiles inside it are evaluated
         # and factored, the sweeps of the gain solve walk inside it (OISAT_ENVELOPE=0: the dense path, in the library)
         first = self._envelope(g)
-        c.check(lib.oisat_cov_build_env(h, self.oxyz.ptr, self.osig.ptr, self.ovar.ptr, m, g, self.S.ptr, ld, self.env.ptr))
+        # the build fills with zeros only what the last run's envelope left outside this one's (equal tables: nothing), the
+        # factorization launch carries the first forward sweep of the gain solve (OISAT_FWD_IN_LAUNCH=0: it does not)
+        claim, self._zero_claim = self._zero_claim, None       # (an exception below leaves no claim behind)
+        if claim is not None and claim[0] != ld:
+            claim = None
+        enveloped, schedule = C.c_int(0), C.c_int(0)
+        c.check(lib.oisat_cov_build_env_zeroed(h, self.oxyz.ptr, self.osig.ptr, self.ovar.ptr, m, g, self.S.ptr, ld, first.ctypes.data,
+                                               self.env.ptr, claim[1].ctypes.data if claim else None,
+                                               self._zero_dev.ptr if claim else None, C.byref(enveloped)))
         info = C.c_int(0)
-        c.check(lib.oisat_potrf_env(h, self.S.ptr, m, ld, first.ctypes.data, self.env.ptr, C.byref(info) if check_pd else None))
+        c.check(lib.oisat_potrf_env_fwd(h, self.S.ptr, m, ld, first.ctypes.data, self.env.ptr, self.d.ptr,
+                                        C.byref(info) if check_pd else None, C.byref(schedule)))
+        self.last_schedule = schedule.value                    # (SCHEDULE_*: which factorization ran, for tests and profiles)
         resid = (C.c_double * (refine + 1))() if want_resid else None
         c.check(lib.oisat_set_obs_blocks(h, self.perm.ptr, m))                                  # per run: handles are shared
         c.check(lib.oisat_gain_solve(h, self.S.ptr, self.oxyz.ptr, self.osig.ptr, self.ovar.ptr, m, ld, g, self.d.ptr,
                                      int(refine), self.z.ptr, resid, self.olat.ptr))
         c.check(lib.oisat_apply_increment_grid(h, self.code, self.gxyz.ptr, self.gsig.ptr, self._ny, self._nx, self.oxyz.ptr,
                                                self.osig.ptr, self.z.ptr, m, g, xb, xa, inc, self.glat.ptr, self.olat.ptr))
+        if self._owns_S and enveloped.value == 1 and schedule.value in (SCHEDULE_ENV_DAG, SCHEDULE_ENV_DAG_FWD):
+            nb = self.mp // NB
+            if claim is None or not np.array_equal(claim[1], first[:nb]):
+                table = np.ascontiguousarray(first[:nb])
+                c.upload_into(self._zero_dev.ptr, table)
+                claim = (ld, table)
+            self._zero_claim = claim
         return list(resid) if want_resid else None
 
     # ---- the same pipeline in two halves, for lock-step (batched) factorization of many plans: build | factor | solve
     def run_build(self, L_km: float):
         c, lib, h = self.ctx, self.ctx.lib, self.ctx.h
         g = self._g = decay_constant(L_km)
+        self._zero_claim = None                                 # (a dense build: S holds correlations everywhere)
         if not self._direct_innovation:
             c.check(lib.oisat_innovation(h, self.code, self.xb_ptr, self.ocell.ptr, self.oy.ptr, self.m, self.d.ptr))
         c.check(lib.oisat_cov_build(h, self.oxyz.ptr, self.osig.ptr, self.ovar.ptr, self.m, g, self.S.ptr, self.mp))
