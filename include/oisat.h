@@ -434,6 +434,16 @@ int oisat_cov_build_cover(const int32_t* first, const int32_t* zero_first, int64
 int oisat_potrf_env_fwd(oisat_ctx* h, float* S, int64_t m, int64_t ld, const int32_t* first, const int32_t* env_dev,
                         const double* d, int* info_host, int* schedule_out);
 
+/* oisat_trsv_plan (host only): the launch shape of the triangular sweeps of a factor of nb block rows on cu_count CUs.
+ * band = the widest block row of an enveloped factor, max over b of (b - first[b]) + 1, or 0 for a dense one.
+ * two_tiles_out = 1: every workgroup keeps the row's inverted diagonal block in a second LDS tile (132 KB, one workgroup
+ * per CU), staged before the row starts waiting -- chosen when nb <= cu_count or 0 < band <= cu_count / 2; grid_out is
+ * then min(nb, cu_count), each workgroup claiming rows by ticket until none is left.  Otherwise one tile and one
+ * workgroup per block row.  Either out pointer may be NULL.  In the environment (read at every sweep):
+ * OISAT_TRSV_TWO_TILES=0|1 overrides the choice (both are always legal), OISAT_TRSV_MAX_WGS=<n >= 1> caps the grid;
+ * anything else in either is OISAT_EINVAL.  Neither changes a bit of any result. */
+int oisat_trsv_plan(int64_t nb, int band, int cu_count, int32_t* two_tiles_out, int32_t* grid_out);
+
 /* z <- L^-T L^-1 z  (dev double[m], fp32 factor, double accumulation). */
 int oisat_potrs(oisat_ctx* h, const float* L, int64_t m, int64_t ld, double* z_inout);
 

@@ -1343,10 +1343,11 @@ __device__ __forceinline__ bool wait_payload(const double* src, double* vec, Trs
 // sol must arrive filled with kTrsvEmpty.
 // A workgroup claims block rows by ticket until none is left (round 3).  A row waits only for rows with lower tickets, and
 // every claimed row is in the hands of a running workgroup, so the sweep drains with ANY number of resident workgroups.
-// The grid is one workgroup per OISAT_TRSV_ROWS_PER_WG rows; the default stays 1 (a workgroup per row, as in rounds 1-2):
-// fewer, persistent workgroups would hold fewer of the slots the other group's GEMMs run on, but a row's producers are
-// then fetched one agent-scope round trip after the other instead of while waiting for its turn -- measured at 4 rows per
-// workgroup: 0.54 vs 0.25 ms per sweep at 10,000 observations, a localised month 73.3 vs 69.6 ms.
+// The grid is oisat_trsv_plan's (trsv_solve): a workgroup per row for a dense factor -- with fewer, a row's producers are
+// fetched one agent-scope round trip after the other instead of while waiting for its turn (measured at 4 rows per
+// workgroup: 0.54 vs 0.25 ms per sweep at 10,000 observations, a localised month 73.3 vs 69.6 ms) --, one workgroup per CU
+// with two LDS tiles for a narrow-banded enveloped factor, where only the rows within a band width of the front have
+// anything to do and each workgroup serves several rows one after the other.
 // one block row of a sweep: claim order tk (0 .. nb-1) of ITS system; false = a producer never showed up (bounded spin)
 // DAG: the row is a task of the task-graph launch (dense_dag.inc) -- the vectors are then shared with workgroups of the SAME
 // launch across sweeps, so every store to them is an agent-scope (write-through) store and every load of a word another
@@ -1386,7 +1387,9 @@ __device__ __forceinline__ bool trsv_row(const float* __restrict__ L, int64_t ld
     const float* base = TRANSPOSE ? L + (int64_t)(nb - 1) * NB * ld + (int64_t)b * NB : L + (int64_t)b * NB * ld;
     const int64_t hop = TRANSPOSE ? -(int64_t)NB * ld : (int64_t)NB;      // pointer step from one producer's block to the next
     // two_tiles: T_b goes to a second LDS tile right away -- it depends on nobody -- so that the last pass finds it there
-    // instead of loading and staging it behind the last producer's hand-over
+    // instead of loading and staging it behind the last producer's hand-over.  A workgroup that serves several rows restages
+    // it per row: the claim loop's top barrier stands between the previous row's last read of tileT and this store, and a
+    // barrier (wait_payload's, or the last pass's) between this store and the read -- also for a row without producers.
     if (two_tiles) {
         TILE_PREFETCH(Tb, NB)
         float* tile = tileT;                                // TILE_STORE writes to the `tile` in scope
@@ -2079,6 +2082,45 @@ __global__ __launch_bounds__(1024) void resid_check_batched_kernel(const SolveMe
 // control block, so a solve is exactly two launches.  st: skip both when the refinement has converged.  zout (m entries):
 // where the solution is to be written (accumulate = 0) or added (1) besides rhs.  fwd_done: the forward sweep of this right-
 // hand side ran inside the factorization launch (oisat_potrf_env_fwd) and left both vectors as trsv_fwd would: backward only.
+// The launch shape of the sweeps (host only, include/oisat.h).  A second LDS tile per workgroup (132 KB: one workgroup per CU)
+// takes T_b off the critical path of every hand-over; it is given
+//  - when every block row gets its own CU at once (nb <= cu_count), or
+//  - when the factor is ENVELOPED and its band is at most half the CUs: only the `band` rows behind the front can make
+//    progress, so one workgroup per CU serves them with as many again staging ahead, each workgroup claiming row after row
+//    by ticket.  The workgroups beyond cu_count would only draw a ticket >= nb and leave: grid = min(nb, cu_count).
+// Everything else -- a large dense system, bound by streaming L -- keeps one tile, a workgroup per row and two per CU in flight.
+extern "C" int oisat_trsv_plan(int64_t nb, int band, int cu_count, int32_t* two_tiles_out, int32_t* grid_out) {
+    ARG_CHECK(nb >= 1 && nb <= INT32_MAX && band >= 0 && cu_count >= 0);
+    const bool two = nb <= cu_count || (band > 0 && band <= cu_count / 2);
+    if (two_tiles_out) *two_tiles_out = two ? 1 : 0;
+    if (grid_out) *grid_out = (int32_t)(two ? std::min<int64_t>(nb, cu_count) : nb);
+    return OISAT_OK;
+}
+
+// OISAT_TRSV_TWO_TILES=0|1 forces the choice of oisat_trsv_plan, OISAT_TRSV_MAX_WGS=<n >= 1> caps the sweeps' grid (A/B runs,
+// tests: a few workgroups serving many rows each at a small size); read at every call, like OISAT_ENVELOPE.  Forcing two tiles
+// is always legal: a row waits only for lower tickets, and every claimed ticket is held by a running workgroup.
+static int trsv_launch_shape(const oisat_ctx* h, const ChFactor& f, int nb, int* two_out, int* grid_out) {
+    int32_t two = 0, grid = 0;
+    if (int rc = oisat_trsv_plan(nb, f.env != nullptr ? f.band : 0, h->cu_count, &two, &grid)) return rc;
+    const char* e = getenv("OISAT_TRSV_TWO_TILES");
+    if (e && *e) {
+        ARG_CHECK((e[0] == '0' || e[0] == '1') && e[1] == '\0');
+        two = e[0] == '1';
+        grid = two && h->cu_count > 0 ? std::min(nb, h->cu_count) : nb;
+    }
+    e = getenv("OISAT_TRSV_MAX_WGS");
+    if (e && *e) {
+        char* end = nullptr;
+        const long cap = strtol(e, &end, 10);
+        ARG_CHECK(end != e && *end == '\0' && cap >= 1);
+        if (cap < grid) grid = (int32_t)cap;
+    }
+    *two_out = two;
+    *grid_out = grid;
+    return OISAT_OK;
+}
+
 int trsv_solve(oisat_ctx* h, const ChFactor& f, double* rhs_pad, double* fwd, const SolveState* st, double* zout, int accumulate,
                bool fwd_done = false) {
     const int nb = (int)(f.mp / NB);
@@ -2087,14 +2129,10 @@ int trsv_solve(oisat_ctx* h, const ChFactor& f, double* rhs_pad, double* fwd, co
     if (int rc = status_ws(h, nullptr, &base)) return rc;
     unsigned* err_total = (unsigned*)base;
     char* ctl = base + 16;
-    // a second LDS tile per workgroup (132 KB: one workgroup per CU) when every block row still gets its own CU at once;
-    // larger systems keep two workgroups per CU in flight.  (Dense, they are bound by streaming L.  An ENVELOPED sweep of the
-    // headline size streams 4 GB and is a chain of hand-overs again, 5.1 us each against 3.1 with the second tile; extending
-    // the rule to narrow bands is the open experiment of DESIGN.md section 9.)
-    constexpr bool allow_two = true;
-    constexpr int rows_per_wg = 1;                       // (four rows per workgroup: 0.54 vs 0.25 ms per sweep at 1e4 observations)
-    const int grid = (int)cdiv(nb, rows_per_wg);
-    const int two = allow_two && grid <= h->cu_count ? 1 : 0;
+    // (rows per workgroup are not fixed: a workgroup claims rows by ticket until none is left.  A dense system on a quarter of
+    // the workgroups: 0.54 vs 0.25 ms per sweep at 1e4 observations -- there every row has work from the start.)
+    int two = 0, grid = 0;
+    if (int rc = trsv_launch_shape(h, f, nb, &two, &grid)) return rc;
     const size_t shm = sizeof(float) * NB * TLD * (two ? 2 : 1);
     if (!fwd_done) {
         OISAT_LAUNCH(h, "trsv_fwd", (trsv_pipe_kernel<0>), dim3(grid), dim3(256), shm, f.S, f.ld, (const float*)f.tinv, nb, rhs_pad, fwd,
@@ -2326,6 +2364,9 @@ static int potrf_impl(oisat_ctx* h, float* S, int64_t m, int64_t ld, int* info_h
     h->factor.ld = ld;
     h->factor.tinv = tinv;
     h->factor.env = env_dev;
+    h->factor.band = 0;
+    if (first && env_dev)
+        for (int64_t b = 0; b < mpb; ++b) h->factor.band = std::max(h->factor.band, (int)(b - first[b]) + 1);
     if (info_host) {
         int* pin = (int*)oisat_pinned(h, 64);
         if (!pin) return OISAT_ENOMEM;
@@ -2989,6 +3030,7 @@ extern "C" int oisat_factor_adopt(oisat_ctx* h, const float* L, int64_t m, int64
     h->factor.ld = ld;
     h->factor.tinv = tinv;
     h->factor.env = nullptr;                                // (adopted without an envelope: swept densely)
+    h->factor.band = 0;
     h->factor.fwd_d = nullptr;
     return OISAT_OK;
 }

@@ -33,6 +33,8 @@ struct ChFactor {                // what the triangular solves need besides L: t
     int64_t m = 0, mp = 0, ld = 0;
     float* tinv = nullptr;       // [mp/128][128][128]: inverted diagonal blocks, row-major
     const int* env = nullptr;    // device, first[mp/128] | last[mp/128]: the factor's block envelope (oisat_potrf_env), or nullptr = dense
+    int band = 0;                // enveloped: max over b of (b - first[b]) + 1 block rows, from the host table; 0 = dense / adopted
+                                 // (the sweeps' launch rule, oisat_trsv_plan)
     // oisat_potrf_env_fwd: the right-hand side whose forward vector the factorization launch left in workspace 5 (with the
     // right-hand side re-armed and the solve state reset), or nullptr.  oisat_gain_solve of the same d takes it, once.
     const double* fwd_d = nullptr;

@@ -104,6 +104,7 @@ SIGNATURES = {
                                              C.POINTER(C.c_int)]),
     "oisat_cov_build_cover": (C.c_int, [_ptr, _ptr, _i64, _ptr, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "oisat_potrf_env_fwd": (C.c_int, [_c_ctx, _ptr, _i64, _i64, _ptr, _ptr, _ptr, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "oisat_trsv_plan": (C.c_int, [_i64, C.c_int, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "oisat_potrs": (C.c_int, [_c_ctx, _ptr, _i64, _i64, _ptr]),
     "oisat_cov_residual": (C.c_int, [_c_ctx, _ptr, _ptr, _ptr, _i64, C.c_double, _ptr, _ptr, _ptr, _ptr]),
     "oisat_gain_solve": (C.c_int, [_c_ctx, _ptr, _ptr, _ptr, _ptr, _i64, _i64, C.c_double, _ptr, C.c_int, _ptr,
