@@ -393,6 +393,22 @@ int oisat_potrf(oisat_ctx* h, float* S, int64_t m, int64_t ld, int* info_host);
  * the cut-off 2^-n for every size; 52 reproduces oisat_envelope's table exactly. */
 int oisat_envelope(const double* lat_sorted, int64_t m, double g, int32_t* env_out);
 int oisat_factor_envelope(const double* lat_sorted, int64_t m, double g, int32_t* env_out);
+/* The far stretch of the factor's K-loops (csrc/dense_chol.hip: kFactorFarBits).
+ * oisat_factor_far (host only): far_out[i], first[i] <= far_out[i] <= i, = the first block column of block row i that is NOT
+ * far: every correlation between an observation of block row i and one of a block column k < far_out[i] is below the far
+ * cut-off.  The enveloped task graph runs the K-blocks first[i] <= k < far_out[i] of the row's tiles with both operands
+ * rounded to bf16 (fp32 accumulation): the factor is oisat_gain_solve's preconditioner only.  first = the table of
+ * oisat_factor_envelope (or oisat_envelope) for the same observations and g.  The stretch is on where
+ * oisat_factor_envelope's rule picks the narrow table (tile-work-bound systems, no forced cut-off); everywhere else, and
+ * under OISAT_ENVELOPE=0, far_out == first: no stretch, the factor's bits are those of the fp32 task graph.
+ * OISAT_FACTOR_FAR_BITS=<n> in the environment (read at every call; 0 <= n <= 52, anything else is OISAT_EINVAL): 0 switches
+ * the stretch off, n >= 1 forces the cut-off 2^-n at every enveloped size, also under a forced OISAT_FACTOR_CUT_BITS (an
+ * n at or above the table's own cut-off leaves nothing far).
+ * oisat_set_factor_far: hands the table (host int32[nb], copied; NULL / 0 = none) to the NEXT oisat_potrf_env /
+ * oisat_potrf_env_fwd on this handle, which consumes it whatever its outcome and checks it against its own first.  Without
+ * it, and in every other factorization (oisat_potrf, the batched ones), there is no far stretch. */
+int oisat_factor_far(const double* lat_sorted, int64_t m, double g, const int32_t* first, int32_t* far_out);
+int oisat_set_factor_far(oisat_ctx* h, const int32_t* far, int64_t nb);
 int oisat_cov_build_env(oisat_ctx* h, const double* oxyz, const double* osig, const double* ovar, int64_t m,
                         double g, float* S, int64_t ld, const int32_t* env_dev);
 int oisat_potrf_env(oisat_ctx* h, float* S, int64_t m, int64_t ld, const int32_t* first, const int32_t* env_dev,
@@ -521,6 +537,12 @@ int oisat_gain_diag(oisat_ctx* h, const float* L, int64_t m, int64_t ld, const d
  * ticket, or is its system's chain) and of that bound. */
 int oisat_dag_task_order(int nsys, const int32_t* block_rows, int wave, int32_t* tasks_out, int64_t capacity,
                          int64_t* ntasks_out, int32_t* reserve_out, int32_t* max_wave_chains_out);
+/* ... and of the ENVELOPED launch of one system of nb <= 1024 block rows (oisat_potrf_env): first = its envelope, far = its
+ * far stretch (oisat_factor_far) or NULL.  A bulk task's first word is kind | k0 << 8 | kfar << 18 (ten bits each): its
+ * K-loop runs over the block columns k0 = first[i] .. kend - 1 (kend = j, PRE: j - 1), the blocks k0 .. kfar - 1 of it on
+ * the bf16 pipe, k0 <= kfar = clamp(far[i]) <= kend. */
+int oisat_dag_task_order_env(int nb, const int32_t* first, const int32_t* far, int32_t* tasks_out, int64_t capacity,
+                             int64_t* ntasks_out);
 
 /* Schedule of the factorizations this handle runs from now on (oisat_potrf, batches made by oisat_batch_create): 1 = the
  * task graph (ONE persistent launch of left-looking tile tasks, csrc/dense_dag.inc) wherever it applies, 0 = the recursion

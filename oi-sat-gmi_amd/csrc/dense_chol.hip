@@ -2258,8 +2258,9 @@ static bool fwd_in_launch_off() {
 // first / env_dev: nullptr (dense), or the envelope of S (host: first[mpb]; device: first[mpb] | last[mpb], oisat_envelope)
 // fwd_d (device double[m]) or nullptr: the right-hand side whose first forward sweep rides in the task-graph launch
 // (oisat_potrf_env_fwd).  schedule_out (optional): OISAT_SCHEDULE_* of what ran.
+// far (host int32[mpb], with first) or nullptr: the far stretch of every block row (oisat_factor_far), bf16 K-blocks in the task graph
 static int potrf_impl(oisat_ctx* h, float* S, int64_t m, int64_t ld, int* info_host, const int32_t* first, const int32_t* env_dev,
-                      const double* fwd_d = nullptr, int* schedule_out = nullptr) {
+                      const double* fwd_d = nullptr, int* schedule_out = nullptr, const int32_t* far = nullptr) {
     ARG_CHECK(h && S && m > 0);
     h->factor.fwd_d = nullptr;                                  // whatever comes of this call, the last factor's forward vector is history
     if (schedule_out) *schedule_out = OISAT_SCHEDULE_OTHER;
@@ -2290,7 +2291,8 @@ static int potrf_impl(oisat_ctx* h, float* S, int64_t m, int64_t ld, int* info_h
         }
     }
     int rc;
-    if (!lookahead && !getenv("OISAT_POTRF") && dag_wanted(h, mpb, 1) && dag_fits(1, dag_slots(h))) {
+    // (an enveloped ticket has ten bits for a block column: larger systems take the recursion, which reads the build's zeros)
+    if (!lookahead && !getenv("OISAT_POTRF") && dag_wanted(h, mpb, 1) && dag_fits(1, dag_slots(h)) && (!first || mpb <= kDagEnvMaxBlocks)) {
         // the plan of this (S, tinv, ld, block rows, enveloped or not) -- a handle keeps the last few (a lane that factors its
         // tiles one after the other in ONE shared buffer meets the same few sizes month after month).  An enveloped plan's
         // ticket list belongs to ONE envelope: the table itself is compared, and another envelope refills the plan's buffers.
@@ -2300,8 +2302,9 @@ static int potrf_impl(oisat_ctx* h, float* S, int64_t m, int64_t ld, int* info_h
             if (c.plan && c.S == S && c.tinv == tinv && c.ld == ld && c.mpb == mpb && c.enveloped == (first != nullptr) && c.fwd == ride) hit = &c;
         if (hit && first) {
             DagPlan& pl = *(DagPlan*)hit->plan;
-            if (memcmp(pl.first.data(), first, sizeof(int) * (size_t)mpb) != 0)
-                if (int rf = dag_plan_refill(pl, first, h->stream)) return rf;
+            if (memcmp(pl.first.data(), first, sizeof(int) * (size_t)mpb) != 0 ||
+                memcmp(pl.far.data(), far ? far : first, sizeof(int) * (size_t)mpb) != 0)
+                if (int rf = dag_plan_refill(pl, first, far, h->stream)) return rf;
         }
         if (!hit) {
             DagSingle* slot = nullptr;
@@ -2320,7 +2323,7 @@ static int potrf_impl(oisat_ctx* h, float* S, int64_t m, int64_t ld, int* info_h
                 shape.refine = 0;
                 shape.fwd_only = true;
             }
-            slot->plan = dag_plan_create(std::vector<BatchMat>{BatchMat{S, tinv, ld, m, (int)mpb, 0}}, h->stream, shape, first);
+            slot->plan = dag_plan_create(std::vector<BatchMat>{BatchMat{S, tinv, ld, m, (int)mpb, 0}}, h->stream, shape, first, first ? far : nullptr);
             if (!slot->plan) return OISAT_ENOMEM;
             slot->S = S; slot->tinv = tinv; slot->ld = ld; slot->mpb = mpb; slot->enveloped = first != nullptr; slot->fwd = ride;
             hit = slot;
@@ -2470,20 +2473,102 @@ extern "C" int oisat_factor_envelope(const double* lat_sorted, int64_t m, double
     return OISAT_OK;
 }
 
+// The far stretch of the factor's K-loops.  Left of the 2^-kFactorCutBits table every entry of S is dropped; just inside it, in
+// the block columns first[i] <= k < far[i], every correlation between an observation of block row i and one of block column k
+// is still below 2^-kFactorFarBits, and the products L(i,k) L(j,k)^T of those K-blocks add terms bounded by such entries.  The
+// factor is a preconditioner (kFactorCutBits above): rounding BOTH operands of those products to bf16 -- relative error 2^-8
+// of a term that small -- is of the order of what the cut-off drops already, and the bf16 matrix pipe issues them at 1/16 of
+// the fp32 pipe's cycles (dense_dag.inc: dag_seg_bf16).  On by default only where the narrow table is: tile-work-bound
+// systems, no forced OISAT_FACTOR_CUT_BITS.  OISAT_FACTOR_FAR_BITS=<n> (read at every call): 0 = off; 1 .. 52 forces 2^-n
+// at every enveloped size (also under a forced cut-off; a value at or above the table's own cut-off leaves nothing far).
+// The value is a measurement, by the protocol of kFactorCutBits (profiles/EXPERIMENTS.md, "The far stretch on the bf16 pipe"): on
+// the same four months 24 .. 14 bits leave the first residual within 1.0 % of the run without a stretch, the number of solves
+// and the last residual (within 4 %) where they were; 12 bits raise the first residual by 6 - 14 %.  Kept: the smallest
+// admissible value, 14, plus 4 bits of headroom for a denser month.  Headline: 872 522 of 2 519 868 K-blocks are far (0.346),
+// potrf_dag 84.0 -> 67.2 ms, the step 100.6 -> 83.8 ms.
+constexpr double kFactorFarBits = 18.0;
+
+extern "C" int oisat_factor_far(const double* lat_sorted, int64_t m, double g, const int32_t* first, int32_t* far_out) {
+    ARG_CHECK(lat_sorted && first && far_out && m > 0 && g >= 0.0);
+    for (int64_t i = 1; i < m; ++i) ARG_CHECK(lat_sorted[i] >= lat_sorted[i - 1]);
+    const int64_t nb = cdiv(m, NB);
+    ARG_CHECK(envelope_table_ok(first, nb));
+    double bits = kFactorFarBits;
+    bool on = false;
+    const char* e = getenv("OISAT_FACTOR_FAR_BITS");
+    if (e && *e) {
+        char* end = nullptr;
+        bits = strtod(e, &end);
+        ARG_CHECK(end != e && *end == '\0' && bits >= 0.0 && bits <= kCutBits);
+        on = bits >= 1.0;
+        ARG_CHECK(on || bits == 0.0);
+    } else {
+        const char* c = getenv("OISAT_FACTOR_CUT_BITS");
+        if (!(c && *c)) {                                       // the default rule's own choice: the narrow table, or not
+            std::vector<int32_t> narrow(2 * (size_t)nb);
+            envelope_table(lat_sorted, m, g, kFactorCutBits, narrow.data());
+            on = (double)envelope_ksteps(narrow.data(), nb) > kFactorMinKstepsPerRow * (double)nb;
+        }
+    }
+    if (on && !oisat_envelope_off()) {
+        std::vector<int32_t> t(2 * (size_t)nb);
+        envelope_table(lat_sorted, m, g, bits, t.data());
+        for (int64_t i = 0; i < nb; ++i) far_out[i] = std::min<int32_t>(std::max(t[i], first[i]), (int32_t)i);
+    } else {
+        for (int64_t i = 0; i < nb; ++i) far_out[i] = first[i];
+    }
+    return OISAT_OK;
+}
+
+extern "C" int oisat_set_factor_far(oisat_ctx* h, const int32_t* far, int64_t nb) {
+    ARG_CHECK(h != nullptr && nb >= 0 && (far != nullptr || nb == 0));
+    h->factor_far.assign(far, far + nb);
+    return OISAT_OK;
+}
+
+// the table the caller set for this factorization (empty: none) against its envelope
+static bool far_table_ok(const std::vector<int32_t>& far, const int32_t* first, int64_t nb) {
+    if (far.empty()) return true;
+    if ((int64_t)far.size() != nb) return false;
+    for (int64_t i = 0; i < nb; ++i)
+        if (far[i] < first[i] || far[i] > i) return false;
+    return true;
+}
+
+extern "C" int oisat_dag_task_order_env(int nb, const int32_t* first, const int32_t* far, int32_t* tasks_out, int64_t capacity,
+                                        int64_t* ntasks_out) {
+    ARG_CHECK(nb >= 1 && nb <= kDagEnvMaxBlocks && first && ntasks_out && (tasks_out || capacity == 0));
+    ARG_CHECK(envelope_table_ok(first, nb));
+    if (far)
+        for (int i = 0; i < nb; ++i) ARG_CHECK(far[i] >= first[i] && far[i] <= i);
+    DagOrder order;
+    dag_task_order(std::vector<int>{nb}, 0, order, first, far);
+    *ntasks_out = (int64_t)order.tasks.size();
+    if ((int64_t)order.tasks.size() > capacity) return capacity == 0 ? OISAT_OK : OISAT_EINVAL;
+    memcpy(tasks_out, order.tasks.data(), sizeof(int4) * order.tasks.size());
+    return OISAT_OK;
+}
+
 extern "C" int oisat_potrf_env(oisat_ctx* h, float* S, int64_t m, int64_t ld, const int32_t* first, const int32_t* env_dev,
                                int* info_host) {
-    ARG_CHECK(h && first && env_dev && m > 0);
-    ARG_CHECK(envelope_table_ok(first, cdiv(m, NB)));
+    ARG_CHECK(h != nullptr);
+    std::vector<int32_t> far;
+    far.swap(h->factor_far);                                    // one-shot, whatever this call's outcome
+    ARG_CHECK(first && env_dev && m > 0);
+    ARG_CHECK(envelope_table_ok(first, cdiv(m, NB)) && far_table_ok(far, first, cdiv(m, NB)));
     if (oisat_envelope_off()) return potrf_impl(h, S, m, ld, info_host, nullptr, nullptr);
-    return potrf_impl(h, S, m, ld, info_host, first, env_dev);
+    return potrf_impl(h, S, m, ld, info_host, first, env_dev, nullptr, nullptr, far.empty() ? nullptr : far.data());
 }
 
 extern "C" int oisat_potrf_env_fwd(oisat_ctx* h, float* S, int64_t m, int64_t ld, const int32_t* first, const int32_t* env_dev,
                                    const double* d, int* info_host, int* schedule_out) {
-    ARG_CHECK(h && first && env_dev && d && m > 0);
-    ARG_CHECK(envelope_table_ok(first, cdiv(m, NB)));
+    ARG_CHECK(h != nullptr);
+    std::vector<int32_t> far;
+    far.swap(h->factor_far);                                    // one-shot, whatever this call's outcome
+    ARG_CHECK(first && env_dev && d && m > 0);
+    ARG_CHECK(envelope_table_ok(first, cdiv(m, NB)) && far_table_ok(far, first, cdiv(m, NB)));
     if (oisat_envelope_off()) return potrf_impl(h, S, m, ld, info_host, nullptr, nullptr, d, schedule_out);
-    return potrf_impl(h, S, m, ld, info_host, first, env_dev, d, schedule_out);
+    return potrf_impl(h, S, m, ld, info_host, first, env_dev, d, schedule_out, far.empty() ? nullptr : far.data());
 }
 
 extern "C" int oisat_potrs(oisat_ctx* h, const float* L, int64_t m, int64_t ld, double* z_inout) {

@@ -174,6 +174,76 @@ __device__ __forceinline__ void dag_seg(float* __restrict__ lds, const DagLane& 
 #undef DAG_FRAG
 }
 
+// The same K-segment on the bf16 matrix pipe -- the FAR stretch of a bulk task's K-loop (kfar, "Far stretch" at
+// dag_task_order): over the SAME fp32 LDS image and the same LDS-DMA fill as dag_seg, nothing changes in memory.  A K-step
+// of 32 is two k-chunks of 16.  v_mfma_f32_32x32x16_bf16 takes A[row lane & 31][k = 8 (lane >> 5) + e], e = 0 .. 7, from
+// each lane -- and B likewise --, so a lane reads the 8 consecutive floats 16 c + 8 fh .. + 7 of its operand row: the logical
+// 16-byte chunks 4 c + 2 fh and + 1 through the image's XOR swizzle (over the 32 rows of a half-wave the same bank pattern
+// as dag_seg's fragment reads), rounds them to nearest even with v_cvt_pk_bf16_f32 and issues the four MFMAs of its 64 x 64
+// quadrant into the same accumulators (the C/D layout does not depend on the operand type).  1/16 of dag_seg's MFMA cycles
+// per K-step, the same LDS reads; what bounds a far K-step is the landing of its LDS-DMA (one step of look-ahead), and a
+// workgroup that waits for it leaves the matrix pipe to its CU-mate.
+typedef __attribute__((ext_vector_type(8))) __bf16 dag_bf16x8;
+typedef __attribute__((ext_vector_type(4))) unsigned dag_u32x4;
+__device__ __forceinline__ unsigned dag_pk_bf16(float lo, float hi) {
+    unsigned r;
+    asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(r) : "v"(lo), "v"(hi));
+    return r;
+}
+__device__ __forceinline__ dag_bf16x8 dag_pack8(const float4& a, const float4& b) {
+    const dag_u32x4 u = {dag_pk_bf16(a.x, a.y), dag_pk_bf16(a.z, a.w), dag_pk_bf16(b.x, b.y), dag_pk_bf16(b.z, b.w)};
+    return __builtin_bit_cast(dag_bf16x8, u);
+}
+__device__ __forceinline__ void dag_seg_bf16(float* __restrict__ lds, const DagLane& L, const float* Ad, int64_t lda, const float* Bd, int64_t ldb,
+                                             int nkt, f32x16& acc00, f32x16& acc01, f32x16& acc10, f32x16& acc11) {
+    typedef __attribute__((address_space(1))) const void* gptr_t;
+    typedef __attribute__((address_space(3))) void* lptr_t;
+    constexpr int IMG = NB * BK;
+#define DAG_DMA(buf, k0)                                                                                           \
+    do {                                                                                                           \
+        _Pragma("unroll") for (int i = 0; i < 4; ++i) {                                                            \
+            __builtin_amdgcn_global_load_lds((gptr_t)(Ad + (int64_t)(8 * i) * lda + (k0)),                         \
+                                             (lptr_t)(lds + ((buf) * 2 + 0) * IMG + (L.wid * 32 + 8 * i) * BK), 16, 0, 0); \
+            __builtin_amdgcn_global_load_lds((gptr_t)(Bd + (int64_t)(8 * i) * ldb + (k0)),                         \
+                                             (lptr_t)(lds + ((buf) * 2 + 1) * IMG + (L.wid * 32 + 8 * i) * BK), 16, 0, 0); \
+        }                                                                                                          \
+    } while (0)
+    // the 8 floats of k-chunk c of row `row` (an offset into an operand image), as two 16-byte reads
+#define DAG_RD8(lo, hi, buf, op, row, c)                                                                                              \
+    do {                                                                                                                              \
+        lo = *reinterpret_cast<const float4*>(lds + ((buf) * 2 + (op)) * IMG + (row) + 4 * ((4 * (c) + 2 * L.fh) ^ L.sw));            \
+        hi = *reinterpret_cast<const float4*>(lds + ((buf) * 2 + (op)) * IMG + (row) + 4 * ((4 * (c) + 2 * L.fh + 1) ^ L.sw));        \
+    } while (0)
+#define DAG_CHUNK(buf, c)                                                                                          \
+    do {                                                                                                           \
+        float4 a0l, a0h, a1l, a1h, b0l, b0h, b1l, b1h;                                                             \
+        DAG_RD8(a0l, a0h, buf, 0, L.arow, c);                                                                      \
+        DAG_RD8(a1l, a1h, buf, 0, L.arow + 32 * BK, c);                                                            \
+        DAG_RD8(b0l, b0h, buf, 1, L.brow, c);                                                                      \
+        DAG_RD8(b1l, b1h, buf, 1, L.brow + 32 * BK, c);                                                            \
+        const dag_bf16x8 a0 = dag_pack8(a0l, a0h), a1 = dag_pack8(a1l, a1h);                                       \
+        const dag_bf16x8 b0 = dag_pack8(b0l, b0h), b1 = dag_pack8(b1l, b1h);                                       \
+        acc00 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0, b0, acc00, 0, 0, 0);                                   \
+        acc01 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0, b1, acc01, 0, 0, 0);                                   \
+        acc10 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, b0, acc10, 0, 0, 0);                                   \
+        acc11 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, b1, acc11, 0, 0, 0);                                   \
+    } while (0)
+    DAG_DMA(0, 0);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    for (int kt = 0; kt < nkt; ++kt) {
+        const int cur = kt & 1;
+        if (kt + 1 < nkt) DAG_DMA(cur ^ 1, (kt + 1) * BK);       // the other buffer is free since the last barrier
+        DAG_CHUNK(cur, 0);
+        DAG_CHUNK(cur, 1);
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");        // this wave's DMA pieces of K-step kt+1 have landed ...
+        __syncthreads();                                        // ... everyone else's too; every read of K-step kt is back
+    }
+#undef DAG_DMA
+#undef DAG_RD8
+#undef DAG_CHUNK
+}
+
 // The tile held in the accumulators becomes the operand image of a 128x128x128 product with ITSELF (the chain's rank-128
 // update L(j+1,j) L(j+1,j)^T): element (row r, column c) goes to K-step image c / 32 at the swizzled position the fragment reads
 // expect -- the four images fill the workgroup's LDS exactly -- and after a barrier every wave accumulates from LDS alone.
@@ -247,8 +317,12 @@ __device__ __forceinline__ const float* dag_src(const float* tile0, int64_t ld, 
 // DAG_SUB (i = j + 1: k < j, leaves the updated tile, publishes sub[j]), DAG_PRE (i = j: k < j - 1, publishes pre[j]).
 // k0 (wave-uniform, from the ticket): the K-loop's first block column -- 0, or first[i] of an ENVELOPED system ("Envelope" at
 // dag_task_order): the blocks left of it are exact zeros that nobody wrote or reads, final by definition.
-__device__ __forceinline__ bool dag_tile_task(const DagSys& sy, int kind, int k0, int i, int j, DagCtl* ctl, float* lds, const DagLane& L, int* s_flag,
-                                              int* s_kav, long long* tr /* thread 0, tracing: [2] += time spent polling */) {
+// kfar (wave-uniform, from the ticket, k0 <= kfar <= kend): the block columns k0 .. kfar - 1 are the row's FAR stretch -- every
+// correlation between an observation of block row i and one of those block columns is below the far cut-off -- and their
+// K-blocks run on the bf16 pipe (dag_seg_bf16); FAR = false (the launch that also solves): the ticket's kfar is ignored.
+template <bool FAR>
+__device__ __forceinline__ bool dag_tile_task(const DagSys& sy, int kind, int k0, int kfar, int i, int j, DagCtl* ctl, float* lds, const DagLane& L,
+                                              int* s_flag, int* s_kav, long long* tr /* thread 0, tracing: [2] += time spent polling */) {
     const int t = threadIdx.x;
     const int kend = kind == DAG_PRE ? j - 1 : j;
     int* const st = sy.state;
@@ -270,9 +344,15 @@ __device__ __forceinline__ bool dag_tile_task(const DagSys& sy, int kind, int k0
             *s_kav = a < kend ? a : kend;
         }
         if (!dag_join(ok, s_flag)) return false;
-        const int kav = *s_kav;
-        dag_seg(lds, L, dag_src(Arow + (int64_t)k * NB, sy.ld, L), sy.ld, dag_src(Brow + (int64_t)k * NB, sy.ld, L), sy.ld, (kav - k) * (NB / BK),
-                acc00, acc01, acc10, acc11);
+        int kav = *s_kav;
+        if (FAR && k < kfar) {                                  // a segment ends where the far stretch does
+            kav = kav < kfar ? kav : kfar;
+            dag_seg_bf16(lds, L, dag_src(Arow + (int64_t)k * NB, sy.ld, L), sy.ld, dag_src(Brow + (int64_t)k * NB, sy.ld, L), sy.ld,
+                         (kav - k) * (NB / BK), acc00, acc01, acc10, acc11);
+        } else {
+            dag_seg(lds, L, dag_src(Arow + (int64_t)k * NB, sy.ld, L), sy.ld, dag_src(Brow + (int64_t)k * NB, sy.ld, L), sy.ld, (kav - k) * (NB / BK),
+                    acc00, acc01, acc10, acc11);
+        }
         k = kav;
         __syncthreads();                                        // s_kav / s_flag may be rewritten
     }
@@ -928,7 +1008,7 @@ __global__ __launch_bounds__(256, 2) void potrf_dag_kernel(const DagSys* __restr
             if (ready_task) ok = dag_fwd_row_task(sy, task.z, sv, ctl, lds);
             else if ((task.x & 255) == DAG_CHAIN)
                 ok = dag_chain_task(sy, ctl, info, lds, L, &s_flag, trace ? trace + 4 * (int64_t)(ntasks + sv.qcap) + 8 * (int64_t)task.z : nullptr, &sv);
-            else ok = dag_tile_task(sy, task.x & 255, task.x >> 8, task.z, task.w, ctl, lds, L, &s_flag, &s_kav, tr);
+            else ok = dag_tile_task<true>(sy, task.x & 255, (task.x >> 8) & 1023, task.x >> 18, task.z, task.w, ctl, lds, L, &s_flag, &s_kav, tr);
         } else if (ready_task) {
             const SolveMember mb = sv.mem[task.y];
             if (task.x == DAG_FWD) ok = dag_sweep_task<0>(sy, mb, task.y, task.z, task.w, sv, ctl, lds, &s_kav, L.spin);
@@ -940,7 +1020,8 @@ __global__ __launch_bounds__(256, 2) void potrf_dag_kernel(const DagSys* __restr
             ok = dag_chain_task(sy, ctl, info, lds, L, &s_flag, trace ? trace + 4 * (int64_t)(ntasks + (SOLVE ? sv.qcap : 0)) + 8 * (int64_t)task.z : nullptr,
                                 SOLVE ? &sv : (const DagSolve*)nullptr);
         } else {
-            ok = dag_tile_task(sy, task.x & 255, task.x >> 8, task.z, task.w, ctl, lds, L, &s_flag, &s_kav, tr);      // (kind | k0 << 8)
+            ok = dag_tile_task<SOLVE != DAG_SOLVE_ALL>(sy, task.x & 255, (task.x >> 8) & 1023, task.x >> 18, task.z, task.w, ctl, lds, L, &s_flag,
+                                                       &s_kav, tr);                                          // (kind | k0 << 8 | kfar << 18)
         }
         if (tr && t == 0) {
             tr[1] = wall_clock64();
@@ -1005,6 +1086,7 @@ struct DagPlan {
     std::vector<DagSys> sys_host;
     std::vector<int4> tasks_host;
     std::vector<int> first;                                     // the envelope this single-system plan's ticket list was made for (empty: dense)
+    std::vector<int> far;                                       // ... and its far stretch (oisat_factor_far; no stretch: equal to first)
     size_t tasks_cap = 0;                                       // tickets tasks_dev holds (an enveloped plan: the dense list's, so a new envelope refills it)
     long long* trace_dev = nullptr;                             // OISAT_DAG_TRACE: [ntasks][4] + [chain_rows][8] stamps of the last launch
 };
@@ -1028,6 +1110,7 @@ struct DagOrder {
 };
 constexpr int kDagWave = 8;                                     // systems per wave of small systems (12, 16, 24 and 48 measure the same to 0.2 ms of a month's 48.7)
 constexpr double kDagEnvLead = 0.15;                            // enveloped systems: columns a task is drawn early per block of its K-loop (below)
+constexpr double kDagEnvLeadFar = 0.2;                          // ... where part of the K-loops is a far stretch on the bf16 pipe (below)
 constexpr int kDagWave0Max = 64;                                // wave 0 holds at most this many chains
 // Envelope (first != nullptr: ONE system whose rows are in an order that makes it a band, first[i] = first block column of
 // block row i that can be non-zero, non-decreasing, first[i] <= max(i - 1, 0)).  A Cholesky factor has no fill left of its
@@ -1036,7 +1119,13 @@ constexpr int kDagWave0Max = 64;                                // wave 0 holds 
 // the row's first task publishes first[i] + 1 and every wait is for rowfin >= k + 1 with k >= k0.  PRE(j) and SUB(j) are
 // always emitted (the sub-diagonal tile is inside every envelope), so the chain is unchanged; the order -- column-major with the
 // deep tasks drawn early, "Enveloped" below -- stays topological.
-void dag_task_order(const std::vector<int>& nb_of, int wave_arg, DagOrder& out, const int* first = nullptr) {
+// Far stretch (far != nullptr, with first: far[i] = first block column of block row i that is NOT far, first[i] <= far[i] <= i,
+// oisat_factor_far).  A bulk task's first word carries kfar = far[i] clamped into [k0, kend] next to k0: kind | k0 << 8 |
+// kfar << 18, ten bits each (kDagEnvMaxBlocks block rows); its K-blocks k0 .. kfar - 1 run on the bf16 pipe (dag_tile_task).
+// All three bulk kinds; the chain's own panel product and rank-128 update stay fp32.  The dense list and far == nullptr emit
+// kfar = k0: an empty stretch.
+constexpr int kDagEnvMaxBlocks = 1024;
+void dag_task_order(const std::vector<int>& nb_of, int wave_arg, DagOrder& out, const int* first = nullptr, const int* far = nullptr) {
     const int nsys = (int)nb_of.size();
     // Ticket order.  Systems are taken in WAVES.  The BIG systems -- those with at least half the block rows of the largest
     // (a month's polar caps; at most 64) -- go two at a time, the others (table order, largest first) eight at a time.  A
@@ -1081,6 +1170,9 @@ void dag_task_order(const std::vector<int>& nb_of, int wave_arg, DagOrder& out, 
     }
     std::vector<int4>& tasks = out.tasks;
     tasks.clear();
+    bool any_far = false;
+    for (int i = 0; first && far && i < nb_of[0]; ++i) any_far = any_far || far[i] > first[i];
+    const double env_lead = any_far ? kDagEnvLeadFar : kDagEnvLead;
     int chain_rows = 0;                                         // (.z of a chain task: first row of its stamps in the trace)
     int max_wave_chains = 0, second = 0;
     struct Item { double key; int4 task; };
@@ -1111,15 +1203,26 @@ void dag_task_order(const std::vector<int>& nb_of, int wave_arg, DagOrder& out, 
                 // computing: lead 0.05 / 0.1 / 0.15 / 0.2 / 0.25 / 0.3 = 128.8 / 116.2 / 111.0 / 110.7 / 111.3 / 111.3 ms per step (0.15 .. 0.3
                 // within the spread between calls); 0.15 is kept, the smallest of the flat stretch -- at the 2^-52 band (override
                 // only) it costs 0.4 % (181.1 -> 181.9 ms).
-                auto ekey = [&](int i, int jj) { return ((double)jj - kDagEnvLead * (double)(jj - first[i])) / (double)nb; };
+                // With a far stretch (kFactorFarBits = 18: 35 % of the headline's K-blocks at a third of their fp32 time) the tasks are
+                // shorter and a column passes faster: lead 0.1 / 0.15 / 0.2 / 0.25 / 0.3 = 91.8 / 85.2, 85.1 / 84.4 / 84.6 / 84.4 ms per step;
+                // 0.2 is kept there, the smallest of the flat stretch again.  Without a stretch the list is the one above, ticket for ticket.
+                auto ekey = [&](int i, int jj) { return ((double)jj - env_lead * (double)(jj - first[i])) / (double)nb; };
                 // PRE(j) reads row j up to column j - 2 only (the chain adds column j - 1 itself), so it is drawn ONE COLUMN EARLY,
                 // in front of column j - 1's tasks: drawn with column j it was what a small system's chain waited for at every
                 // step (58 us of a 141-us step; the tile tasks of column j then polled for T_j: 37 -> 16 us per task).  The
                 // wait moves to SUB(j), which cannot start its last block before column j - 1 is out; a month: 48.9 -> 48.5 ms.
-                if (j >= 2) items.push_back(Item{(first ? ekey(j, j - 1) : (double)(j - 1) / (double)nb) - 1e-9, int4{DAG_PRE | (first ? first[j] << 8 : 0), s, j, j}});
-                if (j >= 1 && j + 1 < nb) items.push_back(Item{first ? ekey(j + 1, j) : key, int4{DAG_SUB | (first ? first[j + 1] << 8 : 0), s, j + 1, j}});
+                auto word = [&](int kind, int i, int kend) {      // kind | k0 << 8 | kfar << 18
+                    if (!first) return kind;
+                    const int k0 = first[i];
+                    int kfar = far ? far[i] : k0;
+                    kfar = kfar < k0 ? k0 : kfar;
+                    kfar = kfar > kend ? (kend > k0 ? kend : k0) : kfar;
+                    return kind | k0 << 8 | kfar << 18;
+                };
+                if (j >= 2) items.push_back(Item{(first ? ekey(j, j - 1) : (double)(j - 1) / (double)nb) - 1e-9, int4{word(DAG_PRE, j, j - 1), s, j, j}});
+                if (j >= 1 && j + 1 < nb) items.push_back(Item{first ? ekey(j + 1, j) : key, int4{word(DAG_SUB, j + 1, j), s, j + 1, j}});
                 for (int i = j + 2; i < nb && (!first || first[i] <= j); ++i)
-                    items.push_back(Item{first ? ekey(i, j) : key, int4{DAG_TILE | (first ? first[i] << 8 : 0), s, i, j}});
+                    items.push_back(Item{first ? ekey(i, j) : key, int4{word(DAG_TILE, i, j), s, i, j}});
             }
         }
         std::stable_sort(items.begin(), items.end(), [](const Item& a, const Item& b) { return a.key < b.key; });
@@ -1166,7 +1269,7 @@ static inline int dag_slots(const oisat_ctx* h) { return 2 * (h->cu_count > 0 ? 
 // uninitialised words (wrong tickets, flags that read "ready").
 // first (single system only): its envelope; the ticket buffer is then sized for the dense list of these block rows
 DagPlan* dag_plan_create(const std::vector<BatchMat>& table, hipStream_t stream, const DagSolveShape& shape = DagSolveShape(),
-                         const int* first = nullptr) {
+                         const int* first = nullptr, const int* far = nullptr) {
     DagPlan* p = new DagPlan();
     const int nsys = (int)table.size();
     p->nsys = nsys;
@@ -1183,8 +1286,11 @@ DagPlan* dag_plan_create(const std::vector<BatchMat>& table, hipStream_t stream,
     {
         std::vector<int> nb_of(nsys);
         for (int s = 0; s < nsys; ++s) nb_of[s] = table[s].mpb;
-        dag_task_order(nb_of, 0, order, nsys == 1 ? first : nullptr);
-        if (first && nsys == 1) p->first.assign(first, first + nb_of[0]);
+        dag_task_order(nb_of, 0, order, nsys == 1 ? first : nullptr, nsys == 1 && first ? far : nullptr);
+        if (first && nsys == 1) {
+            p->first.assign(first, first + nb_of[0]);
+            p->far.assign(far ? far : first, (far ? far : first) + nb_of[0]);
+        }
         if (shape.refine >= 0) {
             int64_t rows = 0, valu = 0;
             dag_queue_entries(nb_of, shape, &rows, &valu);
@@ -1229,10 +1335,10 @@ DagPlan* dag_plan_create(const std::vector<BatchMat>& table, hipStream_t stream,
 
 // A cached enveloped plan meets another envelope (same matrix, same block rows): new ticket list into the SAME buffers.  The
 // copy is enqueued on `stream`, behind the launches that still read the old list.
-int dag_plan_refill(DagPlan& p, const int* first, hipStream_t stream) {
+int dag_plan_refill(DagPlan& p, const int* first, const int* far, hipStream_t stream) {
     const int nb = p.sys_host[0].nb;
     DagOrder order;
-    dag_task_order(std::vector<int>{nb}, 0, order, first);
+    dag_task_order(std::vector<int>{nb}, 0, order, first, far);
     if (order.tasks.size() > p.tasks_cap) {
         oisat_set_error("task-graph factorization: %zu tickets do not fit the plan's %zu", order.tasks.size(), p.tasks_cap);
         return OISAT_EINVAL;
@@ -1241,6 +1347,7 @@ int dag_plan_refill(DagPlan& p, const int* first, hipStream_t stream) {
     p.tasks_host = order.tasks;
     p.ntasks = (int)order.tasks.size();
     p.first.assign(first, first + nb);
+    p.far.assign(far ? far : first, (far ? far : first) + nb);
     p.max_wave_chains = order.max_wave_chains;
     p.chain_rows = order.chain_rows;
     p.reserve_chains = order.reserve_chains;

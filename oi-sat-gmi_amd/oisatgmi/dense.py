@@ -135,7 +135,7 @@ class DenseAnalysis:
             self.perm.shared_with_other_streams()
         # the block envelope of the latitude-sorted system (``oisat_factor_envelope``): first | last, 2 x mp_max / 128 words
         self.env = c.alloc(2 * (self.mp_max // NB) * 4)
-        self._env_host, self._env_g = None, None
+        self._env_host, self._env_g, self._far_host = None, None, None
         # What this plan knows about its S between runs (``oisat_cov_build_env_zeroed``): after a build and an enveloped
         # task-graph factorization with table T nothing outside T has been written, so every lower tile left of T is still the
         # exact zero of the fill.  Kept only by a plan that owns its S (a shared or batched buffer is written by others), as
@@ -191,13 +191,17 @@ class DenseAnalysis:
 
     def _envelope(self, g):
         """Host table ``first`` of this plan's observations at decay constant ``g`` (the library's rule and the fp32 factor's
-        cut-off: ``oisat_factor_envelope``); its device copy ``first | last`` is in ``self.env``.  Made once per (observations, L)."""
+        cut-off: ``oisat_factor_envelope``); its device copy ``first | last`` is in ``self.env``.  With it the far stretch of the
+        factor's K-loops (``oisat_factor_far``: the block columns of every row that run on the bf16 pipe), host only, in
+        ``self._far_host``.  Both made once per (observations, L)."""
         if self._env_host is None or self._env_g != g:
             nb = self.mp // NB
             env = np.empty(2 * nb, dtype=np.int32)
+            far = np.empty(nb, dtype=np.int32)
             self.ctx.check(self.ctx.lib.oisat_factor_envelope(self._lat_sorted.ctypes.data, self.m, g, env.ctypes.data))
+            self.ctx.check(self.ctx.lib.oisat_factor_far(self._lat_sorted.ctypes.data, self.m, g, env.ctypes.data, far.ctypes.data))
             self.ctx.upload_into(self.env.ptr, env)
-            self._env_host, self._env_g = env, g
+            self._env_host, self._env_g, self._far_host = env, g, far
         return self._env_host
 
     def _unsort(self, per_obs):
@@ -246,6 +250,7 @@ class DenseAnalysis:
                                                self.env.ptr, claim[1].ctypes.data if claim else None,
                                                self._zero_dev.ptr if claim else None, C.byref(enveloped)))
         info = C.c_int(0)
+        c.check(lib.oisat_set_factor_far(h, self._far_host.ctypes.data, self._far_host.size))        # per run: handles are shared
         c.check(lib.oisat_potrf_env_fwd(h, self.S.ptr, m, ld, first.ctypes.data, self.env.ptr, self.d.ptr,
                                         C.byref(info) if check_pd else None, C.byref(schedule)))
         self.last_schedule = schedule.value                    # (SCHEDULE_*: which factorization ran, for tests and profiles)
