@@ -408,6 +408,33 @@ int oisat_factor_envelope(const double* lat_sorted, int64_t m, double g, int32_t
  * oisat_potrf_env_fwd on this handle, which consumes it whatever its outcome and checks it against its own first.  Without
  * it, and in every other factorization (oisat_potrf, the batched ones), there is no far stretch. */
 int oisat_factor_far(const double* lat_sorted, int64_t m, double g, const int32_t* first, int32_t* far_out);
+
+/* ---- the correlation model ----------------------------------------------------------------------------------------
+ * OISAT_CORR_GAUSSIAN (default): C = exp(-g chord^2).  OISAT_CORR_GASPARI_COHN: the compactly supported fifth-order function
+ * of Gaspari and Cohn (1999, eq. 4.10) matched to the same g (half-support c = L sqrt(10/3): z = chord sqrt(0.6 g)),
+ *   0 <= z <= 1:  C = -z^5/4 + z^4/2 + 5 z^3/8 - 5 z^2/3 + 1
+ *   1 <  z <  2:  C = z^5/12 - z^4/2 + 5 z^3/8 + 5 z^2/3 - 5 z + 4 - 2/(3 z)
+ *   z >= 2:       C = 0 exactly
+ * It takes no parameter besides g.  Its latitude windows, envelopes and culls end at the support chord 2 / sqrt(0.6 g) and
+ * leave out exact zeros only.
+ * oisat_set_correlation: the model of every later oisat_cov_build*, oisat_cov_residual, oisat_gain_solve,
+ * oisat_apply_increment*, oisat_posterior_error and oisat_batch_solve on this handle (set it per run where handles are
+ * shared, like oisat_set_refine_tol).  oisat_batch_analyse is Gaussian only: OISAT_EINVAL under any other model.
+ * oisat_corr_eval (host only): out[i] = C at squared chord d2[i], float64, by the function the float64 kernels use.
+ * oisat_corr_cut_chord (host only): the chord at which C has fallen to 2^-bits (bits >= 1) -- Gaussian sqrt(bits / (g log2 e));
+ * Gaspari-Cohn by bisection, never beyond the support chord, and the support chord itself from 52 bits on.
+ * oisat_envelope_corr / oisat_factor_envelope_corr / oisat_factor_far_corr: the three tables above for a model; kind =
+ * OISAT_CORR_GAUSSIAN gives the tables of the functions above word for word.  Under Gaspari-Cohn the factor's envelope is the
+ * support envelope (= oisat_envelope_corr) and far_out == first unless OISAT_FACTOR_CUT_BITS / OISAT_FACTOR_FAR_BITS force a
+ * cut-off: the Gaussian's defaults were measured for the Gaussian.  An unknown kind is OISAT_EINVAL. */
+#define OISAT_CORR_GAUSSIAN 0
+#define OISAT_CORR_GASPARI_COHN 1
+int oisat_set_correlation(oisat_ctx* h, int kind);
+int oisat_corr_eval(int kind, double g, const double* d2, int64_t n, double* out);
+int oisat_corr_cut_chord(int kind, double g, double bits, double* chord_out);
+int oisat_envelope_corr(int kind, const double* lat_sorted, int64_t m, double g, int32_t* env_out);
+int oisat_factor_envelope_corr(int kind, const double* lat_sorted, int64_t m, double g, int32_t* env_out);
+int oisat_factor_far_corr(int kind, const double* lat_sorted, int64_t m, double g, const int32_t* first, int32_t* far_out);
 int oisat_set_factor_far(oisat_ctx* h, const int32_t* far, int64_t nb);
 int oisat_cov_build_env(oisat_ctx* h, const double* oxyz, const double* osig, const double* ovar, int64_t m,
                         double g, float* S, int64_t ld, const int32_t* env_dev);
@@ -466,7 +493,7 @@ int oisat_potrs(oisat_ctx* h, const float* L, int64_t m, int64_t ld, double* z_i
 /* r = d - (C.*sig sig^T + diag(var)) z  evaluated in double on the fly (iterative refinement).
  * olat_sorted (may be NULL): dev double[m], latitudes of the observations in degrees, valid only if the
  * observations are stored in ASCENDING latitude order; pairs whose latitudes differ by more than the angle at
- * which exp(-g chord^2) < 2^-64 are then skipped (one contiguous column range per block of rows). */
+ * which the correlation is below 2^-52 are then skipped (one contiguous column range per block of rows). */
 int oisat_cov_residual(oisat_ctx* h, const double* oxyz, const double* osig, const double* ovar, int64_t m,
                        double g, const double* d, const double* z, double* r_out, const double* olat_sorted);
 
@@ -491,9 +518,9 @@ int oisat_apply_increment(oisat_ctx* h, int dtype, const double* gxyz, const dou
 
 /* The same for cells that form a regular ny x nx grid (row-major, cell = y * nx + x): the kernel then takes compact 32-wide
  * PATCHES of cells per workgroup instead of runs of consecutive cells, gives each patch a bounding sphere and skips the
- * observations of the latitude window that lie beyond the covariance's reach (2^-64) of that sphere -- on a 0.25 deg grid at
+ * observations of the latitude window that lie beyond the covariance's reach (2^-52) of that sphere -- on a 0.25 deg grid at
  * L = 300 km most of what the latitude window keeps: a polar cap's cells no longer visit the observations on the other
- * side of the pole.  Same sums over the same observations in the same order (terms below 2^-64 of a term left out). */
+ * side of the pole.  Same sums over the same observations in the same order (terms below 2^-52 of a term left out). */
 int oisat_apply_increment_grid(oisat_ctx* h, int dtype, const double* gxyz, const double* gsig, int64_t ny, int64_t nx,
                                const double* oxyz, const double* osig, const double* z, int64_t m, double g,
                                const void* xb, void* xa, void* inc, const double* glat, const double* olat_sorted);
@@ -502,7 +529,7 @@ int oisat_apply_increment_grid(oisat_ctx* h, int dtype, const double* gxyz, cons
  * they are stored in) along a space-filling curve, so that 64 consecutive entries are neighbours in space.  The float64
  * residual of the gain solves that follow on this handle for systems of exactly m observations (oisat_gain_solve,
  * oisat_cov_residual) then takes its blocks of 64 rows from this list: a block has a small bounding sphere, and of the
- * latitude window's observations only those within the covariance's reach (2^-64) of it are visited -- the residual's rows
+ * latitude window's observations only those within the covariance's reach (2^-52) of it are visited -- the residual's rows
  * are otherwise 64 consecutive LATITUDES, all around the globe.  Same terms per row in the same order.  NULL / m = 0 clears.
  * ONE-SHOT: the next oisat_gain_solve / oisat_cov_residual call on the handle takes the list (if its m matches) and the handle
  * forgets it, whatever that call returns -- perm must stay valid until that call's work has run, and is never read after. */

@@ -1562,8 +1562,11 @@ __global__ __launch_bounds__(1024) void resid_check_kernel(const double* __restr
     }
 }
 
+#include "dense_solve_dev.inc"                                  // (the correlation functions; the solve-phase bodies of dense_dag.inc)
+
 // ---- posterior diagnostics: rows of X <- X L^-T, then row norms -----------------------------------
 // rows [i0, i0+nrows) of (H B)^T: X[r][a] = sig_{i0+r} * osig_a * C(i0+r, a), zero in the padding columns
+template <int KIND>
 __global__ __launch_bounds__(256) void cross_cov_rows_kernel(const double* __restrict__ gxyz, const double* __restrict__ gsig,
                                                               int64_t n, int64_t i0, int64_t nrows, const double* __restrict__ oxyz,
                                                               const double* __restrict__ osig, int64_t m, int64_t mp, float g2,
@@ -1595,7 +1598,7 @@ __global__ __launch_bounds__(256) void cross_cov_rows_kernel(const double* __res
         for (int c = 0; c < 4; ++c) {
             const float4 q = pc[cx + c];
             const float dx = a.x - q.x, dy = a.y - q.y, dz = a.z - q.z;
-            o[c] = (c0 + cx + c < m) ? a.w * q.w * __builtin_amdgcn_exp2f(-g2 * (dx * dx + dy * dy + dz * dz)) : 0.f;
+            o[c] = (c0 + cx + c < m) ? a.w * q.w * corr_f32<KIND>(g2, dx * dx + dy * dy + dz * dz) : 0.f;
         }
         *reinterpret_cast<float4*>(&X[(r0 + r) * ldx + c0 + cx]) = make_float4(o[0], o[1], o[2], o[3]);
     }
@@ -2185,7 +2188,6 @@ hipError_t dense_kernel_attributes() {
     return attr_rc;
 }
 
-#include "dense_solve_dev.inc"
 #include "dense_dag.inc"
 
 // Which factorizations run as a task graph: every system / batch of at least three block rows (below that there is nothing to
@@ -2424,9 +2426,9 @@ constexpr double kFactorMinKstepsPerRow = 1500.0;
 
 // first | last for the pairs whose correlation can reach 2^-bits (lat_sorted checked by the caller): their latitudes differ
 // by at most the angle of that cut-off's chord, great-circle distance >= latitude difference
-static void envelope_table(const double* lat_sorted, int64_t m, double g, double bits, int32_t* env_out) {
+static void envelope_table(int kind, const double* lat_sorted, int64_t m, double g, double bits, int32_t* env_out) {
     const int64_t nb = cdiv(m, NB);
-    const double angle = g > 0.0 ? lat_window_deg(g * (double)kLog2e, bits) : 1e9;
+    const double angle = g > 0.0 ? lat_window_deg(kind, g, bits) : 1e9;
     int64_t k = 0;
     for (int64_t i = 0; i < nb; ++i) {
         const double lo = lat_sorted[i * NB] - angle;           // tile k is outside when lat_max(tile k) < lat_min(tile i) - angle
@@ -2447,15 +2449,25 @@ static int64_t envelope_ksteps(const int32_t* first, int64_t nb) {
     return k;
 }
 
-extern "C" int oisat_envelope(const double* lat_sorted, int64_t m, double g, int32_t* env_out) {
-    ARG_CHECK(lat_sorted && env_out && m > 0 && g >= 0.0);
+static bool corr_kind_ok(int kind) { return kind == OISAT_CORR_GAUSSIAN || kind == OISAT_CORR_GASPARI_COHN; }
+
+extern "C" int oisat_envelope_corr(int kind, const double* lat_sorted, int64_t m, double g, int32_t* env_out) {
+    ARG_CHECK(corr_kind_ok(kind) && lat_sorted && env_out && m > 0 && g >= 0.0);
     for (int64_t i = 1; i < m; ++i) ARG_CHECK(lat_sorted[i] >= lat_sorted[i - 1]);
-    envelope_table(lat_sorted, m, g, kCutBits, env_out);       // the same cut-off as the float64 residual and the increment
+    envelope_table(kind, lat_sorted, m, g, kCutBits, env_out);  // the same cut-off as the float64 residual and the increment
     return OISAT_OK;
 }
 
-extern "C" int oisat_factor_envelope(const double* lat_sorted, int64_t m, double g, int32_t* env_out) {
-    ARG_CHECK(lat_sorted && env_out && m > 0 && g >= 0.0);
+extern "C" int oisat_envelope(const double* lat_sorted, int64_t m, double g, int32_t* env_out) {
+    return oisat_envelope_corr(OISAT_CORR_GAUSSIAN, lat_sorted, m, g, env_out);
+}
+
+// kFactorCutBits, kFactorMinKstepsPerRow and kFactorFarBits below were measured for the Gaussian only.  Gaspari-Cohn reaches
+// 2^-28 and 2^-18 at 99.5 % and 97 % of its support radius, so there is no narrower table worth having: its factor's envelope
+// IS the support envelope (oisat_envelope_corr's, which drops exact zeros only), with no chain-bound fallback to decide, and
+// its far table is empty (far = first).  The two environment variables still force their rules, through cut_chord.
+extern "C" int oisat_factor_envelope_corr(int kind, const double* lat_sorted, int64_t m, double g, int32_t* env_out) {
+    ARG_CHECK(corr_kind_ok(kind) && lat_sorted && env_out && m > 0 && g >= 0.0);
     for (int64_t i = 1; i < m; ++i) ARG_CHECK(lat_sorted[i] >= lat_sorted[i - 1]);
     double bits = kFactorCutBits;
     bool forced = false;
@@ -2467,10 +2479,15 @@ extern "C" int oisat_factor_envelope(const double* lat_sorted, int64_t m, double
         forced = true;
     }
     const int64_t nb = cdiv(m, NB);
-    envelope_table(lat_sorted, m, g, bits, env_out);
-    if (!forced && (double)envelope_ksteps(env_out, nb) <= kFactorMinKstepsPerRow * (double)nb)
-        envelope_table(lat_sorted, m, g, kCutBits, env_out);   // chain-bound: nothing to win, keep the float64 sums' table
+    if (kind == OISAT_CORR_GASPARI_COHN && !forced) bits = kCutBits;
+    envelope_table(kind, lat_sorted, m, g, bits, env_out);
+    if (kind == OISAT_CORR_GAUSSIAN && !forced && (double)envelope_ksteps(env_out, nb) <= kFactorMinKstepsPerRow * (double)nb)
+        envelope_table(kind, lat_sorted, m, g, kCutBits, env_out);     // chain-bound: nothing to win, keep the float64 sums' table
     return OISAT_OK;
+}
+
+extern "C" int oisat_factor_envelope(const double* lat_sorted, int64_t m, double g, int32_t* env_out) {
+    return oisat_factor_envelope_corr(OISAT_CORR_GAUSSIAN, lat_sorted, m, g, env_out);
 }
 
 // The far stretch of the factor's K-loops.  Left of the 2^-kFactorCutBits table every entry of S is dropped; just inside it, in
@@ -2488,8 +2505,8 @@ extern "C" int oisat_factor_envelope(const double* lat_sorted, int64_t m, double
 // potrf_dag 84.0 -> 67.2 ms, the step 100.6 -> 83.8 ms.
 constexpr double kFactorFarBits = 18.0;
 
-extern "C" int oisat_factor_far(const double* lat_sorted, int64_t m, double g, const int32_t* first, int32_t* far_out) {
-    ARG_CHECK(lat_sorted && first && far_out && m > 0 && g >= 0.0);
+extern "C" int oisat_factor_far_corr(int kind, const double* lat_sorted, int64_t m, double g, const int32_t* first, int32_t* far_out) {
+    ARG_CHECK(corr_kind_ok(kind) && lat_sorted && first && far_out && m > 0 && g >= 0.0);
     for (int64_t i = 1; i < m; ++i) ARG_CHECK(lat_sorted[i] >= lat_sorted[i - 1]);
     const int64_t nb = cdiv(m, NB);
     ARG_CHECK(envelope_table_ok(first, nb));
@@ -2504,20 +2521,24 @@ extern "C" int oisat_factor_far(const double* lat_sorted, int64_t m, double g, c
         ARG_CHECK(on || bits == 0.0);
     } else {
         const char* c = getenv("OISAT_FACTOR_CUT_BITS");
-        if (!(c && *c)) {                                       // the default rule's own choice: the narrow table, or not
+        if (!(c && *c) && kind == OISAT_CORR_GAUSSIAN) {        // the default rule's own choice: the narrow table, or not
             std::vector<int32_t> narrow(2 * (size_t)nb);
-            envelope_table(lat_sorted, m, g, kFactorCutBits, narrow.data());
+            envelope_table(kind, lat_sorted, m, g, kFactorCutBits, narrow.data());
             on = (double)envelope_ksteps(narrow.data(), nb) > kFactorMinKstepsPerRow * (double)nb;
         }
     }
     if (on && !oisat_envelope_off()) {
         std::vector<int32_t> t(2 * (size_t)nb);
-        envelope_table(lat_sorted, m, g, bits, t.data());
+        envelope_table(kind, lat_sorted, m, g, bits, t.data());
         for (int64_t i = 0; i < nb; ++i) far_out[i] = std::min<int32_t>(std::max(t[i], first[i]), (int32_t)i);
     } else {
         for (int64_t i = 0; i < nb; ++i) far_out[i] = first[i];
     }
     return OISAT_OK;
+}
+
+extern "C" int oisat_factor_far(const double* lat_sorted, int64_t m, double g, const int32_t* first, int32_t* far_out) {
+    return oisat_factor_far_corr(OISAT_CORR_GAUSSIAN, lat_sorted, m, g, first, far_out);
 }
 
 extern "C" int oisat_set_factor_far(oisat_ctx* h, const int32_t* far, int64_t nb) {
@@ -2673,12 +2694,17 @@ extern "C" int oisat_posterior_error(oisat_ctx* h, const float* L, int64_t m, in
     float* X = (float*)oisat_ws(h, 6, sizeof(float) * chunk_rows * mp + sizeof(double) * chunk_rows);
     if (!X) return OISAT_ENOMEM;
     double* ss = (double*)(X + chunk_rows * mp);
-    const float g2 = (float)(g * 1.4426950408889634);
+    const float g2 = h->corr == OISAT_CORR_GASPARI_COHN ? (float)(kGcZ2PerG * g) : (float)(g * 1.4426950408889634);      // g2 | kz2
     for (int64_t c0 = i0; c0 < i1; c0 += chunk_rows) {
         const int64_t live = (i1 - c0 < chunk_rows) ? i1 - c0 : chunk_rows;
         const int64_t nrows = cdiv(live, NB) * NB;                 // rows live..nrows are zero rows
-        OISAT_LAUNCH(h, "cross_cov_rows", cross_cov_rows_kernel, dim3((unsigned)(mp / 64), (unsigned)(nrows / 64)), dim3(256), 0,
-                     gxyz, gsig, n, c0, live, oxyz, osig, m, mp, g2, X, mp);
+        if (h->corr == OISAT_CORR_GASPARI_COHN) {
+            OISAT_LAUNCH(h, "cross_cov_rows", cross_cov_rows_kernel<OISAT_CORR_GASPARI_COHN>, dim3((unsigned)(mp / 64), (unsigned)(nrows / 64)),
+                         dim3(256), 0, gxyz, gsig, n, c0, live, oxyz, osig, m, mp, g2, X, mp);
+        } else {
+            OISAT_LAUNCH(h, "cross_cov_rows", cross_cov_rows_kernel<OISAT_CORR_GAUSSIAN>, dim3((unsigned)(mp / 64), (unsigned)(nrows / 64)),
+                         dim3(256), 0, gxyz, gsig, n, c0, live, oxyz, osig, m, mp, g2, X, mp);
+        }
         if (nrows > live) HIP_TRY(hipMemsetAsync(X + live * mp, 0, sizeof(float) * (nrows - live) * mp, h->stream));
         const int rc = trsm_rows_rec(h, h->factor, X, nrows, mp, 0, mp / NB);
         if (rc) return rc;
@@ -2995,6 +3021,10 @@ extern "C" int oisat_batch_analyse(oisat_ctx* h, int batch_id, int dtype, double
     ChBatch& bt = *h->batches[batch_id];
     ARG_CHECK(bt.solve_dev != nullptr && bt.ord_total > 0 && refine >= 0 && refine <= DAG_MAX_REFINE && g >= 0.0);
     ARG_CHECK(dtype == OISAT_F32 || dtype == OISAT_F64);
+    if (h->corr != OISAT_CORR_GAUSSIAN) {
+        oisat_set_error("oisat_batch_analyse: the one-launch analysis is Gaussian only (oisat_set_correlation); use oisat_batch_potrf + oisat_batch_solve");
+        return OISAT_EINVAL;
+    }
     if (!bt.dag) {
         oisat_set_error("oisat_batch_analyse: this batch's factorization does not run as a task graph (oisat_set_task_graph / size)");
         return OISAT_EINVAL;
@@ -3009,13 +3039,13 @@ extern "C" int oisat_batch_analyse(oisat_ctx* h, int batch_id, int dtype, double
     sv.mem = bt.solve_dev;
     sv.g = g;
     sv.g2 = g2;
-    sv.win_deg = lat_window_deg(g2);
-    sv.cut_chord = cut_chord_of(g2);
+    sv.win_deg = lat_window_deg(OISAT_CORR_GAUSSIAN, g);
+    sv.cut_chord = cut_chord_of(OISAT_CORR_GAUSSIAN, g);
     sv.tol2 = h->refine_tol * h->refine_tol;
     sv.refine = refine;
     sv.dtype = dtype;
     sv.cells = increment_cells(h->cu_count, bt.max_n, nmem);
-    sv.blocks = residual_blocks_pay(g2) ? 1 : 0;
+    sv.blocks = residual_blocks_pay(OISAT_CORR_GAUSSIAN, g) ? 1 : 0;
     for (const SolveMember& sm : bt.solve_host) sv.blocks = sv.blocks && sm.perm != nullptr;
     sv.trsv_timeouts = (unsigned*)base;
     sv.nsys = nmem;

@@ -1,6 +1,7 @@
-// Dense Gaussian background-error covariance pieces of the north-star analysis
+// Dense background-error covariance pieces of the north-star analysis
 //     x_a = x_b + B H^T (H B H^T + R)^-1 (y - H x_b),   B = D^1/2 C D^1/2,
-//     C(p,q) = exp(-g |p-q|^2),  g = R_earth^2 / (2 L^2),  p,q unit vectors on the sphere.
+//     C(p,q) = exp(-g |p-q|^2),  g = R_earth^2 / (2 L^2),  p,q unit vectors on the sphere (the default model), or the
+//     compactly supported Gaspari-Cohn function of the same g (oisat_set_correlation; dense_solve_dev.inc: corr_f32 / corr_f64).
 // The reference has no counterpart (its OI is the L->0, H=I limit: optimal_interpolation.py:27,
 // :49-50).  Chord distance keeps C positive definite on the sphere; |p-q|^2 is formed from
 // coordinate DIFFERENCES (not 2-2p.q) so that fp32 keeps ~1e-7 relative accuracy at small range.
@@ -14,6 +15,8 @@
 
 namespace {
 
+#include "dense_solve_dev.inc"
+
 // ---- S = sig sig^T .* C + diag(var), lower 64x64 tiles (diagonal tiles complete) ----------------
 // ENV: first[mp/128] (device) is the block envelope of a latitude-sorted system (oisat_envelope).  A tile left of its row's
 // envelope holds correlations below the library's cut-off only: it is not evaluated but filled with exact zeros, so that every
@@ -21,7 +24,7 @@ namespace {
 // BAND (oisat_cov_build_env_zeroed): the grid is tile rows x the widest row's tiles instead of the whole triangle.  Row ti
 // starts at the 128-column block from = min(first, zero_first) of its block row (zero_first = nullptr: 0): tiles in
 // [from, first) are zero-filled, tiles from first on evaluated, and the caller vouches for the zeros left of `from`.
-template <bool ENV, bool BAND>
+template <int KIND, bool ENV, bool BAND>
 __global__ __launch_bounds__(256) void cov_build_kernel(const double* __restrict__ oxyz, const double* __restrict__ osig,
                                                          const double* __restrict__ ovar, int64_t m, int64_t mp, float g2,
                                                          float* __restrict__ S, int64_t ld, int ntile, const int* __restrict__ first,
@@ -79,7 +82,7 @@ __global__ __launch_bounds__(256) void cov_build_kernel(const double* __restrict
             const int64_t gcol = (int64_t)tj * 64 + cx + c;
             const float dx = a.x - q.x, dy = a.y - q.y, dz = a.z - q.z;
             const float d2 = dx * dx + dy * dy + dz * dz;
-            float v = a.w * q.w * __builtin_amdgcn_exp2f(-g2 * d2);
+            float v = a.w * q.w * corr_f32<KIND>(g2, d2);
             if (grow == gcol) v = grow < m ? (float)(osig[grow] * osig[grow] + ovar[grow]) : 1.0f;     // padding: identity
             else if (grow >= m || gcol >= m) v = 0.0f;
             o[c] = v;
@@ -95,15 +98,13 @@ __global__ __launch_bounds__(256) void innovation_kernel(const T* __restrict__ x
     for (int64_t a = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; a < m; a += stride) d[a] = y[a] - (double)xb[cell[a]];
 }
 
-#include "dense_solve_dev.inc"
-
 // LDS of the solve-phase kernels below: one carve-out per workgroup (dense_solve_dev.inc)
 #define SOLVE_LDS(W)                                                                    \
     __shared__ __attribute__((aligned(16))) char solve_lds_raw[kSolveLdsBytes];         \
     const SolveLds W = solve_lds_carve(solve_lds_raw)
 
 // ---- r = d - S z in double (dense_solve_dev.inc: resid_rows_block); blockIdx.x = block of 64 rows ---------------------
-template <bool BATCH>
+template <int KIND, bool BATCH>
 __global__ __launch_bounds__(256) void cov_residual_kernel(const double* __restrict__ oxyz, const double* __restrict__ osig,
                                                             const double* __restrict__ ovar, int64_t m, double g,
                                                             const double* __restrict__ d, const double* __restrict__ z,
@@ -127,7 +128,7 @@ __global__ __launch_bounds__(256) void cov_residual_kernel(const double* __restr
     }
     SOLVE_LDS(W);
     if (converged != nullptr && *converged != 0) return;       // the refinement has met its tolerance: nothing left to evaluate
-    resid_rows_block<false>(oxyz, osig, ovar, m, g, d, z, r, olat, win_deg, BATCH ? (double*)nullptr : partial, nsplit, (int)blockIdx.y,
+    resid_rows_block<KIND, false>(oxyz, osig, ovar, m, g, d, z, r, olat, win_deg, BATCH ? (double*)nullptr : partial, nsplit, (int)blockIdx.y,
                             (int64_t)blockIdx.x, W);
 }
 
@@ -145,7 +146,7 @@ __global__ __launch_bounds__(256) void resid_combine_kernel(const double* __rest
 }
 
 // ---- the same residual on COMPACT blocks of rows (dense_solve_dev.inc: resid_compact_block) ------------------------------
-template <bool BATCH>
+template <int KIND, bool BATCH>
 __global__ __launch_bounds__(256) void cov_residual_blocks_kernel(const double* __restrict__ oxyz, const double* __restrict__ osig,
                                                                    const double* __restrict__ ovar, int64_t m, double g,
                                                                    const double* __restrict__ d, const double* __restrict__ z,
@@ -168,11 +169,11 @@ __global__ __launch_bounds__(256) void cov_residual_blocks_kernel(const double* 
     }
     SOLVE_LDS(W);
     if (converged != nullptr && *converged != 0) return;       // the refinement has met its tolerance: nothing left to evaluate
-    resid_compact_block<false>(oxyz, osig, ovar, m, g, d, z, r, olat, win_deg, perm, cut_chord, (int64_t)blockIdx.x, W);
+    resid_compact_block<KIND, false>(oxyz, osig, ovar, m, g, d, z, r, olat, win_deg, perm, cut_chord, (int64_t)blockIdx.x, W);
 }
 
 // ---- inc_i = sig_i * sum_a C(i,a) w_a ; xa = xb + inc (dense_solve_dev.inc: increment_patch); blockIdx.x = patch / run ----
-template <typename T, int CELLS, bool BATCH>
+template <int KIND, typename T, int CELLS, bool BATCH>
 __global__ __launch_bounds__(256) void apply_increment_kernel(const double* __restrict__ gxyz, const double* __restrict__ gsig,
                                                                int64_t n, const double* __restrict__ oxyz,
                                                                const double* __restrict__ osig, const double* __restrict__ z,
@@ -197,10 +198,44 @@ __global__ __launch_bounds__(256) void apply_increment_kernel(const double* __re
         if (glat != nullptr) { glat = mb->glat; olat = mb->olat; }      // (non-null = "use the latitude window")
     }
     SOLVE_LDS(W);
-    increment_patch<T, CELLS>(gxyz, gsig, n, oxyz, osig, z, m, g2, xb, xa, inc, glat, olat, win_deg, nx, cut_chord, (int64_t)blockIdx.x, W);
+    increment_patch<KIND, T, CELLS>(gxyz, gsig, n, oxyz, osig, z, m, g2, xb, xa, inc, glat, olat, win_deg, nx, cut_chord, (int64_t)blockIdx.x, W);
 }
 
+// launch KERNEL<KIND, ...> for the handle's correlation model (h->corr, oisat_set_correlation): one instantiation per model,
+// no test of the model inside a kernel
+#define OISAT_LAUNCH_CORR(h, NAME, KERNEL, TARGS, grid, block, shmem, ...)                                         \
+    do {                                                                                                           \
+        if ((h)->corr == OISAT_CORR_GASPARI_COHN) {                                                                \
+            OISAT_LAUNCH(h, NAME, (KERNEL<OISAT_CORR_GASPARI_COHN, TARGS>), grid, block, shmem, __VA_ARGS__);      \
+        } else {                                                                                                   \
+            OISAT_LAUNCH(h, NAME, (KERNEL<OISAT_CORR_GAUSSIAN, TARGS>), grid, block, shmem, __VA_ARGS__);          \
+        }                                                                                                          \
+    } while (0)
+#define OISAT_TARGS(...) __VA_ARGS__
+
 }  // namespace
+
+extern "C" int oisat_set_correlation(oisat_ctx* h, int kind) {
+    ARG_CHECK(h != nullptr && (kind == OISAT_CORR_GAUSSIAN || kind == OISAT_CORR_GASPARI_COHN));
+    h->corr = kind;
+    return OISAT_OK;
+}
+
+extern "C" int oisat_corr_eval(int kind, double g, const double* d2, int64_t n, double* out) {
+    ARG_CHECK((kind == OISAT_CORR_GAUSSIAN || kind == OISAT_CORR_GASPARI_COHN) && g >= 0.0 && n >= 0 && ((d2 && out) || n == 0));
+    const double a = corr_scale(kind, g);
+    if (kind == OISAT_CORR_GASPARI_COHN)
+        for (int64_t i = 0; i < n; ++i) out[i] = corr_f64<OISAT_CORR_GASPARI_COHN>(a, d2[i]);
+    else
+        for (int64_t i = 0; i < n; ++i) out[i] = corr_f64<OISAT_CORR_GAUSSIAN>(a, d2[i]);
+    return OISAT_OK;
+}
+
+extern "C" int oisat_corr_cut_chord(int kind, double g, double bits, double* chord_out) {
+    ARG_CHECK((kind == OISAT_CORR_GAUSSIAN || kind == OISAT_CORR_GASPARI_COHN) && g > 0.0 && bits >= 1.0 && chord_out);
+    *chord_out = cut_chord(kind, g, bits);
+    return OISAT_OK;
+}
 
 extern "C" int oisat_cov_build(oisat_ctx* h, const double* oxyz, const double* osig, const double* ovar, int64_t m, double g,
                                float* S, int64_t ld) {
@@ -210,8 +245,8 @@ extern "C" int oisat_cov_build(oisat_ctx* h, const double* oxyz, const double* o
     const int ntile = (int)(mp / 64);
     const int64_t nblk = (int64_t)ntile * (ntile + 1) / 2;
     ARG_CHECK(nblk < (int64_t)INT32_MAX);
-    OISAT_LAUNCH(h, "cov_build", (cov_build_kernel<false, false>), dim3((unsigned)nblk), dim3(256), 0, oxyz, osig, ovar, m, mp,
-                 (float)(g * (double)kLog2e), S, ld, ntile, (const int*)nullptr, (const int*)nullptr);
+    OISAT_LAUNCH_CORR(h, "cov_build", cov_build_kernel, OISAT_TARGS(false, false), dim3((unsigned)nblk), dim3(256), 0, oxyz, osig, ovar, m, mp,
+                      (float)corr_scale2(h->corr, g), S, ld, ntile, (const int*)nullptr, (const int*)nullptr);
     return OISAT_OK;
 }
 
@@ -225,8 +260,8 @@ extern "C" int oisat_cov_build_env(oisat_ctx* h, const double* oxyz, const doubl
     const int ntile = (int)(mp / 64);
     const int64_t nblk = (int64_t)ntile * (ntile + 1) / 2;
     ARG_CHECK(nblk < (int64_t)INT32_MAX);
-    OISAT_LAUNCH(h, "cov_build", (cov_build_kernel<true, false>), dim3((unsigned)nblk), dim3(256), 0, oxyz, osig, ovar, m, mp,
-                 (float)(g * (double)kLog2e), S, ld, ntile, (const int*)env_dev, (const int*)nullptr);
+    OISAT_LAUNCH_CORR(h, "cov_build", cov_build_kernel, OISAT_TARGS(true, false), dim3((unsigned)nblk), dim3(256), 0, oxyz, osig, ovar, m, mp,
+                      (float)corr_scale2(h->corr, g), S, ld, ntile, (const int*)env_dev, (const int*)nullptr);
     return OISAT_OK;
 }
 
@@ -268,8 +303,8 @@ extern "C" int oisat_cov_build_env_zeroed(oisat_ctx* h, const double* oxyz, cons
         if (enveloped_out) *enveloped_out = 1;
         return OISAT_OK;
     }
-    OISAT_LAUNCH(h, "cov_build", (cov_build_kernel<true, true>), dim3((unsigned)width, (unsigned)ntile), dim3(256), 0, oxyz, osig, ovar, m,
-                 mp, (float)(g * (double)kLog2e), S, ld, ntile, (const int*)env_dev, (const int*)zero_first_dev);
+    OISAT_LAUNCH_CORR(h, "cov_build", cov_build_kernel, OISAT_TARGS(true, true), dim3((unsigned)width, (unsigned)ntile), dim3(256), 0, oxyz, osig,
+                      ovar, m, mp, (float)corr_scale2(h->corr, g), S, ld, ntile, (const int*)env_dev, (const int*)zero_first_dev);
     if (enveloped_out) *enveloped_out = 1;
     return OISAT_OK;
 }
@@ -302,11 +337,12 @@ int oisat_cov_residual_if(oisat_ctx* h, const double* oxyz, const double* osig, 
                           const double* d, const double* z, double* r_out, const double* olat_sorted, const int* converged_dev,
                           const int* perm) {
     ARG_CHECK(h && oxyz && osig && ovar && d && z && r_out && m > 0);
-    const double g2 = g * (double)kLog2e;
-    const double win = lat_window_deg(g2);
-    if (perm && olat_sorted && residual_blocks_pay(g2)) {
-        OISAT_LAUNCH(h, "cov_residual", cov_residual_blocks_kernel<false>, dim3((unsigned)cdiv(m, 64)), dim3(256), 0, oxyz, osig, ovar, m, g,
-                     d, z, r_out, olat_sorted, win, converged_dev, (const SolveMember*)nullptr, perm, cut_chord_of(g2));
+    const int kind = h->corr;
+    const double win = lat_window_deg(kind, g);
+    const double gk = corr_scale(kind, g);                  // what the kernels take: g | kz2
+    if (perm && olat_sorted && residual_blocks_pay(kind, g)) {
+        OISAT_LAUNCH_CORR(h, "cov_residual", cov_residual_blocks_kernel, false, dim3((unsigned)cdiv(m, 64)), dim3(256), 0, oxyz, osig, ovar, m,
+                          gk, d, z, r_out, olat_sorted, win, converged_dev, (const SolveMember*)nullptr, perm, cut_chord_of(kind, g));
         return OISAT_OK;
     }
     // fewer than two blocks of 64 rows per CU (m < 32,768 on 256 CUs): the column range is cut into slices, a workgroup per
@@ -321,9 +357,9 @@ int oisat_cov_residual_if(oisat_ctx* h, const double* oxyz, const double* osig, 
         if (!w) return OISAT_ENOMEM;
         partial = w + 2 * mp;
     }
-    OISAT_LAUNCH(h, "cov_residual", cov_residual_kernel<false>, dim3((unsigned)blocks, (unsigned)nsplit), dim3(256), 0, oxyz, osig, ovar, m,
-                 g, d, z, r_out, win < 180.0 ? olat_sorted : (const double*)nullptr, win, converged_dev, (const SolveMember*)nullptr,
-                 partial, nsplit);
+    OISAT_LAUNCH_CORR(h, "cov_residual", cov_residual_kernel, false, dim3((unsigned)blocks, (unsigned)nsplit), dim3(256), 0, oxyz, osig, ovar, m,
+                      gk, d, z, r_out, win < 180.0 ? olat_sorted : (const double*)nullptr, win, converged_dev, (const SolveMember*)nullptr,
+                      partial, nsplit);
     if (nsplit > 1) {
         OISAT_LAUNCH(h, "cov_residual", resid_combine_kernel, dim3((unsigned)cdiv(m, 256)), dim3(256), 0, (const double*)partial, nsplit, m,
                      osig, ovar, d, z, r_out, converged_dev);
@@ -346,10 +382,10 @@ extern "C" int oisat_cov_residual(oisat_ctx* h, const double* oxyz, const double
 
 template <typename T, int CELLS, bool BATCH>
 static int increment_launch(oisat_ctx* h, unsigned gx, unsigned gy, const double* gxyz, const double* gsig, int64_t n, int nx, const double* oxyz,
-                            const double* osig, const double* z, int64_t m, double g2, const void* xb, void* xa, void* inc,
+                            const double* osig, const double* z, int64_t m, double g, const void* xb, void* xa, void* inc,
                             const double* glat, const double* olat, double win, const SolveMember* mem) {
-    OISAT_LAUNCH(h, "apply_increment", (apply_increment_kernel<T, CELLS, BATCH>), dim3(gx, gy), dim3(256), 0, gxyz, gsig, n, oxyz, osig, z,
-                 m, g2, (const T*)xb, (T*)xa, (T*)inc, glat, olat, win, mem, nx, cut_chord_of(g2));
+    OISAT_LAUNCH_CORR(h, "apply_increment", apply_increment_kernel, OISAT_TARGS(T, CELLS, BATCH), dim3(gx, gy), dim3(256), 0, gxyz, gsig, n, oxyz,
+                      osig, z, m, corr_scale2(h->corr, g), (const T*)xb, (T*)xa, (T*)inc, glat, olat, win, mem, nx, cut_chord_of(h->corr, g));
     return OISAT_OK;
 }
 
@@ -361,18 +397,17 @@ static int apply_increment_impl(oisat_ctx* h, int dtype, const double* gxyz, con
     ARG_CHECK(!xa || xb);
     ARG_CHECK(dtype == OISAT_F32 || dtype == OISAT_F64);
     ARG_CHECK(nx >= 0 && nx < (int64_t)INT32_MAX && (nx == 0 || n % nx == 0));
-    const double g2 = g * (double)kLog2e;
-    const double win = lat_window_deg(g2);
+    const double win = lat_window_deg(h->corr, g);
     if (!(win < 180.0) || !glat || !olat_sorted) { glat = nullptr; olat_sorted = nullptr; }
     const int cells = increment_cells(h->cu_count, n, 1);
     const int64_t gx = increment_blocks(n, nx, cells);
     ARG_CHECK(gx < (int64_t)INT32_MAX);
     const unsigned ux = (unsigned)gx;
     if (dtype == OISAT_F32)
-        return cells == 1 ? increment_launch<float, 1, false>(h, ux, 1, gxyz, gsig, n, (int)nx, oxyz, osig, z, m, g2, xb, xa, inc, glat, olat_sorted, win, nullptr)
-                          : increment_launch<float, 2, false>(h, ux, 1, gxyz, gsig, n, (int)nx, oxyz, osig, z, m, g2, xb, xa, inc, glat, olat_sorted, win, nullptr);
-    return cells == 1 ? increment_launch<double, 1, false>(h, ux, 1, gxyz, gsig, n, (int)nx, oxyz, osig, z, m, g2, xb, xa, inc, glat, olat_sorted, win, nullptr)
-                      : increment_launch<double, 2, false>(h, ux, 1, gxyz, gsig, n, (int)nx, oxyz, osig, z, m, g2, xb, xa, inc, glat, olat_sorted, win, nullptr);
+        return cells == 1 ? increment_launch<float, 1, false>(h, ux, 1, gxyz, gsig, n, (int)nx, oxyz, osig, z, m, g, xb, xa, inc, glat, olat_sorted, win, nullptr)
+                          : increment_launch<float, 2, false>(h, ux, 1, gxyz, gsig, n, (int)nx, oxyz, osig, z, m, g, xb, xa, inc, glat, olat_sorted, win, nullptr);
+    return cells == 1 ? increment_launch<double, 1, false>(h, ux, 1, gxyz, gsig, n, (int)nx, oxyz, osig, z, m, g, xb, xa, inc, glat, olat_sorted, win, nullptr)
+                      : increment_launch<double, 2, false>(h, ux, 1, gxyz, gsig, n, (int)nx, oxyz, osig, z, m, g, xb, xa, inc, glat, olat_sorted, win, nullptr);
 }
 
 extern "C" int oisat_apply_increment(oisat_ctx* h, int dtype, const double* gxyz, const double* gsig, int64_t n,
@@ -390,21 +425,22 @@ extern "C" int oisat_apply_increment_grid(oisat_ctx* h, int dtype, const double*
 
 // ---- batched forms (oisat_batch_solve, dense_chol.hip): blockIdx.y = member of the device table --------------------------
 int oisat_cov_residual_batched(oisat_ctx* h, const SolveMember* mem_dev, const std::vector<SolveMember>& mem_host, int64_t max_m, double g) {
-    const double g2 = g * (double)kLog2e;
-    const double win = lat_window_deg(g2);
+    const int kind = h->corr;
+    const double win = lat_window_deg(kind, g);
+    const double gk = corr_scale(kind, g);
     const int nmem = (int)mem_host.size();
-    bool blocks = residual_blocks_pay(g2);
+    bool blocks = residual_blocks_pay(kind, g);
     for (const SolveMember& sm : mem_host) blocks = blocks && sm.perm != nullptr;
     if (blocks) {
-        OISAT_LAUNCH(h, "cov_residual", cov_residual_blocks_kernel<true>, dim3((unsigned)cdiv(max_m, 64), (unsigned)nmem), dim3(256), 0,
-                     (const double*)nullptr, (const double*)nullptr, (const double*)nullptr, (int64_t)0, g, (const double*)nullptr,
-                     (const double*)nullptr, (double*)nullptr, (const double*)nullptr, win, (const int*)nullptr, mem_dev, (const int*)nullptr,
-                     cut_chord_of(g2));
+        OISAT_LAUNCH_CORR(h, "cov_residual", cov_residual_blocks_kernel, true, dim3((unsigned)cdiv(max_m, 64), (unsigned)nmem), dim3(256), 0,
+                          (const double*)nullptr, (const double*)nullptr, (const double*)nullptr, (int64_t)0, gk, (const double*)nullptr,
+                          (const double*)nullptr, (double*)nullptr, (const double*)nullptr, win, (const int*)nullptr, mem_dev, (const int*)nullptr,
+                          cut_chord_of(kind, g));
         return OISAT_OK;
     }
     static const double dummy = 0.0;                        // non-null marker: "use each member's latitude window"
-    OISAT_LAUNCH(h, "cov_residual", cov_residual_kernel<true>, dim3((unsigned)cdiv(max_m, 64), (unsigned)nmem), dim3(256), 0,
-                 (const double*)nullptr, (const double*)nullptr, (const double*)nullptr, (int64_t)0, g, (const double*)nullptr,
+    OISAT_LAUNCH_CORR(h, "cov_residual", cov_residual_kernel, true, dim3((unsigned)cdiv(max_m, 64), (unsigned)nmem), dim3(256), 0,
+                 (const double*)nullptr, (const double*)nullptr, (const double*)nullptr, (int64_t)0, gk, (const double*)nullptr,
                  (const double*)nullptr, (double*)nullptr, win < 180.0 ? &dummy : (const double*)nullptr, win, (const int*)nullptr,
                  mem_dev, (double*)nullptr, 1);
     return OISAT_OK;
@@ -412,8 +448,7 @@ int oisat_cov_residual_batched(oisat_ctx* h, const SolveMember* mem_dev, const s
 
 int oisat_apply_increment_batched(oisat_ctx* h, int dtype, const SolveMember* mem_dev, const std::vector<SolveMember>& mem_host, int64_t max_n,
                                   double g) {
-    const double g2 = g * (double)kLog2e;
-    const double win = lat_window_deg(g2);
+    const double win = lat_window_deg(h->corr, g);
     static const double dummy = 0.0;
     const double* use = win < 180.0 ? &dummy : (const double*)nullptr;
     const int nmem = (int)mem_host.size();
@@ -423,8 +458,8 @@ int oisat_apply_increment_batched(oisat_ctx* h, int dtype, const SolveMember* me
     ARG_CHECK(gx > 0 && gx < (int64_t)INT32_MAX);
     const unsigned ux = (unsigned)gx, gy = (unsigned)nmem;
     if (dtype == OISAT_F32)
-        return cells == 1 ? increment_launch<float, 1, true>(h, ux, gy, nullptr, nullptr, max_n, 0, nullptr, nullptr, nullptr, 0, g2, nullptr, nullptr, nullptr, use, use, win, mem_dev)
-                          : increment_launch<float, 2, true>(h, ux, gy, nullptr, nullptr, max_n, 0, nullptr, nullptr, nullptr, 0, g2, nullptr, nullptr, nullptr, use, use, win, mem_dev);
-    return cells == 1 ? increment_launch<double, 1, true>(h, ux, gy, nullptr, nullptr, max_n, 0, nullptr, nullptr, nullptr, 0, g2, nullptr, nullptr, nullptr, use, use, win, mem_dev)
-                      : increment_launch<double, 2, true>(h, ux, gy, nullptr, nullptr, max_n, 0, nullptr, nullptr, nullptr, 0, g2, nullptr, nullptr, nullptr, use, use, win, mem_dev);
+        return cells == 1 ? increment_launch<float, 1, true>(h, ux, gy, nullptr, nullptr, max_n, 0, nullptr, nullptr, nullptr, 0, g, nullptr, nullptr, nullptr, use, use, win, mem_dev)
+                          : increment_launch<float, 2, true>(h, ux, gy, nullptr, nullptr, max_n, 0, nullptr, nullptr, nullptr, 0, g, nullptr, nullptr, nullptr, use, use, win, mem_dev);
+    return cells == 1 ? increment_launch<double, 1, true>(h, ux, gy, nullptr, nullptr, max_n, 0, nullptr, nullptr, nullptr, 0, g, nullptr, nullptr, nullptr, use, use, win, mem_dev)
+                      : increment_launch<double, 2, true>(h, ux, gy, nullptr, nullptr, max_n, 0, nullptr, nullptr, nullptr, 0, g, nullptr, nullptr, nullptr, use, use, win, mem_dev);
 }

@@ -748,9 +748,9 @@ __device__ __forceinline__ bool dag_res_task(const DagSys& sy, const SolveMember
     __builtin_amdgcn_s_setprio(1);                              // VALU work beside a tile task's MFMA wave: first at the issue port (the MFMA wave
     const SolveLds W = solve_lds_carve(lds);                    // issues one instruction per 64 cycles of its pipe and loses nothing)
     if (sv.blocks)
-        resid_compact_block<true>(mb.oxyz, mb.osig, mb.ovar, mb.m, sv.g, mb.d, mb.z, mb.rhs, mb.olat, sv.win_deg, mb.perm, sv.cut_chord, (int64_t)c, W);
+        resid_compact_block<OISAT_CORR_GAUSSIAN, true>(mb.oxyz, mb.osig, mb.ovar, mb.m, sv.g, mb.d, mb.z, mb.rhs, mb.olat, sv.win_deg, mb.perm, sv.cut_chord, (int64_t)c, W);
     else
-        resid_rows_block<true>(mb.oxyz, mb.osig, mb.ovar, mb.m, sv.g, mb.d, mb.z, mb.rhs, sv.win_deg < 180.0 ? mb.olat : (const double*)nullptr,
+        resid_rows_block<OISAT_CORR_GAUSSIAN, true>(mb.oxyz, mb.osig, mb.ovar, mb.m, sv.g, mb.d, mb.z, mb.rhs, sv.win_deg < 180.0 ? mb.olat : (const double*)nullptr,
                                sv.win_deg, (double*)nullptr, 1, 0, (int64_t)c, W);
     __builtin_amdgcn_s_setprio(0);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -830,10 +830,10 @@ __device__ __forceinline__ bool dag_inc_task(const DagSys& sy, const SolveMember
     const double* glat = windowed ? mb.glat : (const double*)nullptr;
     const double* olat = windowed ? mb.olat : (const double*)nullptr;
     if (sv.cells == 1)
-        increment_patch<T, 1>(mb.gxyz, mb.gsig, mb.n, mb.oxyz, mb.osig, mb.z, mb.m, sv.g2, (const T*)mb.xb, (T*)mb.xa, (T*)mb.inc, glat, olat,
+        increment_patch<OISAT_CORR_GAUSSIAN, T, 1>(mb.gxyz, mb.gsig, mb.n, mb.oxyz, mb.osig, mb.z, mb.m, sv.g2, (const T*)mb.xb, (T*)mb.xa, (T*)mb.inc, glat, olat,
                               sv.win_deg, mb.nx, sv.cut_chord, (int64_t)blk, W);
     else
-        increment_patch<T, 2>(mb.gxyz, mb.gsig, mb.n, mb.oxyz, mb.osig, mb.z, mb.m, sv.g2, (const T*)mb.xb, (T*)mb.xa, (T*)mb.inc, glat, olat,
+        increment_patch<OISAT_CORR_GAUSSIAN, T, 2>(mb.gxyz, mb.gsig, mb.n, mb.oxyz, mb.osig, mb.z, mb.m, sv.g2, (const T*)mb.xb, (T*)mb.xa, (T*)mb.inc, glat, olat,
                               sv.win_deg, mb.nx, sv.cut_chord, (int64_t)blk, W);
     __builtin_amdgcn_s_setprio(0);
     __syncthreads();

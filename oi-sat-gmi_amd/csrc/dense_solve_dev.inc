@@ -10,13 +10,89 @@ constexpr float kLog2e = 1.4426950408889634f;
 // is dropped stays below 1e-12 of the result (rounds 1-3 used 2^-64: 19 % more pairs for nothing measurable).
 constexpr double kCutBits = 52.0;
 
+// ---- the correlation model ------------------------------------------------------------------------------------------
+// KIND = OISAT_CORR_GAUSSIAN (0): C = exp(-g d^2), d = |p - q| the chord.  KIND = OISAT_CORR_GASPARI_COHN (1): the compactly
+// supported fifth-order piecewise rational of Gaspari and Cohn (1999, eq. 4.10) in z = d / c, half-support c = L sqrt(10/3)
+// (the Gaussian's curvature at d = 0), i.e. z^2 = 0.6 g d^2; exactly 0 from z = 2 on.  Positive definite in R^3, hence on the
+// sphere with chord distance (dense_cov.hip, head).  Every kernel that evaluates a correlation is a template on KIND and takes
+// ONE scale next to d^2: what its Gaussian form has always taken (g, or g2 = g log2 e where it uses exp2) or kz2 = 0.6 g.
+constexpr double kGcZ2PerG = 0.6;
+// what a kernel of model `kind` takes in the place of the Gaussian's g2 = g log2 e / of the Gaussian's g
+static inline double corr_scale2(int kind, double g) { return kind == OISAT_CORR_GASPARI_COHN ? kGcZ2PerG * g : g * (double)kLog2e; }
+static inline double corr_scale(int kind, double g) { return kind == OISAT_CORR_GASPARI_COHN ? kGcZ2PerG * g : g; }
+
+// Both branches in Horner form and a select: a wave's 64 pairs straddle all three ranges.  (z = 0: the far branch is -inf /
+// NaN and not selected.)  Rounding noise below 0 next to z = 2 is clamped.
+__device__ __forceinline__ float gc_f32(float kz2, float d2) {
+    const float z2 = kz2 * d2;
+    const float z = __builtin_amdgcn_sqrtf(z2);                             // one v_sqrt_f32 ...
+    const float rz = __builtin_amdgcn_rcpf(z);                              // ... and one v_rcp_f32 (the 2 / (3 z) term)
+    const float nearv = ((((-0.25f * z + 0.5f) * z + 0.625f) * z - 1.6666666666666667f) * z2) + 1.0f;
+    const float farv = (((((0.083333333333333333f * z - 0.5f) * z + 0.625f) * z + 1.6666666666666667f) * z - 5.0f) * z + 4.0f) - 0.66666666666666667f * rz;
+    const float c = z <= 1.0f ? nearv : farv;
+    return z < 2.0f ? fmaxf(c, 0.0f) : 0.0f;
+}
+__host__ __device__ inline double gc_f64(double kz2, double d2) {
+    const double z2 = kz2 * d2;
+    const double z = sqrt(z2);
+#if defined(__HIP_DEVICE_COMPILE__)
+    double rz = __builtin_amdgcn_rcp(z);                                    // v_rcp_f64 and two Newton steps: full precision,
+    rz = __builtin_fma(__builtin_fma(-z, rz, 1.0), rz, rz);                 // cheaper than the division's scale / fix-up
+    rz = __builtin_fma(__builtin_fma(-z, rz, 1.0), rz, rz);
+#else
+    const double rz = 1.0 / z;
+#endif
+    const double nearv = ((((-0.25 * z + 0.5) * z + 0.625) * z - 1.6666666666666667) * z2) + 1.0;
+    const double farv = (((((0.083333333333333333 * z - 0.5) * z + 0.625) * z + 1.6666666666666667) * z - 5.0) * z + 4.0) - 0.66666666666666667 * rz;
+    const double c = z <= 1.0 ? nearv : farv;
+    return z < 2.0 ? (c > 0.0 ? c : 0.0) : 0.0;
+}
+
+__device__ __forceinline__ double exp2_neg(double x);
+// fp32 (the build of S, the rows of H B): a = g2 | kz2
+template <int KIND>
+__device__ __forceinline__ float corr_f32(float a, float d2) {
+    if (KIND == OISAT_CORR_GASPARI_COHN) return gc_f32(a, d2);
+    return __builtin_amdgcn_exp2f(-a * d2);
+}
+// float64 (the residual): a = g | kz2
+template <int KIND>
+__host__ __device__ inline double corr_f64(double a, double d2) {
+    if (KIND == OISAT_CORR_GASPARI_COHN) return gc_f64(a, d2);
+    return exp(-a * d2);
+}
+// float64 (the increment): a = g2 | kz2
+template <int KIND>
+__device__ __forceinline__ double corr_f64_exp2(double a, double d2) {
+    if (KIND == OISAT_CORR_GASPARI_COHN) return gc_f64(a, d2);
+    return exp2_neg(-a * d2);
+}
+
+// ---- host: the chord at which the correlation has fallen to 2^-bits -------------------------------------------------------
+// Gaussian: sqrt(bits / g2).  Gaspari-Cohn: by bisection on z in [0, 2] (C falls monotonically there), the upper end of the
+// last bracket, never beyond the support chord 2 / sqrt(0.6 g); from kCutBits on it IS the support chord: the float64 sums
+// then leave out nothing.  Every window, envelope and cull of the library derives its chord here.
+static inline double cut_chord(int kind, double g, double bits) {
+    if (kind != OISAT_CORR_GASPARI_COHN) return sqrt(bits / (g * (double)kLog2e));
+    double hi = 2.0;
+    if (bits < kCutBits) {
+        const double target = exp2(-bits);
+        double lo = 0.0;
+        for (int it = 0; it < 64; ++it) {
+            const double mid = 0.5 * (lo + hi);
+            if (gc_f64(1.0, mid * mid) > target) lo = mid; else hi = mid;
+        }
+    }
+    return hi / sqrt(kGcZ2PerG * g);
+}
+
 // ---- latitude window ----------------------------------------------------------------------------------
-// exp2(-g2 d^2) < 2^-kCutBits once the chord d exceeds sqrt(kCutBits/g2): such a pair changes a double sum by less than its
-// last bit times the cancellation factor, and two points whose latitudes differ by more than the matching angle are
-// at least that far apart.  With the observations sorted by latitude the pairs worth evaluating for a block of rows /
-// cells are therefore one contiguous index range, found by two binary searches.  (3.6x fewer pairs at L = 300 km.)
-__host__ __device__ inline double lat_window_deg(double g2, double bits = kCutBits) {
-    const double chord = sqrt(bits / g2);
+// The correlation is below 2^-kCutBits once the chord d exceeds cut_chord(): such a pair changes a double sum by less than its
+// last bit times the cancellation factor (Gaspari-Cohn: by nothing), and two points whose latitudes differ by more than the
+// matching angle are at least that far apart.  With the observations sorted by latitude the pairs worth evaluating for a block
+// of rows / cells are therefore one contiguous index range, found by two binary searches.  (3.6x fewer pairs at L = 300 km.)
+static inline double lat_window_deg(int kind, double g, double bits = kCutBits) {
+    const double chord = cut_chord(kind, g, bits);
     return chord >= 2.0 ? 1e9 : 2.0 * asin(0.5 * chord) * 57.29577951308232;
 }
 
@@ -138,12 +214,17 @@ __device__ __forceinline__ double exp2_neg(double x) {
 
 // ---- host: which form of the residual / increment a solve takes (the same rule for the kernels of dense_cov.hip and for the
 // tasks of the task-graph launch, so that the two paths do the same arithmetic) ------------------------------------------------
-// chord beyond which 2^(-g2 chord^2) < 2^-kCutBits (the same cut-off as the latitude window's)
-static inline double cut_chord_of(double g2) { return sqrt(kCutBits / g2); }
+// chord beyond which the correlation is below 2^-kCutBits (the same cut-off as the latitude window's)
+static inline double cut_chord_of(int kind, double g) { return cut_chord(kind, g, kCutBits); }
 // The compact-block residual pays where the covariance's reach is small against the domain: measured at 720x1440 / 1e5
 // observations, L = 300 km (reach 2 800 km): 6.6 -> 4.6 ms; a month's 50 tiles: 1.69 -> 1.59 ms; at 360x720 / 1e4 observations,
 // L = 500 km (reach 4 700 km) the staging costs more than the cull saves: 0.21 -> 0.26 ms.
-static inline bool residual_blocks_pay(double g2) { return sqrt(64.0 / g2) <= 0.5; }       // chord on the unit sphere: 3 200 km (L <= 340 km)
+// (The rule is about the reach: the Gaussian's 2^-64 chord, as measured.  Gaspari-Cohn: the same 0.5 applied to its support
+// chord -- reasoned from the Gaussian's figures, not measured.)
+static inline bool residual_blocks_pay(int kind, double g) {
+    if (kind == OISAT_CORR_GASPARI_COHN) return cut_chord(kind, g, kCutBits) <= 0.5;
+    return sqrt(64.0 / (g * (double)kLog2e)) <= 0.5;           // chord on the unit sphere: 3 200 km (L <= 340 km)
+}
 // two cells per thread share every observation fetched from LDS; with too few cells to fill the GPU that way (a polar cap:
 // 338 workgroups) one cell per thread doubles the waves in flight instead
 static inline int increment_cells(int cu_count, int64_t n, int nmem) {
@@ -196,7 +277,7 @@ __device__ __forceinline__ void solve_store(double* p, double v) {
 // [olat[row0], olat[row_last]] and only columns inside that span +/- the window are visited.
 // partial != nullptr (single system with fewer than two blocks of rows per CU): `slice` = one of nsplit slices of the
 // column range; the slice's sums go to partial[slice][row] and resid_combine_kernel adds them in slice order
-template <bool AGENT>
+template <int KIND, bool AGENT>
 __device__ __forceinline__ void resid_rows_block(const double* __restrict__ oxyz, const double* __restrict__ osig,
                                                  const double* __restrict__ ovar, int64_t m, double g, const double* __restrict__ d,
                                                  const double* __restrict__ z, double* __restrict__ r, const double* __restrict__ olat,
@@ -238,7 +319,7 @@ __device__ __forceinline__ void resid_rows_block(const double* __restrict__ oxyz
         __syncthreads();
         for (int j = ph * 64; j < ph * 64 + 64; ++j) {
             const double dx = ax - sx[j], dy = ay - sy[j], dz = az - sz[j];
-            acc += exp(-g * (dx * dx + dy * dy + dz * dz)) * sw[j];
+            acc += corr_f64<KIND>(g, dx * dx + dy * dy + dz * dz) * sw[j];
         }
     }
     part[ph][lr] = acc;
@@ -258,7 +339,7 @@ __device__ __forceinline__ void resid_rows_block(const double* __restrict__ oxyz
 // sphere and keeps, while staging the candidates into LDS, only the observations within the covariance's reach of it -- the
 // increment's cull (block_sphere / stage_near).  Per row: the same terms in the same (latitude) order, four column phases
 // combined in a fixed order; terms below 2^-kCutBits of a term left out.
-template <bool AGENT>
+template <int KIND, bool AGENT>
 __device__ __forceinline__ void resid_compact_block(const double* __restrict__ oxyz, const double* __restrict__ osig,
                                                     const double* __restrict__ ovar, int64_t m, double g, const double* __restrict__ d,
                                                     const double* __restrict__ z, double* __restrict__ r, const double* __restrict__ olat,
@@ -292,7 +373,7 @@ __device__ __forceinline__ void resid_compact_block(const double* __restrict__ o
                 const double2 oxy = W.bxy[j];
                 const double2 ozw = W.bzw[j];
                 const double dx = ax - oxy.x, dy = ay - oxy.y, dz = az - ozw.x;
-                acc += exp(-g * (dx * dx + dy * dy + dz * dz)) * ozw.y;
+                acc += corr_f64<KIND>(g, dx * dx + dy * dy + dz * dz) * ozw.y;
             }
             fill = 0;
             __syncthreads();
@@ -317,7 +398,7 @@ __device__ __forceinline__ void resid_compact_block(const double* __restrict__ o
 // scale at swath densities, so fp32 partial sums alone cost ~1e-5.
 // Cells of block `blk`: a 32-wide patch of the (ny x nx) grid (nx > 0: CELLS * 8 rows x 32 columns -- a compact patch has a
 // small bounding sphere, 512 consecutive cells of a 1440-wide row span 128 degrees), or CELLS * 256 consecutive cells (nx <= 0).
-template <typename T, int CELLS>
+template <int KIND, typename T, int CELLS>
 __device__ __forceinline__ void increment_patch(const double* __restrict__ gxyz, const double* __restrict__ gsig, int64_t n,
                                                 const double* __restrict__ oxyz, const double* __restrict__ osig,
                                                 const double* __restrict__ z, int64_t m, double g2, const T* __restrict__ xb,
@@ -395,7 +476,7 @@ __device__ __forceinline__ void increment_patch(const double* __restrict__ gxyz,
                     // 1.3e-5 -- outside the 1e-5 bar -- at 360x720 / 1e4 gridded obs, L = 500 km; with this: 4e-8.  Twice the
                     // instructions per pair (taking only the pairs with C > 2^-8 in double diverges inside the waves and is
                     // slower still at L = 500 km); the bounding-sphere cull above pays for it.
-                    acc[q] += exp2_neg(-g2 * (dx * dx + dy * dy + dz * dz)) * ozw.y;
+                    acc[q] += corr_f64_exp2<KIND>(g2, dx * dx + dy * dy + dz * dz) * ozw.y;
                 }
             }
             fill = 0;

@@ -132,6 +132,7 @@ struct oisat_ctx {
     ChFactor factor;
     bool small_tiles = true;            // gemm_nt: 64x64 tiles for launches of <= 700 128x128 tiles (latency-bound ones)
     double refine_tol = 1e-6;           // oisat_set_refine_tol: relative residual at which the gain solve stops refining
+    int corr = 0;                       // oisat_set_correlation: the correlation model of every later call (OISAT_CORR_*)
     int wave_prio = 0;                  // oisat_set_share: s_setprio of this handle's batched factorization kernels (0..3)
     int gemm_wg_per_cu = 0;             // oisat_set_share: workgroups per CU of its persistent GEMM launches (0 = default, 2)
     hipStream_t own_stream = nullptr;   // created by oisat_stream_create, destroyed at shutdown

@@ -4,6 +4,9 @@
     B = s D^1/2 C D^1/2,  D = diag(Sa),  C_ij = exp(-chord_ij^2 R_earth^2 / (2 L^2)),  R = diag(So)
     H = selection of the grid cell that contains each observation
 
+``corr="gaspari_cohn"`` replaces the Gaussian C by the compactly supported function of Gaspari and Cohn (1999, eq. 4.10) of the
+same L (half-support c = L sqrt(10/3), exactly zero beyond 2 c = 3.65 L); ``corr="gaussian"`` is the default everywhere.
+
 The reference's ``OI`` (optimal_interpolation.py:6-52) is the L -> 0 limit of this with one
 observation per cell: there C = I and K_ii = s Sa_i / (s Sa_i + So_i) (:27).  There is NO
 reference implementation of the dense form, so its parity is pinned only in that limit; away from
@@ -56,6 +59,19 @@ def morton_order(lat_deg, lon_deg) -> np.ndarray:
     lo = np.clip((np.mod(np.asarray(lon_deg, dtype=np.float64) + 180.0, 360.0)) / 360.0 * 65535.0, 0, 65535)
     code = (spread(la.astype(np.uint32)) << np.uint32(1)) | spread(lo.astype(np.uint32))
     return np.argsort(code, kind="stable").astype(np.int32)
+
+
+# correlation models (include/oisat.h: OISAT_CORR_*)
+CORRELATIONS = {"gaussian": 0, "gaspari_cohn": 1}
+GC_SUPPORT_PER_L = 2.0 * (10.0 / 3.0) ** 0.5        # Gaspari-Cohn: C = 0 beyond 2 c = 3.6515 L
+
+
+def corr_kind(corr) -> int:
+    """``"gaussian"`` | ``"gaspari_cohn"`` -> the library's code; anything else is a ``ValueError`` (no device call made)."""
+    try:
+        return CORRELATIONS[corr]
+    except (KeyError, TypeError):
+        raise ValueError(f"corr must be one of {sorted(CORRELATIONS)}, not {corr!r}") from None
 
 
 def decay_constant(L_km: float) -> float:
@@ -135,7 +151,8 @@ class DenseAnalysis:
             self.perm.shared_with_other_streams()
         # the block envelope of the latitude-sorted system (``oisat_factor_envelope``): first | last, 2 x mp_max / 128 words
         self.env = c.alloc(2 * (self.mp_max // NB) * 4)
-        self._env_host, self._env_g, self._far_host = None, None, None
+        self._env_host, self._env_key, self._far_host = None, None, None
+        self._kind = 0                                         # the correlation model of the last run / run_build
         # What this plan knows about its S between runs (``oisat_cov_build_env_zeroed``): after a build and an enveloped
         # task-graph factorization with table T nothing outside T has been written, so every lower tile left of T is still the
         # exact zero of the fill.  Kept only by a plan that owns its S (a shared or batched buffer is written by others), as
@@ -174,13 +191,13 @@ class DenseAnalysis:
 
     def _sort_by_latitude(self, obs_lat, obs_lon):
         """Observations live on the device in ascending-latitude order: the pairs (cell, observation) and
-        (observation, observation) whose correlation is above 2^-64 are then contiguous index ranges, which is what the
+        (observation, observation) whose correlation is above 2^-52 are then contiguous index ranges, which is what the
         latitude windows of ``oisat_apply_increment`` / ``oisat_cov_residual`` skip by.  Per-observation results
         (``download_z``, ``gain_diag``) are handed back in the caller's order."""
         lat = np.ravel(np.asarray(obs_lat, dtype=np.float64))
         self._order = np.argsort(lat, kind="stable")
         self._lat_sorted = np.ascontiguousarray(lat[self._order])
-        self._env_host = None                                  # (belongs to these observations and one L: made by run())
+        self._env_host = None                                  # (belongs to these observations, one L and one model: made by run())
         self.ctx.upload_into(self.olat.ptr, self._lat_sorted, dtype=np.float64)
         # ... and the float64 residual takes its blocks of 64 rows along a space-filling curve through them (Morton order of
         # latitude x longitude, as a permutation of the latitude order): neighbours in space, a small bounding sphere
@@ -189,19 +206,20 @@ class DenseAnalysis:
         self.ctx.upload_into(self.perm.ptr, morton_order(lat[self._order], lon))
         return self._order
 
-    def _envelope(self, g):
-        """Host table ``first`` of this plan's observations at decay constant ``g`` (the library's rule and the fp32 factor's
-        cut-off: ``oisat_factor_envelope``); its device copy ``first | last`` is in ``self.env``.  With it the far stretch of the
-        factor's K-loops (``oisat_factor_far``: the block columns of every row that run on the bf16 pipe), host only, in
-        ``self._far_host``.  Both made once per (observations, L)."""
-        if self._env_host is None or self._env_g != g:
+    def _envelope(self, g, kind=0):
+        """Host table ``first`` of this plan's observations at decay constant ``g`` under correlation model ``kind`` (the
+        library's rule and the fp32 factor's cut-off: ``oisat_factor_envelope_corr``); its device copy ``first | last`` is in
+        ``self.env``.  With it the far stretch of the factor's K-loops (``oisat_factor_far_corr``: the block columns of every
+        row that run on the bf16 pipe), host only, in ``self._far_host``.  Both made once per (observations, L, model)."""
+        if self._env_host is None or self._env_key != (g, kind):
             nb = self.mp // NB
             env = np.empty(2 * nb, dtype=np.int32)
             far = np.empty(nb, dtype=np.int32)
-            self.ctx.check(self.ctx.lib.oisat_factor_envelope(self._lat_sorted.ctypes.data, self.m, g, env.ctypes.data))
-            self.ctx.check(self.ctx.lib.oisat_factor_far(self._lat_sorted.ctypes.data, self.m, g, env.ctypes.data, far.ctypes.data))
+            self.ctx.check(self.ctx.lib.oisat_factor_envelope_corr(kind, self._lat_sorted.ctypes.data, self.m, g, env.ctypes.data))
+            self.ctx.check(self.ctx.lib.oisat_factor_far_corr(kind, self._lat_sorted.ctypes.data, self.m, g, env.ctypes.data,
+                                                              far.ctypes.data))
             self.ctx.upload_into(self.env.ptr, env)
-            self._env_host, self._env_g, self._far_host = env, g, far
+            self._env_host, self._env_key, self._far_host = env, (g, kind), far
         return self._env_host
 
     def _unsort(self, per_obs):
@@ -226,11 +244,14 @@ class DenseAnalysis:
         c.upload_into(self.oy.ptr, np.ravel(obs_y)[o], dtype=np.float64)
 
     # ---- the hot path: everything below runs on the device, enqueued on the handle's stream
-    def run(self, L_km: float, refine: int = 2, check_pd: bool = False, want_resid: bool = False, tol=None):
+    def run(self, L_km: float, refine: int = 2, check_pd: bool = False, want_resid: bool = False, tol=None, corr="gaussian"):
         """``refine``: the most refinement rounds the gain solve may take; it stops earlier once the float64 residual is
-        below ``tol`` |d| (default: the handle's, 1e-6 -- ``oisat_set_refine_tol``; 0 runs every round)."""
+        below ``tol`` |d| (default: the handle's, 1e-6 -- ``oisat_set_refine_tol``; 0 runs every round).  ``corr``: the
+        correlation model, ``"gaussian"`` or ``"gaspari_cohn"`` (same L; module docstring)."""
+        kind = self._kind = corr_kind(corr)
         c, lib, h = self.ctx, self.ctx.lib, self.ctx.h
         c.check(lib.oisat_set_refine_tol(h, REFINE_TOL if tol is None else float(tol)))      # per run: handles are shared
+        c.check(lib.oisat_set_correlation(h, kind))                                          # ... and so is the model
         m, ld = self.m, self.mp
         g = self._g = decay_constant(L_km)
         item = self.dt.itemsize
@@ -239,7 +260,7 @@ class DenseAnalysis:
             c.check(lib.oisat_innovation(h, self.code, xb, self.ocell.ptr, self.oy.ptr, m, self.d.ptr))
         # this plan owns the latitude sort, so it may use the covariance's envelope: only the tiles inside it are evaluated
         # and factored, the sweeps of the gain solve walk inside it (OISAT_ENVELOPE=0: the dense path, in the library)
-        first = self._envelope(g)
+        first = self._envelope(g, kind)
         # the build fills with zeros only what the last run's envelope left outside this one's (equal tables: nothing), the
         # factorization launch carries the first forward sweep of the gain solve (OISAT_FWD_IN_LAUNCH=0: it does not)
         claim, self._zero_claim = self._zero_claim, None       # (an exception below leaves no claim behind)
@@ -270,8 +291,10 @@ class DenseAnalysis:
         return list(resid) if want_resid else None
 
     # ---- the same pipeline in two halves, for lock-step (batched) factorization of many plans: build | factor | solve
-    def run_build(self, L_km: float):
+    def run_build(self, L_km: float, corr="gaussian"):
+        kind = self._kind = corr_kind(corr)
         c, lib, h = self.ctx, self.ctx.lib, self.ctx.h
+        c.check(lib.oisat_set_correlation(h, kind))             # per run: handles are shared
         g = self._g = decay_constant(L_km)
         self._zero_claim = None                                 # (a dense build: S holds correlations everywhere)
         if not self._direct_innovation:
@@ -287,6 +310,7 @@ class DenseAnalysis:
         item = self.dt.itemsize
         xb, xa, inc = self.xb_ptr, self.out_ptr, self.out_ptr + self.n * item
         c.check(lib.oisat_set_refine_tol(h, REFINE_TOL if tol is None else float(tol)))
+        c.check(lib.oisat_set_correlation(h, self._kind))       # (the model of this plan's run_build)
         c.check(lib.oisat_factor_adopt(h, self.S.ptr, m, ld, self.tinv.ptr))
         c.check(lib.oisat_set_obs_blocks(h, self.perm.ptr, m))
         c.check(lib.oisat_gain_solve(h, self.S.ptr, self.oxyz.ptr, self.osig.ptr, self.ovar.ptr, m, ld, g, self.d.ptr,
@@ -301,6 +325,7 @@ class DenseAnalysis:
         if not hasattr(self, "_err"):
             self._err = c.alloc(self.n * 4)
         g = self._g
+        c.check(c.lib.oisat_set_correlation(c.h, self._kind))   # (the model of the run that left the factor)
         c.check(c.lib.oisat_posterior_error(c.h, self.S.ptr, self.m, self.mp, self.gxyz.ptr, self.gsig.ptr, self.n, 0, self.n,
                                             self.oxyz.ptr, self.osig.ptr, g, int(chunk_rows), self._err.ptr))
         return c.download(self._err.ptr, self.shape, np.float32)
@@ -478,7 +503,9 @@ class BatchedFactor:
             if sequential and gi > 0:
                 ctx.wait_for(self.ctxs[gi - 1])             # one parked queue
             info = (C.c_int * 2)(0, -1)
-            if self.one_launch:
+            kind = g[0]._kind                               # (every plan was built by the same run: one model)
+            ctx.check(ctx.lib.oisat_set_correlation(ctx.h, kind))
+            if self.one_launch and kind == 0:               # (the one-launch analysis is Gaussian only: the two calls otherwise)
                 # factorization, gain solves and increments of the whole group as tasks of ONE persistent launch: the solves of
                 # the systems factored first run underneath the factorization of the others (csrc/dense_dag.inc)
                 ctx.check(ctx.lib.oisat_set_refine_tol(ctx.h, REFINE_TOL))
@@ -771,25 +798,27 @@ class TiledAnalysis:
             per_lane[self._lane_of[ti]].append(lambda p=self.plans[ti]: fn(p))
         return per_lane
 
-    def enqueue(self, L_km, refine=2, check_pd=False):
+    def enqueue(self, L_km, refine=2, check_pd=False, corr="gaussian"):
+        corr_kind(corr)
         if not self._order:                              # not a single observation in any owned tile: x_a = x_b
             return
         if not self.batched:
-            self.pool.enqueue(self._per_lane(lambda p: p.run(L_km, refine=refine, check_pd=check_pd)))
+            self.pool.enqueue(self._per_lane(lambda p: p.run(L_km, refine=refine, check_pd=check_pd, corr=corr)))
             return
         self.factor.fence(self.pool)
-        self.pool.enqueue(self._per_lane(lambda p: p.run_build(L_km)))         # innovation, S = H B H^T + R
+        self.pool.enqueue(self._per_lane(lambda p: p.run_build(L_km, corr=corr)))      # innovation, S = H B H^T + R
         plans = [[] for _ in self.lanes]
         for ti in self._order:
             plans[self._lane_of[ti]].append(self.plans[ti])
         self.factor.run(self.pool, plans, refine, check_pd=check_pd)            # lock-step factor | gain solve, increment
 
-    def run(self, L_km, refine=2, check_pd=False):
+    def run(self, L_km, refine=2, check_pd=False, corr="gaussian"):
         """Enqueue every tile on its lane's stream (largest first), wait for all lanes and check their solve status:
         a non-positive pivot or a triangular-solve time-out in ANY tile raises ``OisatError``."""
+        corr_kind(corr)
         self.ctx.sync()                                 # inputs uploaded on the default stream are complete
-        self._L, self._refine = float(L_km), int(refine)
-        self.enqueue(L_km, refine=refine, check_pd=check_pd)
+        self._L, self._refine, self._corr = float(L_km), int(refine), corr
+        self.enqueue(L_km, refine=refine, check_pd=check_pd, corr=corr)
         _check_all("tiled analysis", self.pool, self.factor)
 
     def close(self):
@@ -826,7 +855,7 @@ class TiledAnalysis:
             if self.batched:                             # every tile still holds its own factor: adopt, do not redo
                 p.ctx.check(p.ctx.lib.oisat_factor_adopt(p.ctx.h, p.S.ptr, p.m, p.mp, p.tinv.ptr))
             else:
-                p.run(self._L, refine=self._refine, check_pd=True)
+                p.run(self._L, refine=self._refine, check_pd=True, corr=self._corr)
             err[y0:y1, x0:x1] = p.posterior_error(chunk_rows)
             a = p.gain_diag(chunk_rows)
             inside = self._inside[ti]                    # halo observations belong to another tile's cells
@@ -882,7 +911,8 @@ class MonthTileBatch:
         self._run_order = [self.units[i][:2] for i in order]
         self.flops = sum(ta.flops for ta in self.months.values())
 
-    def run(self, L_km, refine=2, check_pd=False, wait=True):
+    def run(self, L_km, refine=2, check_pd=False, wait=True, corr="gaussian"):
+        corr_kind(corr)
         self.ctx.sync()
         def per_lane(fn):
             out = [[] for _ in self.pool.lanes]
@@ -894,14 +924,14 @@ class MonthTileBatch:
             pass
         elif self.batched:
             self.factor.fence(self.pool)
-            self.pool.enqueue(per_lane(lambda p: p.run_build(L_km)))
+            self.pool.enqueue(per_lane(lambda p: p.run_build(L_km, corr=corr)))
             plans = [[] for _ in self.pool.lanes]
             for key, ti in self._run_order:
                 ta = self.months[key]
                 plans[ta._lane_of[ti]].append(ta.plans[ti])
             self.factor.run(self.pool, plans, refine, check_pd=check_pd)
         else:
-            self.pool.enqueue(per_lane(lambda p: p.run(L_km, refine=refine, check_pd=check_pd)))
+            self.pool.enqueue(per_lane(lambda p: p.run(L_km, refine=refine, check_pd=check_pd, corr=corr)))
         if wait:
             self.check()
 
@@ -925,16 +955,18 @@ class MonthTileBatch:
         self.pool.close()
 
 
-def OI_dense(Xa, Y, Sa, So, lat, lon, L_km, scale=1.0, refine=2, obs=None, dtype=None, want_error=False, tol=None):
+def OI_dense(Xa, Y, Sa, So, lat, lon, L_km, scale=1.0, refine=2, obs=None, dtype=None, want_error=False, tol=None,
+             corr="gaussian"):
     """Dense-covariance analysis with the reference's gridded argument convention.
 
     ``Xa, Sa``: (ny, nx) background and its variance; ``Y, So``: (ny, nx) observations and their
     variance, NaN where unobserved (as ``oisatgmi.oi`` passes them, driver.py:110-111);
     ``lat, lon``: (ny, nx) cell centres; ``L_km``: correlation length.  ``obs`` (optional) replaces
-    ``Y, So`` by scattered observations: dict(lat, lon, y, var).
+    ``Y, So`` by scattered observations: dict(lat, lon, y, var).  ``corr``: ``"gaussian"`` (default) or ``"gaspari_cohn"``.
     Returns ``(Xb, increment, info)``; unlike the element-wise ``OI`` every cell is analysed
     (unobserved cells get the spread increment instead of NaN).
     """
+    corr_kind(corr)                                           # (ValueError before anything is touched)
     Xa = np.asarray(Xa)
     if obs is None:
         Y[Y < 0] = 0.0                                        # same clamp as optimal_interpolation.py:14
@@ -961,7 +993,7 @@ def OI_dense(Xa, Y, Sa, So, lat, lon, L_km, scale=1.0, refine=2, obs=None, dtype
     sa_f = np.where(np.isfinite(Sa), Sa, 0.0)
     plan.load_background(xa_f, sa_f, scale=scale)
     plan.load_obs(olat, olon, cell, oy, ovar)
-    resid = plan.run(L_km, refine=refine, check_pd=True, want_resid=True, tol=tol)
+    resid = plan.run(L_km, refine=refine, check_pd=True, want_resid=True, tol=tol, corr=corr)
     xb, inc = plan.download()
     extra = {}
     if want_error:                     # the other two members of OI's 4-tuple: averaging kernel and sqrt(Sb)
@@ -982,24 +1014,27 @@ def OI_dense(Xa, Y, Sa, So, lat, lon, L_km, scale=1.0, refine=2, obs=None, dtype
 
 
 def OI_tiled(Xa, Y, Sa, So, lat, lon, L_km, tile_deg=30.0, halo_km=None, scale=1.0, refine=2, dtype=None, want_error=False,
-             streams=12):
+             streams=12, corr="gaussian"):
     """Localised block-B analysis with the reference's gridded argument convention (see ``OI_dense``): the grid is cut
-    into ``tile_deg`` tiles, each analysed with the observations inside it or within ``halo_km`` (default 3 L).
+    into ``tile_deg`` tiles, each analysed with the observations inside it or within ``halo_km`` (default: 3 L for the
+    Gaussian; the support 2 c = 3.6515 L for ``corr="gaspari_cohn"``, where the halo is then a true boundary).
     Returns ``(Xb, increment, info)``; ``info`` carries ``ak`` / ``err`` when ``want_error``."""
+    kind = corr_kind(corr)                                    # (ValueError before anything is touched)
     Xa = np.asarray(Xa)
     Y[Y < 0] = 0.0                                            # same clamp as optimal_interpolation.py:14
     ok = np.isfinite(np.ravel(Y)) & np.isfinite(np.ravel(So)) & np.isfinite(np.ravel(Xa)) & np.isfinite(np.ravel(Sa))
     cell = np.flatnonzero(ok)
     dt = np.dtype(dtype) if dtype is not None else _hip.compute_dtype(Xa)
     if cell.size == 0:
-        return OI_dense(Xa, Y, Sa, So, lat, lon, L_km, scale=scale, dtype=dt, want_error=want_error)
+        return OI_dense(Xa, Y, Sa, So, lat, lon, L_km, scale=scale, dtype=dt, want_error=want_error, corr=corr)
     xa_f = np.where(np.isfinite(Xa), Xa, 0.0)
     sa_f = np.where(np.isfinite(Sa), Sa, 0.0)
-    ta = TiledAnalysis(lat, lon, tile_deg=tile_deg, halo_km=3.0 * float(L_km) if halo_km is None else halo_km, dtype=dt,
-                       streams=streams)
+    if halo_km is None:
+        halo_km = (GC_SUPPORT_PER_L if kind == CORRELATIONS["gaspari_cohn"] else 3.0) * float(L_km)
+    ta = TiledAnalysis(lat, lon, tile_deg=tile_deg, halo_km=halo_km, dtype=dt, streams=streams)
     try:
         ta.load(xa_f, sa_f, np.ravel(lat)[cell], np.ravel(lon)[cell], np.ravel(Y)[cell], np.ravel(So)[cell], scale=scale)
-        ta.run(L_km, refine=refine, check_pd=True)
+        ta.run(L_km, refine=refine, check_pd=True, corr=corr)
         xb, inc = ta.download()
         extra = {}
         if want_error:

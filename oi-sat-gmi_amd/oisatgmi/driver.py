@@ -85,7 +85,9 @@ class oisatgmi(object):
     # ---- analysis mode (extension; the signature of oi() is the reference's) -----------------------------
     #   mode        attribute `oi_mode`        | env OISAT_OI_MODE        diag (default) | dense | tiled
     #   L           attribute `corr_length_km` | env OISAT_CORR_LENGTH_KM km, default 300           (dense, tiled)
-    #   tile size   attribute `tile_deg`       | env OISAT_TILE_DEG       degrees, default 30       (tiled; halo = 3 L)
+    #   model       attribute `oi_correlation` | env OISAT_CORRELATION    gaussian (default) | gaspari_cohn  (dense, tiled)
+    #   tile size   attribute `tile_deg`       | env OISAT_TILE_DEG       degrees, default 30       (tiled; halo = 3 L,
+    #               gaspari_cohn: its support 3.65 L)
     #   unobserved  attribute `oi_unobserved`  | env OISAT_UNOBSERVED     nan (default) | xa        (dense, tiled)
     #   grid        attributes `grid_lat`, `grid_lon` (ny, nx), else the first granule's latitude_center/longitude_center
     #   knee        attribute `oi_reg_index`: force the index into the 99-scaling sweep (all modes)
@@ -126,6 +128,9 @@ class oisatgmi(object):
         if mode not in ("dense", "tiled"):
             raise ValueError(f"OISAT_OI_MODE / oi_mode must be diag, dense or tiled, not {mode!r}")
         L = self._oi_setting("corr_length_km", "OISAT_CORR_LENGTH_KM", 300.0, float)
+        corr = self._oi_setting("oi_correlation", "OISAT_CORRELATION", "gaussian").lower()
+        if corr not in ("gaussian", "gaspari_cohn"):
+            raise ValueError(f"OISAT_CORRELATION / oi_correlation must be gaussian or gaspari_cohn, not {corr!r}")
         unobserved = self._oi_setting("oi_unobserved", "OISAT_UNOBSERVED", "nan").lower()
         if unobserved not in ("nan", "xa"):
             raise ValueError(f"OISAT_UNOBSERVED / oi_unobserved must be nan or xa, not {unobserved!r}")
@@ -146,7 +151,7 @@ class oisatgmi(object):
         for tail in np.ndindex(*xa.shape[2:]):
             sl = (slice(None), slice(None)) + tail
             res, info = self._oi_spatial(mode, xa[sl], y[sl], np.asarray(Sa)[sl], np.asarray(So)[sl], lat, lon, L, tile,
-                                         unobserved, reg_index, want_error)
+                                         unobserved, reg_index, want_error, corr=corr)
             for o, r in zip(outs, res):
                 o[sl] = r
             infos.append(info)
@@ -154,16 +159,16 @@ class oisatgmi(object):
         self.oi_info = dict(infos[0]) if len(infos) == 1 else {**infos[0], "slices": infos}
 
     @staticmethod
-    def _oi_spatial(mode, xa, y, Sa, So, lat, lon, L, tile, unobserved, reg_index, want_error):
+    def _oi_spatial(mode, xa, y, Sa, So, lat, lon, L, tile, unobserved, reg_index, want_error, corr="gaussian"):
         """One (ny, nx) Gaussian-B analysis -> ((Xb, AK, increment, error), info) in the reference's attribute order."""
         from . import dense
         from . import optimal_interpolation as oi_mod
         index, scale, curve, found = oi_mod.regularization_pick(Sa, So, reg_index)
         print("The regularization factor is " + str(scale))
         if mode == "dense":
-            xb, inc, info = dense.OI_dense(xa, y, Sa, So, lat, lon, L, scale=scale, want_error=want_error)
+            xb, inc, info = dense.OI_dense(xa, y, Sa, So, lat, lon, L, scale=scale, want_error=want_error, corr=corr)
         else:
-            xb, inc, info = dense.OI_tiled(xa, y, Sa, So, lat, lon, L, tile_deg=tile, scale=scale, want_error=want_error)
+            xb, inc, info = dense.OI_tiled(xa, y, Sa, So, lat, lon, L, tile_deg=tile, scale=scale, want_error=want_error, corr=corr)
         xb, inc = np.array(xb, dtype=np.float64), np.array(inc, dtype=np.float64)
         if want_error:
             err, ak = np.array(info["err"], dtype=np.float64), np.array(info["ak"], dtype=np.float64)
@@ -184,7 +189,7 @@ class oisatgmi(object):
                 ak[~observed & np.isfinite(xa)] = 0.0
             for a in (inc, err, ak):
                 a[~np.isfinite(xa)] = np.nan
-        return (xb, ak, inc, err), {"mode": mode, "corr_length_km": L, "scale": scale, "reg_index": index, "knee_found": found,
+        return (xb, ak, inc, err), {"mode": mode, "corr_length_km": L, "correlation": corr, "scale": scale, "reg_index": index, "knee_found": found,
                                     "nobs": info["nobs"], "unobserved": unobserved, "want_error": want_error}
 
     def scaling_factor(self):
