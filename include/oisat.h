@@ -408,6 +408,23 @@ int oisat_factor_envelope(const double* lat_sorted, int64_t m, double g, int32_t
  * oisat_potrf_env_fwd on this handle, which consumes it whatever its outcome and checks it against its own first.  Without
  * it, and in every other factorization (oisat_potrf, the batched ones), there is no far stretch. */
 int oisat_factor_far(const double* lat_sorted, int64_t m, double g, const int32_t* first, int32_t* far_out);
+/* The middle stretch of the factor's K-loops (csrc/dense_chol.hip: kFactorMidBits).
+ * oisat_factor_mid (host only): mid_out[i], far[i] <= mid_out[i] <= i, = the first block column of block row i that is NOT
+ * middle: every correlation between an observation of block row i and one of a block column k < mid_out[i] is below the
+ * middle cut-off.  The enveloped task graph runs the K-blocks far[i] <= k < mid_out[i] of the row's tiles as split bf16
+ * products: each operand a = hi + lo, hi = bf16(a), lo = bf16(a - hi), and a b^T becomes lo hi^T + hi lo^T + hi hi^T with fp32
+ * accumulation (relative error ~2^-16 where the far stretch has 2^-8).  first and far are the tables of
+ * oisat_factor_envelope and oisat_factor_far for the same observations and g (far == first: no far stretch, the middle one
+ * starts at first[i]); the same argument checks as oisat_factor_far, and far is checked against first.  The stretch is on
+ * exactly where the far stretch is on by default; everywhere else, and under OISAT_ENVELOPE=0, mid_out == far.
+ * OISAT_FACTOR_MID_BITS=<n> in the environment (read at every call; 0 <= n <= 52, anything else is OISAT_EINVAL): 0 switches
+ * the stretch off, n >= 1 forces the cut-off 2^-n at every enveloped size, whatever OISAT_FACTOR_FAR_BITS says (an n at or above
+ * the far cut-off in force leaves nothing in the middle).
+ * oisat_set_factor_mid: hands the table (host int32[nb], copied; NULL / 0 = none) to the NEXT oisat_potrf_env /
+ * oisat_potrf_env_fwd on this handle, which consumes it whatever its outcome and checks it against its own first and the far
+ * table set for the same call.  Without it, and in every other factorization, there is no middle stretch.  The ticket words
+ * of oisat_dag_task_order_env do not carry it: the launch reads the table itself. */
+int oisat_factor_mid(const double* lat_sorted, int64_t m, double g, const int32_t* first, const int32_t* far, int32_t* mid_out);
 
 /* ---- the correlation model ----------------------------------------------------------------------------------------
  * OISAT_CORR_GAUSSIAN (default): C = exp(-g chord^2).  OISAT_CORR_GASPARI_COHN: the compactly supported fifth-order function
@@ -436,6 +453,9 @@ int oisat_envelope_corr(int kind, const double* lat_sorted, int64_t m, double g,
 int oisat_factor_envelope_corr(int kind, const double* lat_sorted, int64_t m, double g, int32_t* env_out);
 int oisat_factor_far_corr(int kind, const double* lat_sorted, int64_t m, double g, const int32_t* first, int32_t* far_out);
 int oisat_set_factor_far(oisat_ctx* h, const int32_t* far, int64_t nb);
+int oisat_factor_mid_corr(int kind, const double* lat_sorted, int64_t m, double g, const int32_t* first, const int32_t* far,
+                          int32_t* mid_out);       /* oisat_factor_mid for a model; Gaspari-Cohn: mid_out == far unless forced */
+int oisat_set_factor_mid(oisat_ctx* h, const int32_t* mid, int64_t nb);
 int oisat_cov_build_env(oisat_ctx* h, const double* oxyz, const double* osig, const double* ovar, int64_t m,
                         double g, float* S, int64_t ld, const int32_t* env_dev);
 int oisat_potrf_env(oisat_ctx* h, float* S, int64_t m, int64_t ld, const int32_t* first, const int32_t* env_dev,

@@ -2261,8 +2261,9 @@ static bool fwd_in_launch_off() {
 // fwd_d (device double[m]) or nullptr: the right-hand side whose first forward sweep rides in the task-graph launch
 // (oisat_potrf_env_fwd).  schedule_out (optional): OISAT_SCHEDULE_* of what ran.
 // far (host int32[mpb], with first) or nullptr: the far stretch of every block row (oisat_factor_far), bf16 K-blocks in the task graph
+// mid (likewise) or nullptr: the middle stretch behind it (oisat_factor_mid), split bf16 K-blocks
 static int potrf_impl(oisat_ctx* h, float* S, int64_t m, int64_t ld, int* info_host, const int32_t* first, const int32_t* env_dev,
-                      const double* fwd_d = nullptr, int* schedule_out = nullptr, const int32_t* far = nullptr) {
+                      const double* fwd_d = nullptr, int* schedule_out = nullptr, const int32_t* far = nullptr, const int32_t* mid = nullptr) {
     ARG_CHECK(h && S && m > 0);
     h->factor.fwd_d = nullptr;                                  // whatever comes of this call, the last factor's forward vector is history
     if (schedule_out) *schedule_out = OISAT_SCHEDULE_OTHER;
@@ -2305,8 +2306,9 @@ static int potrf_impl(oisat_ctx* h, float* S, int64_t m, int64_t ld, int* info_h
         if (hit && first) {
             DagPlan& pl = *(DagPlan*)hit->plan;
             if (memcmp(pl.first.data(), first, sizeof(int) * (size_t)mpb) != 0 ||
-                memcmp(pl.far.data(), far ? far : first, sizeof(int) * (size_t)mpb) != 0)
-                if (int rf = dag_plan_refill(pl, first, far, h->stream)) return rf;
+                memcmp(pl.far.data(), far ? far : first, sizeof(int) * (size_t)mpb) != 0 ||
+                memcmp(pl.mid.data(), mid ? mid : far ? far : first, sizeof(int) * (size_t)mpb) != 0)
+                if (int rf = dag_plan_refill(pl, first, far, mid, h->stream)) return rf;
         }
         if (!hit) {
             DagSingle* slot = nullptr;
@@ -2325,7 +2327,8 @@ static int potrf_impl(oisat_ctx* h, float* S, int64_t m, int64_t ld, int* info_h
                 shape.refine = 0;
                 shape.fwd_only = true;
             }
-            slot->plan = dag_plan_create(std::vector<BatchMat>{BatchMat{S, tinv, ld, m, (int)mpb, 0}}, h->stream, shape, first, first ? far : nullptr);
+            slot->plan = dag_plan_create(std::vector<BatchMat>{BatchMat{S, tinv, ld, m, (int)mpb, 0}}, h->stream, shape, first, first ? far : nullptr,
+                                         first ? mid : nullptr);
             if (!slot->plan) return OISAT_ENOMEM;
             slot->S = S; slot->tinv = tinv; slot->ld = ld; slot->mpb = mpb; slot->enveloped = first != nullptr; slot->fwd = ride;
             hit = slot;
@@ -2556,6 +2559,78 @@ static bool far_table_ok(const std::vector<int32_t>& far, const int32_t* first, 
     return true;
 }
 
+// The middle stretch of the factor's K-loops: the block columns far[i] <= k < mid[i] of block row i, between the far stretch
+// and the fp32 rest.  Every correlation between an observation of block row i and one of those block columns is below
+// 2^-kFactorMidBits; the products of those K-blocks run on the bf16 pipe as SPLIT products (dense_dag.inc: dag_seg_bf16x2,
+// hi hi^T + hi lo^T + lo hi^T, relative error ~2^-16 instead of the far stretch's 2^-8), 3/16 of the fp32 pipe's MFMA cycles.
+// The argument is the far stretch's, eight bits further in: an error of 2^-16 of a term bounded by 2^-f.  On by default exactly
+// where the far stretch is (Gaussian, tile-work-bound, no forced OISAT_FACTOR_CUT_BITS, not OISAT_ENVELOPE=0).
+// OISAT_FACTOR_MID_BITS=<n> (read at every call): 0 = off (mid = far); 1 .. 52 forces 2^-n at every enveloped size; an n at or
+// above the far cut-off in force leaves nothing in the middle (the table is clamped to far[i] <= mid[i] <= i), and with the far
+// stretch off the middle one starts at first[i].
+// The value is a measurement, by the protocol of kFactorFarBits (profiles/EXPERIMENTS.md, "The middle stretch as split bf16
+// products"; profiles/mid_band_sweep.json): on the same four months, far stretch at 2^-18, OISAT_FACTOR_MID_BITS = 16 .. 6
+// leave the first residual within +1.3 % / -0.6 % of the run without a middle stretch, one correction converges, the last
+// residual within 8 %; 4 bits, the smallest value swept, are still admissible by the rule (first residual <= 1.05 x: it is
+// 1.5 - 3.6 % up, the last residual 2 - 6 %) but the rise has begun -- the host emulation puts the break between 6 and 4.
+// Kept: the smallest admissible value, 4, plus 4 bits of headroom for a denser month.  Headline: 892 351 of 2 519 868 K-blocks
+// are middle (0.354) next to 872 522 far ones (0.346); the step falls by 2.9 ms per 0.1 of share, against 4.7 for the far
+// stretch: a middle K-block costs about 0.6 of an fp32 one.  potrf_dag 66.9 -> 56.5 ms, the step 84.6 - 84.8 -> 74.4 - 74.6 ms.
+constexpr double kFactorMidBits = 8.0;
+
+extern "C" int oisat_factor_mid_corr(int kind, const double* lat_sorted, int64_t m, double g, const int32_t* first, const int32_t* far,
+                                     int32_t* mid_out) {
+    ARG_CHECK(corr_kind_ok(kind) && lat_sorted && first && far && mid_out && m > 0 && g >= 0.0);
+    for (int64_t i = 1; i < m; ++i) ARG_CHECK(lat_sorted[i] >= lat_sorted[i - 1]);
+    const int64_t nb = cdiv(m, NB);
+    ARG_CHECK(envelope_table_ok(first, nb));
+    for (int64_t i = 0; i < nb; ++i) ARG_CHECK(far[i] >= first[i] && far[i] <= i);
+    double bits = kFactorMidBits;
+    bool on = false;
+    const char* e = getenv("OISAT_FACTOR_MID_BITS");
+    if (e && *e) {
+        char* end = nullptr;
+        bits = strtod(e, &end);
+        ARG_CHECK(end != e && *end == '\0' && bits >= 0.0 && bits <= kCutBits);
+        on = bits >= 1.0;
+        ARG_CHECK(on || bits == 0.0);
+    } else {
+        const char* c = getenv("OISAT_FACTOR_CUT_BITS");
+        if (!(c && *c) && kind == OISAT_CORR_GAUSSIAN) {        // the far stretch's default rule
+            std::vector<int32_t> narrow(2 * (size_t)nb);
+            envelope_table(kind, lat_sorted, m, g, kFactorCutBits, narrow.data());
+            on = (double)envelope_ksteps(narrow.data(), nb) > kFactorMinKstepsPerRow * (double)nb;
+        }
+    }
+    if (on && !oisat_envelope_off()) {
+        std::vector<int32_t> t(2 * (size_t)nb);
+        envelope_table(kind, lat_sorted, m, g, bits, t.data());
+        for (int64_t i = 0; i < nb; ++i) mid_out[i] = std::min<int32_t>(std::max(t[i], far[i]), (int32_t)i);
+    } else {
+        for (int64_t i = 0; i < nb; ++i) mid_out[i] = far[i];
+    }
+    return OISAT_OK;
+}
+
+extern "C" int oisat_factor_mid(const double* lat_sorted, int64_t m, double g, const int32_t* first, const int32_t* far, int32_t* mid_out) {
+    return oisat_factor_mid_corr(OISAT_CORR_GAUSSIAN, lat_sorted, m, g, first, far, mid_out);
+}
+
+extern "C" int oisat_set_factor_mid(oisat_ctx* h, const int32_t* mid, int64_t nb) {
+    ARG_CHECK(h != nullptr && nb >= 0 && (mid != nullptr || nb == 0));
+    h->factor_mid.assign(mid, mid + nb);
+    return OISAT_OK;
+}
+
+// the middle table the caller set for this factorization (empty: none) against its envelope and its far table (empty: first)
+static bool mid_table_ok(const std::vector<int32_t>& mid, const std::vector<int32_t>& far, const int32_t* first, int64_t nb) {
+    if (mid.empty()) return true;
+    if ((int64_t)mid.size() != nb || !far_table_ok(far, first, nb)) return false;
+    for (int64_t i = 0; i < nb; ++i)
+        if (mid[i] < (far.empty() ? first[i] : far[i]) || mid[i] > i) return false;
+    return true;
+}
+
 extern "C" int oisat_dag_task_order_env(int nb, const int32_t* first, const int32_t* far, int32_t* tasks_out, int64_t capacity,
                                         int64_t* ntasks_out) {
     ARG_CHECK(nb >= 1 && nb <= kDagEnvMaxBlocks && first && ntasks_out && (tasks_out || capacity == 0));
@@ -2573,23 +2648,29 @@ extern "C" int oisat_dag_task_order_env(int nb, const int32_t* first, const int3
 extern "C" int oisat_potrf_env(oisat_ctx* h, float* S, int64_t m, int64_t ld, const int32_t* first, const int32_t* env_dev,
                                int* info_host) {
     ARG_CHECK(h != nullptr);
-    std::vector<int32_t> far;
+    std::vector<int32_t> far, mid;
     far.swap(h->factor_far);                                    // one-shot, whatever this call's outcome
+    mid.swap(h->factor_mid);                                    // likewise
     ARG_CHECK(first && env_dev && m > 0);
-    ARG_CHECK(envelope_table_ok(first, cdiv(m, NB)) && far_table_ok(far, first, cdiv(m, NB)));
+    ARG_CHECK(envelope_table_ok(first, cdiv(m, NB)) && far_table_ok(far, first, cdiv(m, NB)) &&
+              mid_table_ok(mid, far, first, cdiv(m, NB)));
     if (oisat_envelope_off()) return potrf_impl(h, S, m, ld, info_host, nullptr, nullptr);
-    return potrf_impl(h, S, m, ld, info_host, first, env_dev, nullptr, nullptr, far.empty() ? nullptr : far.data());
+    return potrf_impl(h, S, m, ld, info_host, first, env_dev, nullptr, nullptr, far.empty() ? nullptr : far.data(),
+                      mid.empty() ? nullptr : mid.data());
 }
 
 extern "C" int oisat_potrf_env_fwd(oisat_ctx* h, float* S, int64_t m, int64_t ld, const int32_t* first, const int32_t* env_dev,
                                    const double* d, int* info_host, int* schedule_out) {
     ARG_CHECK(h != nullptr);
-    std::vector<int32_t> far;
+    std::vector<int32_t> far, mid;
     far.swap(h->factor_far);                                    // one-shot, whatever this call's outcome
+    mid.swap(h->factor_mid);                                    // likewise
     ARG_CHECK(first && env_dev && d && m > 0);
-    ARG_CHECK(envelope_table_ok(first, cdiv(m, NB)) && far_table_ok(far, first, cdiv(m, NB)));
+    ARG_CHECK(envelope_table_ok(first, cdiv(m, NB)) && far_table_ok(far, first, cdiv(m, NB)) &&
+              mid_table_ok(mid, far, first, cdiv(m, NB)));
     if (oisat_envelope_off()) return potrf_impl(h, S, m, ld, info_host, nullptr, nullptr, d, schedule_out);
-    return potrf_impl(h, S, m, ld, info_host, first, env_dev, d, schedule_out, far.empty() ? nullptr : far.data());
+    return potrf_impl(h, S, m, ld, info_host, first, env_dev, d, schedule_out, far.empty() ? nullptr : far.data(),
+                      mid.empty() ? nullptr : mid.data());
 }
 
 extern "C" int oisat_potrs(oisat_ctx* h, const float* L, int64_t m, int64_t ld, double* z_inout) {

@@ -48,6 +48,7 @@ struct DagSys {                  // one system of a task-graph launch (device ta
     int* state;                  // zero when a launch starts (zeroed at allocation, then by the last workgroup of every launch)
     int nb;                      // block rows
     int which;                   // index reported through info[3] (the batch table's index)
+    const int* mid;              // int32[nb]: first block column of each block row that is not "middle" (DagPlan::mid_dev), or null: no middle stretch
 };
 
 struct DagCtl {                  // zero when a launch starts
@@ -239,8 +240,72 @@ __device__ __forceinline__ void dag_seg_bf16(float* __restrict__ lds, const DagL
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");        // this wave's DMA pieces of K-step kt+1 have landed ...
         __syncthreads();                                        // ... everyone else's too; every read of K-step kt is back
     }
+#undef DAG_CHUNK
+}
+
+// The same K-segment as SPLIT bf16 products -- the MIDDLE stretch of a bulk task's K-loop (kmid, "Middle stretch" at
+// dag_task_order): dag_seg_bf16's LDS image, LDS-DMA fill, barriers and fragment reads, but every operand fragment a becomes
+// two bf16 fragments, hi = bf16(a) (round to nearest even, the far stretch's own rounding) and lo = bf16(a - float(hi)) --
+// a - float(hi) is exact in fp32 -- and a product a b^T becomes lo hi^T + hi lo^T + hi hi^T: relative error ~2^-16 per term
+// (the dropped lo lo^T and the rounding of lo) where dag_seg_bf16 has 2^-8.  Twelve MFMAs per k-chunk into the same four
+// accumulators, in ONE order: a_lo b_hi^T of the quadrants 00, 01, 10, 11, then a_hi b_lo^T of the four, then a_hi b_hi^T of
+// the four -- every accumulator takes its small terms first, and no MFMA waits for the one issued in front of it.  3/16 of
+// dag_seg's MFMA cycles per K-step; the split is VALU work, ~3 instructions per operand element (unpack, subtract, pack),
+// operand by operand so that the raw fp32 fragment of one operand is dead before the next is split.
+__device__ __forceinline__ unsigned dag_pk_bf16_lo(float x, float y, unsigned hi /* dag_pk_bf16(x, y) */) {
+    return dag_pk_bf16(x - __builtin_bit_cast(float, hi << 16), y - __builtin_bit_cast(float, hi & 0xffff0000u));
+}
+__device__ __forceinline__ void dag_split8(const float4& a, const float4& b, dag_bf16x8& hi, dag_bf16x8& lo) {
+    const dag_u32x4 h = {dag_pk_bf16(a.x, a.y), dag_pk_bf16(a.z, a.w), dag_pk_bf16(b.x, b.y), dag_pk_bf16(b.z, b.w)};
+    const dag_u32x4 l = {dag_pk_bf16_lo(a.x, a.y, h.x), dag_pk_bf16_lo(a.z, a.w, h.y), dag_pk_bf16_lo(b.x, b.y, h.z), dag_pk_bf16_lo(b.z, b.w, h.w)};
+    hi = __builtin_bit_cast(dag_bf16x8, h);
+    lo = __builtin_bit_cast(dag_bf16x8, l);
+}
+__device__ __forceinline__ void dag_seg_bf16x2(float* __restrict__ lds, const DagLane& L, const float* Ad, int64_t lda, const float* Bd, int64_t ldb,
+                                               int nkt, f32x16& acc00, f32x16& acc01, f32x16& acc10, f32x16& acc11) {
+    typedef __attribute__((address_space(1))) const void* gptr_t;
+    typedef __attribute__((address_space(3))) void* lptr_t;
+    constexpr int IMG = NB * BK;
+#define DAG_SPLIT(H, LO, buf, op, row, c)                                                                          \
+    do {                                                                                                           \
+        float4 rl, rh;                                                                                             \
+        DAG_RD8(rl, rh, buf, op, row, c);                                                                          \
+        dag_split8(rl, rh, H, LO);                                                                                 \
+    } while (0)
+#define DAG_CHUNK(buf, c)                                                                                          \
+    do {                                                                                                           \
+        dag_bf16x8 a0, a0l, a1, a1l, b0, b0l, b1, b1l;                                                             \
+        DAG_SPLIT(a0, a0l, buf, 0, L.arow, c);                                                                     \
+        DAG_SPLIT(a1, a1l, buf, 0, L.arow + 32 * BK, c);                                                           \
+        DAG_SPLIT(b0, b0l, buf, 1, L.brow, c);                                                                     \
+        DAG_SPLIT(b1, b1l, buf, 1, L.brow + 32 * BK, c);                                                           \
+        acc00 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0l, b0, acc00, 0, 0, 0);                                  \
+        acc01 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0l, b1, acc01, 0, 0, 0);                                  \
+        acc10 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1l, b0, acc10, 0, 0, 0);                                  \
+        acc11 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1l, b1, acc11, 0, 0, 0);                                  \
+        acc00 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0, b0l, acc00, 0, 0, 0);                                  \
+        acc01 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0, b1l, acc01, 0, 0, 0);                                  \
+        acc10 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, b0l, acc10, 0, 0, 0);                                  \
+        acc11 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, b1l, acc11, 0, 0, 0);                                  \
+        acc00 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0, b0, acc00, 0, 0, 0);                                   \
+        acc01 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0, b1, acc01, 0, 0, 0);                                   \
+        acc10 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, b0, acc10, 0, 0, 0);                                   \
+        acc11 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, b1, acc11, 0, 0, 0);                                   \
+    } while (0)
+    DAG_DMA(0, 0);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    for (int kt = 0; kt < nkt; ++kt) {
+        const int cur = kt & 1;
+        if (kt + 1 < nkt) DAG_DMA(cur ^ 1, (kt + 1) * BK);       // the other buffer is free since the last barrier
+        DAG_CHUNK(cur, 0);
+        DAG_CHUNK(cur, 1);
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");        // this wave's DMA pieces of K-step kt+1 have landed ...
+        __syncthreads();                                        // ... everyone else's too; every read of K-step kt is back
+    }
 #undef DAG_DMA
 #undef DAG_RD8
+#undef DAG_SPLIT
 #undef DAG_CHUNK
 }
 
@@ -320,6 +385,9 @@ __device__ __forceinline__ const float* dag_src(const float* tile0, int64_t ld, 
 // kfar (wave-uniform, from the ticket, k0 <= kfar <= kend): the block columns k0 .. kfar - 1 are the row's FAR stretch -- every
 // correlation between an observation of block row i and one of those block columns is below the far cut-off -- and their
 // K-blocks run on the bf16 pipe (dag_seg_bf16); FAR = false (the launch that also solves): the ticket's kfar is ignored.
+// kmid (wave-uniform, one scalar load from sy.mid per task, kfar <= kmid <= kend; no table: kfar): the block columns
+// kfar .. kmid - 1 are the row's MIDDLE stretch, split bf16 products (dag_seg_bf16x2); kmid .. kend - 1 run in fp32.
+// FAR = false ignores it too.
 template <bool FAR>
 __device__ __forceinline__ bool dag_tile_task(const DagSys& sy, int kind, int k0, int kfar, int i, int j, DagCtl* ctl, float* lds, const DagLane& L,
                                               int* s_flag, int* s_kav, long long* tr /* thread 0, tracing: [2] += time spent polling */) {
@@ -331,6 +399,12 @@ __device__ __forceinline__ bool dag_tile_task(const DagSys& sy, int kind, int k0
     const float* Arow = sy.S + (int64_t)i * NB * sy.ld;
     const float* Brow = sy.S + (int64_t)j * NB * sy.ld;
     f32x16 acc00 = {0}, acc01 = {0}, acc10 = {0}, acc11 = {0};
+    int kmid = kfar;
+    if (FAR && sy.mid) {
+        kmid = sy.mid[i];
+        kmid = kmid < kfar ? kfar : kmid;
+        kmid = kmid > kend ? (kend > kfar ? kend : kfar) : kmid;
+    }
     int k = k0;
     while (k < kend) {
         bool ok = true;
@@ -349,6 +423,10 @@ __device__ __forceinline__ bool dag_tile_task(const DagSys& sy, int kind, int k0
             kav = kav < kfar ? kav : kfar;
             dag_seg_bf16(lds, L, dag_src(Arow + (int64_t)k * NB, sy.ld, L), sy.ld, dag_src(Brow + (int64_t)k * NB, sy.ld, L), sy.ld,
                          (kav - k) * (NB / BK), acc00, acc01, acc10, acc11);
+        } else if (FAR && k < kmid) {                           // ... and where the middle stretch does
+            kav = kav < kmid ? kav : kmid;
+            dag_seg_bf16x2(lds, L, dag_src(Arow + (int64_t)k * NB, sy.ld, L), sy.ld, dag_src(Brow + (int64_t)k * NB, sy.ld, L), sy.ld,
+                           (kav - k) * (NB / BK), acc00, acc01, acc10, acc11);
         } else {
             dag_seg(lds, L, dag_src(Arow + (int64_t)k * NB, sy.ld, L), sy.ld, dag_src(Brow + (int64_t)k * NB, sy.ld, L), sy.ld, (kav - k) * (NB / BK),
                     acc00, acc01, acc10, acc11);
@@ -1087,6 +1165,8 @@ struct DagPlan {
     std::vector<int4> tasks_host;
     std::vector<int> first;                                     // the envelope this single-system plan's ticket list was made for (empty: dense)
     std::vector<int> far;                                       // ... and its far stretch (oisat_factor_far; no stretch: equal to first)
+    std::vector<int> mid;                                       // ... and its middle stretch (oisat_factor_mid; no stretch: equal to far)
+    int* mid_dev = nullptr;                                     // the device copy of mid (an enveloped plan's int32[nb]); DagSys::mid points here while a stretch exists
     size_t tasks_cap = 0;                                       // tickets tasks_dev holds (an enveloped plan: the dense list's, so a new envelope refills it)
     long long* trace_dev = nullptr;                             // OISAT_DAG_TRACE: [ntasks][4] + [chain_rows][8] stamps of the last launch
 };
@@ -1098,6 +1178,7 @@ void dag_plan_free(DagPlan* p) {
     if (p->state_dev) (void)hipFree(p->state_dev);
     if (p->ctl_dev) (void)hipFree(p->ctl_dev);
     if (p->queue_dev) (void)hipFree(p->queue_dev);
+    if (p->mid_dev) (void)hipFree(p->mid_dev);
     if (p->trace_dev) (void)hipFree(p->trace_dev);
     delete p;
 }
@@ -1124,6 +1205,11 @@ constexpr int kDagWave0Max = 64;                                // wave 0 holds 
 // kfar << 18, ten bits each (kDagEnvMaxBlocks block rows); its K-blocks k0 .. kfar - 1 run on the bf16 pipe (dag_tile_task).
 // All three bulk kinds; the chain's own panel product and rank-128 update stay fp32.  The dense list and far == nullptr emit
 // kfar = k0: an empty stretch.
+// Middle stretch (oisat_factor_mid: mid[i] = first block column of block row i that is NOT middle, far[i] <= mid[i] <= i): the
+// K-blocks kfar .. kmid - 1 of a bulk task run as split bf16 products (dag_seg_bf16x2).  Ten more bits do not fit the ticket's
+// first word, and the words stay what they are: the table itself goes to the device (DagPlan::mid_dev, uploaded with the ticket
+// list by dag_plan_mid) and a task clamps kmid = mid[i] into [kfar, kend] with one scalar load.  The ticket ORDER does not
+// depend on it.
 constexpr int kDagEnvMaxBlocks = 1024;
 void dag_task_order(const std::vector<int>& nb_of, int wave_arg, DagOrder& out, const int* first = nullptr, const int* far = nullptr) {
     const int nsys = (int)nb_of.size();
@@ -1206,6 +1292,9 @@ void dag_task_order(const std::vector<int>& nb_of, int wave_arg, DagOrder& out, 
                 // With a far stretch (kFactorFarBits = 18: 35 % of the headline's K-blocks at a third of their fp32 time) the tasks are
                 // shorter and a column passes faster: lead 0.1 / 0.15 / 0.2 / 0.25 / 0.3 = 91.8 / 85.2, 85.1 / 84.4 / 84.6 / 84.4 ms per step;
                 // 0.2 is kept there, the smallest of the flat stretch again.  Without a stretch the list is the one above, ticket for ticket.
+                // With the middle stretch behind it (kFactorMidBits = 8: another 35 % of the K-blocks at ~0.6 of their fp32 time) the sweep
+                // was repeated: lead 0.15 / 0.2 / 0.25 / 0.3 / 0.4 = 75.4, 75.5 / 74.4 / 74.2 / 74.4 / 74.8 ms per step.  0.2 .. 0.3 are level
+                // within 0.2 ms: 0.2 stays, no third constant, and the order does not read the middle table.
                 auto ekey = [&](int i, int jj) { return ((double)jj - env_lead * (double)(jj - first[i])) / (double)nb; };
                 // PRE(j) reads row j up to column j - 2 only (the chain adds column j - 1 itself), so it is drawn ONE COLUMN EARLY,
                 // in front of column j - 1's tasks: drawn with column j it was what a small system's chain waited for at every
@@ -1263,13 +1352,29 @@ static inline void dag_queue_entries(const std::vector<int>& nb_of, const DagSol
 static inline bool dag_fits(int max_wave_chains, int slots) { return 4 * max_wave_chains <= slots; }
 static inline int dag_slots(const oisat_ctx* h) { return 2 * (h->cu_count > 0 ? h->cu_count : 256); }
 
+// The middle table of an enveloped single-system plan: host copy (mid == nullptr: far, no stretch), device copy, and the
+// system's pointer to it -- null while no row has a middle block.  Enqueued on `stream`; the host vectors are the sources of
+// the copies, so the caller has synchronised with whatever copy of them was in flight.
+static hipError_t dag_plan_mid(DagPlan& p, const int* mid, hipStream_t stream) {
+    const size_t nb = p.first.size();
+    p.mid.assign(mid ? mid : p.far.data(), (mid ? mid : p.far.data()) + nb);
+    bool any = false;
+    for (size_t i = 0; i < nb; ++i) any = any || p.mid[i] > p.far[i];
+    const int* want = any ? p.mid_dev : nullptr;
+    if (any)
+        if (hipError_t e = hipMemcpyAsync(p.mid_dev, p.mid.data(), sizeof(int) * nb, hipMemcpyHostToDevice, stream)) return e;
+    if (p.sys_host[0].mid == want) return hipSuccess;
+    p.sys_host[0].mid = want;
+    return hipMemcpyAsync(p.sys_dev, p.sys_host.data(), sizeof(DagSys), hipMemcpyHostToDevice, stream);
+}
+
 // systems in table order (largest first)
 // The progress words and the control block are zeroed ON `stream` (the stream the plan's launches go to): a plain hipMemset is
 // ordered in the NULL stream only, which the handles' non-blocking streams do not wait for -- a launch could start on
 // uninitialised words (wrong tickets, flags that read "ready").
 // first (single system only): its envelope; the ticket buffer is then sized for the dense list of these block rows
 DagPlan* dag_plan_create(const std::vector<BatchMat>& table, hipStream_t stream, const DagSolveShape& shape = DagSolveShape(),
-                         const int* first = nullptr, const int* far = nullptr) {
+                         const int* first = nullptr, const int* far = nullptr, const int* mid = nullptr) {
     DagPlan* p = new DagPlan();
     const int nsys = (int)table.size();
     p->nsys = nsys;
@@ -1315,6 +1420,7 @@ DagPlan* dag_plan_create(const std::vector<BatchMat>& table, hipStream_t stream,
               hipMalloc((void**)&p->tasks_dev, sizeof(int4) * p->tasks_cap) == hipSuccess &&
               hipMalloc((void**)&p->state_dev, sizeof(int) * words) == hipSuccess &&
               hipMalloc((void**)&p->ctl_dev, sizeof(DagCtl)) == hipSuccess &&
+              (p->first.empty() || hipMalloc((void**)&p->mid_dev, sizeof(int) * p->first.size()) == hipSuccess) &&
               (p->qcap == 0 || (p->qcap < (int64_t)INT32_MAX / 4 && hipMalloc((void**)&p->queue_dev, 16 * (size_t)p->qcap) == hipSuccess));
     if (ok && p->qcap > 0) ok = hipMemsetAsync(p->queue_dev, 0, 16 * (size_t)p->qcap, stream) == hipSuccess;
     if (ok) {
@@ -1324,6 +1430,7 @@ DagPlan* dag_plan_create(const std::vector<BatchMat>& table, hipStream_t stream,
              hipMemcpy(p->tasks_dev, tasks.data(), sizeof(int4) * tasks.size(), hipMemcpyHostToDevice) == hipSuccess &&
              hipMemsetAsync(p->state_dev, 0, sizeof(int) * words, stream) == hipSuccess &&
              hipMemsetAsync(p->ctl_dev, 0, sizeof(DagCtl), stream) == hipSuccess;
+        if (ok && !p->first.empty()) ok = dag_plan_mid(*p, mid, stream) == hipSuccess;
     }
     if (!ok) {
         dag_plan_free(p);
@@ -1335,7 +1442,7 @@ DagPlan* dag_plan_create(const std::vector<BatchMat>& table, hipStream_t stream,
 
 // A cached enveloped plan meets another envelope (same matrix, same block rows): new ticket list into the SAME buffers.  The
 // copy is enqueued on `stream`, behind the launches that still read the old list.
-int dag_plan_refill(DagPlan& p, const int* first, const int* far, hipStream_t stream) {
+int dag_plan_refill(DagPlan& p, const int* first, const int* far, const int* mid, hipStream_t stream) {
     const int nb = p.sys_host[0].nb;
     DagOrder order;
     dag_task_order(std::vector<int>{nb}, 0, order, first, far);
@@ -1353,6 +1460,7 @@ int dag_plan_refill(DagPlan& p, const int* first, const int* far, hipStream_t st
     p.reserve_chains = order.reserve_chains;
     if (p.trace_dev) { (void)hipFree(p.trace_dev); p.trace_dev = nullptr; }      // (profiling aid: sized by the ticket count)
     HIP_TRY(hipMemcpyAsync(p.tasks_dev, p.tasks_host.data(), sizeof(int4) * p.tasks_host.size(), hipMemcpyHostToDevice, stream));
+    HIP_TRY(dag_plan_mid(p, mid, stream));
     return OISAT_OK;
 }
 

@@ -146,6 +146,7 @@ struct oisat_ctx {
     const int* obs_perm = nullptr;      // oisat_set_obs_blocks: space-filling order of the observations of the next gain solves
     int64_t obs_perm_m = 0;
     std::vector<int32_t> factor_far;    // oisat_set_factor_far: the far stretch of the NEXT enveloped factorization (one-shot)
+    std::vector<int32_t> factor_mid;    // oisat_set_factor_mid: ... and its middle stretch (one-shot)
     int dag_mode = -1;                  // oisat_set_task_graph: -1 = by size (and OISAT_DAG), 0 = recursion only, 1 = task graph wherever it applies
     DagSingle dag_cache[8];
     uint64_t dag_clock = 0;

@@ -100,12 +100,15 @@ SIGNATURES = {
     "oisat_factor_envelope": (C.c_int, [_ptr, _i64, C.c_double, _ptr]),
     "oisat_factor_far": (C.c_int, [_ptr, _i64, C.c_double, _ptr, _ptr]),
     "oisat_set_factor_far": (C.c_int, [_ptr, _ptr, _i64]),
+    "oisat_factor_mid": (C.c_int, [_ptr, _i64, C.c_double, _ptr, _ptr, _ptr]),
+    "oisat_set_factor_mid": (C.c_int, [_ptr, _ptr, _i64]),
     "oisat_set_correlation": (C.c_int, [_c_ctx, C.c_int]),
     "oisat_corr_eval": (C.c_int, [C.c_int, C.c_double, _ptr, _i64, _ptr]),
     "oisat_corr_cut_chord": (C.c_int, [C.c_int, C.c_double, C.c_double, C.POINTER(C.c_double)]),
     "oisat_envelope_corr": (C.c_int, [C.c_int, _ptr, _i64, C.c_double, _ptr]),
     "oisat_factor_envelope_corr": (C.c_int, [C.c_int, _ptr, _i64, C.c_double, _ptr]),
     "oisat_factor_far_corr": (C.c_int, [C.c_int, _ptr, _i64, C.c_double, _ptr, _ptr]),
+    "oisat_factor_mid_corr": (C.c_int, [C.c_int, _ptr, _i64, C.c_double, _ptr, _ptr, _ptr]),
     "oisat_dag_task_order_env": (C.c_int, [C.c_int, _ptr, _ptr, _ptr, _i64, C.POINTER(_i64)]),
     "oisat_cov_build_env": (C.c_int, [_c_ctx, _ptr, _ptr, _ptr, _i64, C.c_double, _ptr, _i64, _ptr]),
     "oisat_potrf_env": (C.c_int, [_c_ctx, _ptr, _i64, _i64, _ptr, _ptr, C.POINTER(C.c_int)]),

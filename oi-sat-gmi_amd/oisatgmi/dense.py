@@ -151,7 +151,7 @@ class DenseAnalysis:
             self.perm.shared_with_other_streams()
         # the block envelope of the latitude-sorted system (``oisat_factor_envelope``): first | last, 2 x mp_max / 128 words
         self.env = c.alloc(2 * (self.mp_max // NB) * 4)
-        self._env_host, self._env_key, self._far_host = None, None, None
+        self._env_host, self._env_key, self._far_host, self._mid_host = None, None, None, None
         self._kind = 0                                         # the correlation model of the last run / run_build
         # What this plan knows about its S between runs (``oisat_cov_build_env_zeroed``): after a build and an enveloped
         # task-graph factorization with table T nothing outside T has been written, so every lower tile left of T is still the
@@ -210,16 +210,20 @@ class DenseAnalysis:
         """Host table ``first`` of this plan's observations at decay constant ``g`` under correlation model ``kind`` (the
         library's rule and the fp32 factor's cut-off: ``oisat_factor_envelope_corr``); its device copy ``first | last`` is in
         ``self.env``.  With it the far stretch of the factor's K-loops (``oisat_factor_far_corr``: the block columns of every
-        row that run on the bf16 pipe), host only, in ``self._far_host``.  Both made once per (observations, L, model)."""
+        row that run on the bf16 pipe), host only, in ``self._far_host``, and the middle stretch behind it (``oisat_factor_mid_corr``:
+        split bf16 products) in ``self._mid_host``.  All made once per (observations, L, model)."""
         if self._env_host is None or self._env_key != (g, kind):
             nb = self.mp // NB
             env = np.empty(2 * nb, dtype=np.int32)
             far = np.empty(nb, dtype=np.int32)
+            mid = np.empty(nb, dtype=np.int32)
             self.ctx.check(self.ctx.lib.oisat_factor_envelope_corr(kind, self._lat_sorted.ctypes.data, self.m, g, env.ctypes.data))
             self.ctx.check(self.ctx.lib.oisat_factor_far_corr(kind, self._lat_sorted.ctypes.data, self.m, g, env.ctypes.data,
                                                               far.ctypes.data))
+            self.ctx.check(self.ctx.lib.oisat_factor_mid_corr(kind, self._lat_sorted.ctypes.data, self.m, g, env.ctypes.data,
+                                                              far.ctypes.data, mid.ctypes.data))
             self.ctx.upload_into(self.env.ptr, env)
-            self._env_host, self._env_key, self._far_host = env, (g, kind), far
+            self._env_host, self._env_key, self._far_host, self._mid_host = env, (g, kind), far, mid
         return self._env_host
 
     def _unsort(self, per_obs):
@@ -272,6 +276,7 @@ class DenseAnalysis:
                                                self._zero_dev.ptr if claim else None, C.byref(enveloped)))
         info = C.c_int(0)
         c.check(lib.oisat_set_factor_far(h, self._far_host.ctypes.data, self._far_host.size))        # per run: handles are shared
+        c.check(lib.oisat_set_factor_mid(h, self._mid_host.ctypes.data, self._mid_host.size))
         c.check(lib.oisat_potrf_env_fwd(h, self.S.ptr, m, ld, first.ctypes.data, self.env.ptr, self.d.ptr,
                                         C.byref(info) if check_pd else None, C.byref(schedule)))
         self.last_schedule = schedule.value                    # (SCHEDULE_*: which factorization ran, for tests and profiles)

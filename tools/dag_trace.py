@@ -76,6 +76,25 @@ def report(path):
     print("   by tenth of the span: " + " ".join(line))
 
 
+def kblock_costs(path, mid):
+    """Least squares over the tile tasks: time not polling = c + a far K-blocks + b middle K-blocks + f fp32 K-blocks (the
+    ranges as the kernel clamps them: kfar from the ticket word, kmid = mid[i] into [kfar, kend])."""
+    raw = open(path, "rb").read()
+    nt = int(np.frombuffer(raw, np.int32, 1)[0])
+    words = np.frombuffer(raw, np.int32, 4 * nt, 8).reshape(nt, 4)
+    _, tk, _ = parse(path)
+    sel = (words[:, 0] >= 0) & ((words[:, 0] & 255) == 1) & (tk[:, 1] > 0)
+    w, t = words[sel], tk[sel]
+    k0, kfar, i, kend = (w[:, 0] >> 8) & 1023, w[:, 0] >> 18, w[:, 2], w[:, 3]
+    kmid = np.minimum(np.maximum(mid[i], kfar), np.maximum(kend, kfar))
+    A = np.stack([np.ones(len(w)), kfar - k0, kmid - kfar, kend - kmid], 1).astype(np.float64)
+    y = (t[:, 1] - t[:, 0] - t[:, 2]) * 0.01
+    c = np.linalg.lstsq(A, y, rcond=None)[0]
+    n = A[:, 1:].sum(0)
+    print("tile tasks, time not polling ~ %.1f us + %.2f us per far K-block (%d) + %.2f per middle K-block (%d) + %.2f per fp32 K-block (%d); rms of the fit %.1f us"
+          % (c[0], c[1], n[0], c[2], n[1], c[3], n[2], np.sqrt(np.mean((A @ c - y) ** 2))))
+
+
 if __name__ == "__main__":
     arg = sys.argv[1] if len(sys.argv) > 1 else "10000"
     if os.path.exists(arg):
@@ -101,3 +120,5 @@ if __name__ == "__main__":
     plan.check()
     del os.environ["OISAT_DAG_TRACE"]
     report(out)
+    if plan._mid_host is not None:
+        kblock_costs(out, plan._mid_host)
