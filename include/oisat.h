@@ -167,7 +167,14 @@ int oisat_column_sum(oisat_ctx* h, int dtype, const void* ctm_pmid, const void* 
 /* ---- averaging-kernel convolution: ak_conv_mopitt.py / ak_conv_gosat.py (driver.py:46-51 conv_ak) ------------
  * The satellite_opt counterpart of oisat_amf_recal: per pixel the model column (cubes of dtype ctm_dtype,
  * level-major [nzc][n]) is interpolated in log-pressure onto the satellite levels (double, [nzs][n]) with
- * scipy interp1d's arithmetic, then the retrieval's averaging kernels are applied.
+ * scipy interp1d's arithmetic, then the retrieval's averaging kernels are applied.  np.log / np.log10 of a float32
+ * cube is the double logarithm rounded once to float32.
+ * Which arithmetic interp1d uses depends on the dtype and the fill value, and so does this library:
+ *   - float32 cubes (either sensor) and GOSAT's fill_value="extrapolate": interp1d._call_linear -- stable sort with NaN
+ *     last, searchsorted-left, end segments clipped, slope*(x - x_lo) + y_lo with the slope in the cubes' dtype;
+ *   - float64 cubes under MOPITT's fill_value=nan: interp1d._call_linear_np, i.e. np.interp -- the node's own value
+ *     when a level lies exactly on a node (of equal nodes, the last one's), and where the left-hand expression is NaN
+ *     the same slope taken from the right-hand node, then the common value if both nodes hold it.
  * MOPITT (ak_conv_mopitt.py:118-146): fill NaN outside the model's pressure range; averaging_kernels is
  *   [nzs+1][n] (row 0 = surface); model_vcd = aprior_column + nansum(AK[1:]*(log10 x - log10 apriori_profile))
  *   + AK[0]*(log10 x_model[0] - log10 apriori_surface); model_xcol = 1e6*model_vcd/nansum(air partial column);

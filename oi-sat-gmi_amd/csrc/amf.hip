@@ -7,8 +7,8 @@
 // pixel (:97-119).  Here a thread owns a pixel: its scattering-weight profile is sorted by
 // log-pressure in thread-private memory (interp1d sorts with a stable argsort), every model level is
 // located by binary search and interpolated / extrapolated with the operation order of scipy's
-// _call_linear, and the two column sums are taken in NumPy's pairwise order, so float64 results
-// agree with the reference to the last bits.
+// _call_linear (np.interp's where scipy delegates to it: see ModelColumn), and the two column sums
+// are taken in NumPy's pairwise order, so float64 results agree with the reference to the last bits.
 //
 // HBM layout: level-major cubes [nz][ny*nx] (what the readers and interpolator() produce), so for
 // each level a wave reads 64 consecutive pixels: coalesced.  Everything is double.
@@ -174,9 +174,13 @@ __global__ __launch_bounds__(256) void pwv_sum_kernel(const T* __restrict__ part
 
 // ---- averaging-kernel convolution ------------------------------------------------------------------
 // interp1d(np.log(model pressure), model profile)(np.log(satellite pressure)) for one pixel: the model column is
-// sorted by log-pressure in the cubes' dtype T (stable, NaN last), a satellite level is located by binary search and
-// evaluated with scipy's _call_linear order -- the slope in T, the rest in double, exactly as NumPy promotes
-// float32 model arrays against the float64 satellite levels.
+// sorted by log-pressure in the cubes' dtype T (stable, NaN last) and a satellite level is located by binary search.
+// Which of scipy's two linear paths evaluates it depends on the dtype and the fill value (interp1d.__init__):
+//   float32 cubes, or fill_value="extrapolate" (GOSAT): _call_linear -- searchsorted-left, end segments clipped, the
+//     slope in T and the rest in double, exactly as NumPy promotes float32 model arrays against float64 levels;
+//   float64 cubes with fill_value=nan (MOPITT): _call_linear_np, i.e. np.interp -- the node's own value at a node, and
+//     a retry from the right-hand node when the left-hand expression is NaN (at_interp below).
+// np.log of a float32 cube is float32: the logarithm is taken in double and rounded once to T.
 template <typename T>
 struct ModelColumn {
     T xs[kMaxCtm], ys[kMaxCtm];
@@ -184,14 +188,37 @@ struct ModelColumn {
     __device__ void load(const T* __restrict__ pmid, const T* __restrict__ prof, int nzc, int64_t stride, int64_t p) {
         n = nzc;
         for (int k = 0; k < nzc; ++k) {
-            const T x = (T)log(pmid[(int64_t)k * stride + p]), y = prof[(int64_t)k * stride + p];
+            const T x = (T)log((double)pmid[(int64_t)k * stride + p]), y = prof[(int64_t)k * stride + p];
             int j = k;
             while (j > 0 && before((double)x, (double)xs[j - 1])) { xs[j] = xs[j - 1]; ys[j] = ys[j - 1]; --j; }
             xs[j] = x;
             ys[j] = y;
         }
     }
+    // np.interp(xq, xs, ys) under interp1d's fill_value=nan, bounds_error=False (NumPy's arr_interp; float64 cubes only)
+    __device__ double at_interp(double xq) const {
+        const double nan = __builtin_nan("");
+        if (xq != xq) return xq;
+        if (xq < (double)xs[0] || xq > (double)xs[n - 1]) return nan;       // interp1d._check_bounds
+        int lo = 0, hi = n;                 // j = last node with xs[j] <= xq; a NaN node (sorted last) is above every query
+        while (lo < hi) {
+            const int mid = (lo + hi) >> 1;
+            if (xq >= (double)xs[mid]) lo = mid + 1; else hi = mid;
+        }
+        const int j = lo < 1 ? 0 : lo - 1;
+        const double x_j = (double)xs[j], y_j = (double)ys[j];
+        if (j == n - 1 || x_j == xq) return y_j;
+        const double x_k = (double)xs[j + 1], y_k = (double)ys[j + 1];
+        const double slope = (y_k - y_j) / (x_k - x_j);
+        double y = slope * (xq - x_j) + y_j;
+        if (y != y) {                       // NaN in one direction: try the other
+            y = slope * (xq - x_k) + y_k;
+            if (y != y && y_j == y_k) y = y_j;
+        }
+        return y;
+    }
     __device__ double at(double xq, bool extrapolate) const {
+        if (sizeof(T) == sizeof(double) && !extrapolate) return at_interp(xq);
         int lo = 0, hi = n;                 // np.searchsorted(xs, xq, 'left'); NaN query -> n
         if (xq != xq) lo = n;
         else
@@ -235,7 +262,7 @@ __global__ __launch_bounds__(128) void ak_conv_mopitt_kernel(const T* __restrict
     }
     const double prof_part = ap_col[p] + numpy_sum_le128<double>(term, nzs);
     const T surf = ctm_prof[p];            // model level 0 (before sorting), log10 in the cubes' dtype
-    const double surf_part = ak[p] * ((double)(T)log10(surf) - log10(ap_surf[p]));
+    const double surf_part = ak[p] * ((double)(T)log10((double)surf) - log10(ap_surf[p]));
     const double v = prof_part + surf_part;
     T air[kMaxCtm];
     for (int c = 0; c < nzc; ++c) {

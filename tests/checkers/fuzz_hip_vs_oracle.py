@@ -214,6 +214,58 @@ def fuzz_amf_recal(rng):
             close(getattr(a, f), getattr(b, f), 1e-11 if f64 else 1e-5, "amf_recal " + f, p)
 
 
+def _compare_granules(got, ref, fields, tol, what, p):
+    if len(ref) != len(got):
+        BAD.append((what + " length", p, f"{len(got)} vs {len(ref)}"))
+        return
+    for a, b in zip(got, ref):
+        if (a is None) != (b is None):
+            BAD.append((what + " None", p, ""))
+            continue
+        if b is None:
+            continue
+        for f in fields:
+            close(getattr(a, f), getattr(b, f), tol, f"{what} {f}", p)
+
+
+def fuzz_ak_conv(rng):
+    """The averaging-kernel convolution of both sensors (ak_conv_mopitt.py / ak_conv_gosat.py) on monthly-mean records."""
+    import copy
+    from oisatgmi.ak_conv_mopitt import ak_conv_mopitt as hip_mopitt
+    from oisatgmi.ak_conv_gosat import ak_conv_gosat as hip_gosat
+    sensor = "MOPITT" if rng.integers(0, 2) else "GOSAT"
+    ny, nx, nz = int(rng.integers(5, 40)), int(rng.integers(5, 40)), int(rng.integers(2, 40))
+    nmonths, k, nzs = int(rng.integers(1, 3)), int(rng.integers(1, 4)), int(rng.integers(1, 30))
+    ctmtype = str(rng.choice(["ECCOH", "FREE"]))
+    s1, s2 = int(rng.integers(1, 10 ** 6)), int(rng.integers(1, 10 ** 6))
+    f64 = bool(rng.integers(0, 2))
+    ctm = syn.ctm_monthly(ny, nx, nz, nmonths, s1, ctmtype=ctmtype, dtype=np.float64 if f64 else np.float32)
+    sat = syn.opt_granules(ctm, nzs, k, s2, sensor=sensor)
+    p = dict(sensor=sensor, ny=ny, nx=nx, nz=nz, nmonths=nmonths, k=k, nzs=nzs, ctmtype=ctmtype, s1=s1, s2=s2, f64=f64)
+    with np.errstate(all="ignore"):
+        got = quiet(hip_mopitt if sensor == "MOPITT" else hip_gosat, ctm, copy.deepcopy(sat))
+        ref = quiet(orc.ak_conv, ctm, copy.deepcopy(sat), sensor)
+    _compare_granules(got, ref, ("ctm_vcd", "ctm_xcol"), 1e-11 if f64 else 1e-5, "ak_conv " + sensor, p)
+
+
+def fuzz_pwv(rng):
+    """Model precipitable water for SSMIS (pwv_cal.py)."""
+    import copy
+    from oisatgmi.pwv_cal import pwv_calculator as hip_pwv
+    ny, nx, nz = int(rng.integers(5, 40)), int(rng.integers(5, 40)), int(rng.integers(2, 40))     # (one level: the reference's squeeze() drops the axis)
+    nmonths, k = int(rng.integers(1, 3)), int(rng.integers(1, 4))
+    ctmtype = str(rng.choice(["ECCOH", "FREE"]))
+    s1, s2 = int(rng.integers(1, 10 ** 6)), int(rng.integers(1, 10 ** 6))
+    f64 = bool(rng.integers(0, 2))
+    ctm = syn.ctm_monthly(ny, nx, nz, nmonths, s1, ctmtype=ctmtype, dtype=np.float64 if f64 else np.float32)
+    sat = syn.ssmis_granules(ctm, k, s2)
+    p = dict(ny=ny, nx=nx, nz=nz, nmonths=nmonths, k=k, ctmtype=ctmtype, s1=s1, s2=s2, f64=f64)
+    with np.errstate(all="ignore"):
+        got = quiet(hip_pwv, ctm, copy.deepcopy(sat))
+        ref = quiet(orc.pwv_calculator, ctm, copy.deepcopy(sat))
+    _compare_granules(got, ref, ("ctm_vcd",), 1e-12 if f64 else 1e-6, "pwv", p)
+
+
 def fuzz_dense(rng):
     """The dense Gaussian-B analysis (no reference code: the oracle is the float64 restatement) on random small months."""
     from oisatgmi import dense, _hip
@@ -270,7 +322,8 @@ def main():
     rounds = int(sys.argv[1]) if len(sys.argv) > 1 else 20
     rng = np.random.default_rng(int(sys.argv[2]) if len(sys.argv) > 2 else 20261005)
     for name, fn, mult in (("OI", fuzz_oi, 3), ("error_averager", fuzz_error_averager, 5), ("averaging", fuzz_averaging, 1), ("upscaler", fuzz_upscaler, 2),
-                           ("interpolator", fuzz_interpolator, 1), ("amf_recal", fuzz_amf_recal, 2), ("dense", fuzz_dense, 2)):
+                           ("interpolator", fuzz_interpolator, 1), ("amf_recal", fuzz_amf_recal, 2), ("ak_conv", fuzz_ak_conv, 2), ("pwv", fuzz_pwv, 1),
+                           ("dense", fuzz_dense, 2)):
         before, checks = len(BAD), CHECKS[0]
         for _ in range(rounds * mult):
             fn(rng)
