@@ -463,6 +463,22 @@ int oisat_set_factor_far(oisat_ctx* h, const int32_t* far, int64_t nb);
 int oisat_factor_mid_corr(int kind, const double* lat_sorted, int64_t m, double g, const int32_t* first, const int32_t* far,
                           int32_t* mid_out);       /* oisat_factor_mid for a model; Gaspari-Cohn: mid_out == far unless forced */
 int oisat_set_factor_mid(oisat_ctx* h, const int32_t* mid, int64_t nb);
+/* The factor's shadow (csrc/dense_dag.inc "Shadow"): where an enveloped factorization has a far or a
+ * middle block, the task that makes a strictly-lower tile (r, k), first[r] <= k < r, final also stores its two bf16 images,
+ * hi = bf16(a) (nearest even) and lo = bf16(a - hi), into a per-handle workspace of 64 KiB per tile, and the two stretches
+ * read those instead of converting the fp32 tile in every K-loop.  The factor's bits do not depend on it.  No memory for it:
+ * the launch converts in its K-loops, which is not an error.  OISAT_FACTOR_SHADOW in the environment (read at every call):
+ * unset or 1 = both stretches read it, 0 = none is made, far / mid = only that stretch reads it; anything else is
+ * OISAT_EINVAL of the factorization.
+ * oisat_factor_shadow_layout (host only): rowoff_out[r] (int64[nb]) = number of the first tile of block row r, tile (r, k) is
+ * number rowoff_out[r] + (k - first[r]); *ntiles_out = sum of r - first[r].  A table that is no envelope is OISAT_EINVAL.
+ * oisat_set_factor_shadow_cap: the most bytes the shadow of this handle's later factorizations may take (-1, the default:
+ * no limit; 0: never a shadow).
+ * oisat_factor_shadow_tile (debugging, tests): the images of tile (r, k) as the LAST factorization on this handle left
+ * them, row-major uint16[128 x 128] each; OISAT_EINVAL if that factorization had no shadow or (r, k) is not one of its tiles. */
+int oisat_factor_shadow_layout(int nb, const int32_t* first, int64_t* rowoff_out, int64_t* ntiles_out);
+int oisat_set_factor_shadow_cap(oisat_ctx* h, int64_t bytes);
+int oisat_factor_shadow_tile(oisat_ctx* h, int r, int k, uint16_t* hi_out, uint16_t* lo_out);
 int oisat_cov_build_env(oisat_ctx* h, const double* oxyz, const double* osig, const double* ovar, int64_t m,
                         double g, float* S, int64_t ld, const int32_t* env_dev);
 int oisat_potrf_env(oisat_ctx* h, float* S, int64_t m, int64_t ld, const int32_t* first, const int32_t* env_dev,

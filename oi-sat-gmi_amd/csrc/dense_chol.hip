@@ -2257,6 +2257,18 @@ static bool fwd_in_launch_off() {
     return e != nullptr && atoi(e) == 0;
 }
 
+// OISAT_FACTOR_SHADOW (read at every call): who reads the factor's shadow (dense_dag.inc "Shadow") -- unset or 1: the far and
+// the middle stretch (3); 0: there is none, both convert in their K-loops (A/B timing, tests); far / mid: only that stretch
+// reads it (1 / 2; the writers store all the same, so that each half can be judged alone).  Anything else: -1.
+static int factor_shadow_mode() {
+    const char* e = getenv("OISAT_FACTOR_SHADOW");
+    if (!e || !*e || strcmp(e, "1") == 0) return 3;
+    if (strcmp(e, "0") == 0) return 0;
+    if (strcmp(e, "far") == 0) return 1;
+    if (strcmp(e, "mid") == 0) return 2;
+    return -1;
+}
+
 // first / env_dev: nullptr (dense), or the envelope of S (host: first[mpb]; device: first[mpb] | last[mpb], oisat_envelope)
 // fwd_d (device double[m]) or nullptr: the right-hand side whose first forward sweep rides in the task-graph launch
 // (oisat_potrf_env_fwd).  schedule_out (optional): OISAT_SCHEDULE_* of what ran.
@@ -2266,6 +2278,7 @@ static int potrf_impl(oisat_ctx* h, float* S, int64_t m, int64_t ld, int* info_h
                       const double* fwd_d = nullptr, int* schedule_out = nullptr, const int32_t* far = nullptr, const int32_t* mid = nullptr) {
     ARG_CHECK(h && S && m > 0);
     h->factor.fwd_d = nullptr;                                  // whatever comes of this call, the last factor's forward vector is history
+    h->shadow_last = nullptr;                                   // ... and so is its shadow
     if (schedule_out) *schedule_out = OISAT_SCHEDULE_OTHER;
     const int64_t mp = cdiv(m, NB) * NB;
     ARG_CHECK(ld >= mp && (ld % 4) == 0 && ((uintptr_t)S % 16) == 0);
@@ -2335,6 +2348,24 @@ static int potrf_impl(oisat_ctx* h, float* S, int64_t m, int64_t ld, int* info_h
         }
         hit->stamp = ++h->dag_clock;
         DagPlan& pl = *(DagPlan*)hit->plan;
+        // The shadow: only where a far or middle block exists (the plan's tables are this call's), in workspace slot 10 -- grow-only,
+        // one per handle, whose factorizations follow each other on its stream.  No room for it (or more than
+        // oisat_set_factor_shadow_cap allows): the launch converts in its K-loops as before, the same bits; that is not an error.
+        char* shadow = nullptr;
+        int shadow_use = 0;
+        if (first && (far || mid)) {
+            const int mode = factor_shadow_mode();
+            ARG_CHECK(mode >= 0 && "OISAT_FACTOR_SHADOW is 0, 1, far or mid");
+            bool any = false;
+            for (int64_t b = 0; b < mpb; ++b) any = any || pl.mid[b] > pl.first[b];
+            const size_t bytes = (size_t)pl.sh_tiles * (size_t)kShTile;
+            if (mode > 0 && any && (h->shadow_cap < 0 || bytes <= (size_t)h->shadow_cap)) {
+                shadow = (char*)oisat_ws(h, 10, bytes);
+                if (!shadow) (void)hipGetLastError();          // (the refused allocation is not this launch's error)
+                shadow_use = shadow ? mode : 0;
+            }
+        }
+        HIP_TRY(dag_plan_shadow(pl, shadow, shadow_use, h->stream));
         if (ride) {
             // what oisat_gain_solve does in front of its first solve: the padded right-hand side, the forward vector "not yet
             // published", the solve state reset -- then the launch, whose chain pushes row j of the sweep behind diagonal block j
@@ -2359,6 +2390,11 @@ static int potrf_impl(oisat_ctx* h, float* S, int64_t m, int64_t ld, int* info_h
             rc = dag_launch(h, pl, info_dev, (unsigned*)(info_dev + kInfoDagTimeouts));
         }
         if (schedule_out) *schedule_out = !first ? OISAT_SCHEDULE_OTHER : ride ? OISAT_SCHEDULE_ENV_DAG_FWD : OISAT_SCHEDULE_ENV_DAG;
+        if (rc == OISAT_OK && shadow) {                         // what oisat_factor_shadow_tile reads back
+            h->shadow_last = shadow;
+            h->shadow_first = pl.first;
+            h->shadow_shrow = pl.shrow;
+        }
     } else {
         rc = lookahead ? potrf_lookahead(h, S, ld, mpb, tinv, info_dev, pw) : potrf_rec(h, S, ld, mpb, 0, mpb, tinv, info_dev);
     }
@@ -2629,6 +2665,34 @@ static bool mid_table_ok(const std::vector<int32_t>& mid, const std::vector<int3
     for (int64_t i = 0; i < nb; ++i)
         if (mid[i] < (far.empty() ? first[i] : far[i]) || mid[i] > i) return false;
     return true;
+}
+
+extern "C" int oisat_factor_shadow_layout(int nb, const int32_t* first, int64_t* rowoff_out, int64_t* ntiles_out) {
+    ARG_CHECK(nb >= 1 && nb <= kDagEnvMaxBlocks && first && rowoff_out && ntiles_out);
+    ARG_CHECK(envelope_table_ok(first, nb));
+    *ntiles_out = dag_shadow_layout(first, nb, rowoff_out);
+    return OISAT_OK;
+}
+
+extern "C" int oisat_set_factor_shadow_cap(oisat_ctx* h, int64_t bytes) {
+    ARG_CHECK(h != nullptr && bytes >= -1);
+    h->shadow_cap = bytes;
+    return OISAT_OK;
+}
+
+extern "C" int oisat_factor_shadow_tile(oisat_ctx* h, int r, int k, uint16_t* hi_out, uint16_t* lo_out) {
+    ARG_CHECK(h != nullptr && hi_out && lo_out);
+    ARG_CHECK(h->shadow_last != nullptr && "the last factorization on this handle filled a shadow");
+    ARG_CHECK(r >= 1 && r < (int)h->shadow_first.size() && k >= h->shadow_first[r] && k < r);
+    std::vector<uint16_t> raw((size_t)kShTile / 2);
+    HIP_TRY(hipMemcpyAsync(raw.data(), h->shadow_last + (h->shadow_shrow[r] + k) * kShTile, (size_t)kShTile, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    for (int plane = 0; plane < 2; ++plane)                     // plane [half][row][64 columns] -> row-major 128 x 128
+        for (int half = 0; half < 2; ++half)
+            for (int row = 0; row < NB; ++row)
+                memcpy((plane ? lo_out : hi_out) + row * NB + half * 64, raw.data() + (plane * kShPlane + half * kShHalf + row * 128) / 2,
+                       128);
+    return OISAT_OK;
 }
 
 extern "C" int oisat_dag_task_order_env(int nb, const int32_t* first, const int32_t* far, int32_t* tasks_out, int64_t capacity,

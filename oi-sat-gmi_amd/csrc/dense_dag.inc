@@ -49,6 +49,11 @@ struct DagSys {                  // one system of a task-graph launch (device ta
     int nb;                      // block rows
     int which;                   // index reported through info[3] (the batch table's index)
     const int* mid;              // int32[nb]: first block column of each block row that is not "middle" (DagPlan::mid_dev), or null: no middle stretch
+    // The shadow ("Shadow" below): the bf16 images of every final strictly-lower tile inside the envelope, or null: none, the
+    // far and middle stretches convert in their K-loops.  Tile (r, k) starts at shadow + (shrow[r] + k) * kShTile bytes.
+    char* shadow;
+    const int64_t* shrow;        // int64[nb]: rowoff[r] - first[r] (DagPlan::shrow_dev; rowoff: oisat_factor_shadow_layout)
+    int shuse;                   // who READS it: 1 = the far stretch, 2 = the middle stretch (OISAT_FACTOR_SHADOW); the writers always store
 };
 
 struct DagCtl {                  // zero when a launch starts
@@ -97,6 +102,10 @@ __device__ __forceinline__ bool dag_wait_ge(const int* p, int v, DagCtl* ctl, un
 // factorizations on three streams under bursty memory traffic, saw one wrong factor in ~5,000: a tile task that landed on the
 // CU where SUB(j) had run read L(j+1,j) as SUB(j) had left it.  Both lines of defence -- the producers' drops and the consumers'
 // acquires -- are unconditional in the product.)
+// The shadow (dag_shadow_store) needs nothing more: a shadow tile is written exactly ONCE per launch, write-through, with its
+// final content, in front of the publish of the rowfin word that announces the fp32 tile, and nobody reads it before that
+// word -- there is no pre-final content of it that an L1 or another XCD's L2 could hold; what a previous launch left in a
+// cache is gone at the launch boundary, as for S itself.
 __device__ __forceinline__ void dag_drop_l1() { asm volatile("buffer_inv sc1" ::: "memory"); }
 
 // consumer side, whole workgroup: thread 0 has polled (ok = its verdict)
@@ -309,6 +318,158 @@ __device__ __forceinline__ void dag_seg_bf16x2(float* __restrict__ lds, const Da
 #undef DAG_CHUNK
 }
 
+// ---- Shadow: the bf16 images of the final tiles, made once -----------------------------------------------------------------
+// A finished tile L(r,k) is an operand of up to a band's width of later tasks, and every one of them rounded it (far) or
+// split it (middle) again in its K-loop: 96 VALU instructions per lane and k-chunk in front of the middle stretch's MFMAs,
+// and four bytes fetched per element where the far stretch needs two.  hi = bf16(a) and lo = bf16(a - float(hi)) are pure
+// functions of the final tile, so the task that stores a final off-diagonal tile stores them too (dag_shadow_store) and the
+// two stretches DMA them (dag_seg_bf16_sh, dag_seg_bf16x2_sh): the same operand bits into the same MFMAs in the same order
+// as dag_seg_bf16 / dag_seg_bf16x2 -- the factor does not change by a bit.
+// Layout of a shadow tile (kShTile = 64 KiB, tiles of a block row consecutive in k; DagSys::shadow): two PLANES, hi then lo,
+// each [half h = 0, 1][row 0 .. 127][64 columns 64 h .. 64 h + 63] in bf16 -- rows of 128 bytes, a 64-column step of 16 KiB
+// contiguous.  Only LDS-DMA reads it and every lane gives its own 16-byte source, so
+//   * a FAR K-step is 64 columns deep in the LDS footprint of dag_seg's 32: one contiguous 16 KiB step of the hi plane per
+//     operand, whole cache lines, half the round trips of dag_seg_bf16 and half its bytes; the image row is 8 chunks of 8
+//     columns, k-chunk c of a lane is the logical chunk 2 c + fh: one ds_read_b128 where dag_seg_bf16 has two and four packs;
+//   * a MIDDLE K-step stays 32 columns: an image row is hi of the 32 columns (logical chunks 0 .. 3, 64 bytes of the hi plane's
+//     row) | their lo (chunks 4 .. 7, from the lo plane); k-chunk c is the chunks 2 c + fh and 4 + 2 c + fh.
+// Both images keep dag_seg's 16-byte XOR swizzle (physical chunk = logical ^ (row & 7)), and the fragment reads are
+// dag_seg's pattern with another constant under the XOR -- a bijection of the chunks of a row, so the reads are spread over
+// the 64 banks exactly as swz_sweep found for the fp32 image.  No cache line holds parts of two tiles.
+// Tried and not kept: the images BEHIND the publish of rowfin, announced by a progress word of their own that the shadow
+// segments poll instead, with the chain's images converted from its LDS image under the rank-128 update's MFMAs.  The chain's
+// panel step went back from 15.3 to 12.8 us, but its rank-128 update rose from 7.8 to 10.3 us and its diagonal block from 22.9
+// to 24.8 us: the headline step was the same to 0.1 ms, for a fourth progress array and a second writer.
+constexpr int64_t kShTile = 65536;                              // bytes of a shadow tile
+constexpr int kShPlane = 32768, kShHalf = 16384;                // ... of a plane, of a 64-column half of a plane
+// lane's DMA source inside the shadow tile at `tile` (row wid*32 + rl, logical chunk lc of the image row): far, middle
+__device__ __forceinline__ const char* dag_sh_src_far(const char* tile, const DagLane& L) { return tile + (L.wid * 32 + L.rl) * 128 + 16 * L.lc; }
+__device__ __forceinline__ const char* dag_sh_src_mid(const char* tile, const DagLane& L) {
+    return tile + (L.wid * 32 + L.rl) * 128 + 16 * (L.lc & 3) + (L.lc >> 2) * kShPlane;
+}
+#define DAG_SH_DMA(buf, off)                                                                                       \
+    do {                                                                                                           \
+        _Pragma("unroll") for (int i = 0; i < 4; ++i) {                                                            \
+            __builtin_amdgcn_global_load_lds((gptr_t)(Ad + (off) + 8 * i * 128),                                   \
+                                             (lptr_t)(lds + ((buf) * 2 + 0) * IMG + (L.wid * 32 + 8 * i) * BK), 16, 0, 0); \
+            __builtin_amdgcn_global_load_lds((gptr_t)(Bd + (off) + 8 * i * 128),                                   \
+                                             (lptr_t)(lds + ((buf) * 2 + 1) * IMG + (L.wid * 32 + 8 * i) * BK), 16, 0, 0); \
+        }                                                                                                          \
+    } while (0)
+// the bf16 fragment (8 columns) at logical chunk q of row `row` of an operand image
+#define DAG_SH_RD(buf, op, row, q) (*reinterpret_cast<const dag_bf16x8*>(lds + ((buf) * 2 + (op)) * IMG + (row) + 4 * ((q) ^ L.sw)))
+// The far stretch over the shadow.  Ad / Bd: dag_sh_src_far of the segment's first tile of each operand row; nkt K-steps of
+// 64 columns (two per tile).  Barriers and look-ahead as in dag_seg_bf16.
+__device__ __forceinline__ void dag_seg_bf16_sh(float* __restrict__ lds, const DagLane& L, const char* Ad, const char* Bd, int nkt,
+                                                f32x16& acc00, f32x16& acc01, f32x16& acc10, f32x16& acc11) {
+    typedef __attribute__((address_space(1))) const void* gptr_t;
+    typedef __attribute__((address_space(3))) void* lptr_t;
+    constexpr int IMG = NB * BK;
+#define DAG_CHUNK(buf, c)                                                                                          \
+    do {                                                                                                           \
+        const dag_bf16x8 a0 = DAG_SH_RD(buf, 0, L.arow, 2 * (c) + L.fh), a1 = DAG_SH_RD(buf, 0, L.arow + 32 * BK, 2 * (c) + L.fh); \
+        const dag_bf16x8 b0 = DAG_SH_RD(buf, 1, L.brow, 2 * (c) + L.fh), b1 = DAG_SH_RD(buf, 1, L.brow + 32 * BK, 2 * (c) + L.fh); \
+        acc00 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0, b0, acc00, 0, 0, 0);                                   \
+        acc01 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0, b1, acc01, 0, 0, 0);                                   \
+        acc10 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, b0, acc10, 0, 0, 0);                                   \
+        acc11 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, b1, acc11, 0, 0, 0);                                   \
+    } while (0)
+    DAG_SH_DMA(0, 0);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    for (int kt = 0; kt < nkt; ++kt) {
+        const int cur = kt & 1, nx = kt + 1;
+        if (nx < nkt) DAG_SH_DMA(cur ^ 1, (int64_t)(nx >> 1) * kShTile + (nx & 1) * kShHalf);      // the other buffer is free since the last barrier
+        DAG_CHUNK(cur, 0);
+        DAG_CHUNK(cur, 1);
+        DAG_CHUNK(cur, 2);
+        DAG_CHUNK(cur, 3);
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");        // this wave's DMA pieces of K-step kt+1 have landed ...
+        __syncthreads();                                        // ... everyone else's too; every read of K-step kt is back
+    }
+#undef DAG_CHUNK
+}
+// The middle stretch over the shadow.  Ad / Bd: dag_sh_src_mid; nkt K-steps of 32 columns (four per tile).  The twelve MFMAs
+// of a k-chunk in dag_seg_bf16x2's order.
+__device__ __forceinline__ void dag_seg_bf16x2_sh(float* __restrict__ lds, const DagLane& L, const char* Ad, const char* Bd, int nkt,
+                                                  f32x16& acc00, f32x16& acc01, f32x16& acc10, f32x16& acc11) {
+    typedef __attribute__((address_space(1))) const void* gptr_t;
+    typedef __attribute__((address_space(3))) void* lptr_t;
+    constexpr int IMG = NB * BK;
+#define DAG_CHUNK(buf, c)                                                                                          \
+    do {                                                                                                           \
+        const dag_bf16x8 a0 = DAG_SH_RD(buf, 0, L.arow, 2 * (c) + L.fh), a1 = DAG_SH_RD(buf, 0, L.arow + 32 * BK, 2 * (c) + L.fh); \
+        const dag_bf16x8 b0 = DAG_SH_RD(buf, 1, L.brow, 2 * (c) + L.fh), b1 = DAG_SH_RD(buf, 1, L.brow + 32 * BK, 2 * (c) + L.fh); \
+        const dag_bf16x8 a0l = DAG_SH_RD(buf, 0, L.arow, 4 + 2 * (c) + L.fh), a1l = DAG_SH_RD(buf, 0, L.arow + 32 * BK, 4 + 2 * (c) + L.fh); \
+        const dag_bf16x8 b0l = DAG_SH_RD(buf, 1, L.brow, 4 + 2 * (c) + L.fh), b1l = DAG_SH_RD(buf, 1, L.brow + 32 * BK, 4 + 2 * (c) + L.fh); \
+        acc00 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0l, b0, acc00, 0, 0, 0);                                  \
+        acc01 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0l, b1, acc01, 0, 0, 0);                                  \
+        acc10 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1l, b0, acc10, 0, 0, 0);                                  \
+        acc11 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1l, b1, acc11, 0, 0, 0);                                  \
+        acc00 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0, b0l, acc00, 0, 0, 0);                                  \
+        acc01 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0, b1l, acc01, 0, 0, 0);                                  \
+        acc10 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, b0l, acc10, 0, 0, 0);                                  \
+        acc11 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, b1l, acc11, 0, 0, 0);                                  \
+        acc00 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0, b0, acc00, 0, 0, 0);                                   \
+        acc01 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0, b1, acc01, 0, 0, 0);                                   \
+        acc10 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, b0, acc10, 0, 0, 0);                                   \
+        acc11 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, b1, acc11, 0, 0, 0);                                   \
+    } while (0)
+    DAG_SH_DMA(0, 0);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    for (int kt = 0; kt < nkt; ++kt) {
+        const int cur = kt & 1, nx = kt + 1;
+        if (nx < nkt) DAG_SH_DMA(cur ^ 1, (int64_t)(nx >> 2) * kShTile + ((nx >> 1) & 1) * kShHalf + (nx & 1) * 64);
+        DAG_CHUNK(cur, 0);
+        DAG_CHUNK(cur, 1);
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");        // this wave's DMA pieces of K-step kt+1 have landed ...
+        __syncthreads();                                        // ... everyone else's too; every read of K-step kt is back
+    }
+#undef DAG_CHUNK
+}
+#undef DAG_SH_DMA
+#undef DAG_SH_RD
+
+// The writer: the final tile held in the accumulators -> its two planes at `tile` (a shadow tile).  Through LDS, so that the
+// stores are coalesced 16-byte ones: a wave's 64 x 64 quadrant is 64 whole 128-byte rows of half wc of each plane, 8 KiB
+// contiguous in memory, and it stages them in the two 8 KiB pieces of the image that dag_acc_to_image gives the same wave
+// (disjoint between waves: no barrier, the wave's own LDS accesses complete in order).  Every element is rounded as the
+// in-loop variants round it: hi by v_cvt_pk_bf16_f32 (nearest even), lo = the same rounding of a - float(hi).  Stores are
+// write-through (`sc1`) like the epilogue's and are drained by the vmcnt(0) of the caller's dag_publish.  On entry no wave
+// reads or fills the LDS image; on return this wave's staging reads are complete.
+__device__ __forceinline__ void dag_shadow_store(float* __restrict__ lds, const DagLane& L, char* tile, const f32x16& acc00, const f32x16& acc01,
+                                                 const f32x16& acc10, const f32x16& acc11) {
+    constexpr int IMG = NB * BK;
+    unsigned short* hi = reinterpret_cast<unsigned short*>(lds + (L.wc * 2) * IMG + L.wr * (IMG / 2));
+    unsigned short* lo = reinterpret_cast<unsigned short*>(lds + (L.wc * 2 + 1) * IMG + L.wr * (IMG / 2));
+#define DAG_SH_PUT(ACC, i, j)                                                                           \
+    _Pragma("unroll") for (int e = 0; e < 16; ++e) {                                                    \
+        const int at = ((i) * 32 + (e & 3) + 8 * (e >> 2) + 4 * L.fh) * 64 + (j) * 32 + L.frow;         \
+        const float a = ACC[e];                                                                         \
+        const unsigned h = dag_pk_bf16(a, a);                                                           \
+        const float rest = a - __builtin_bit_cast(float, h << 16);                                      \
+        hi[at] = (unsigned short)h;                                                                     \
+        lo[at] = (unsigned short)dag_pk_bf16(rest, rest);                                               \
+    }
+    DAG_SH_PUT(acc00, 0, 0)
+    DAG_SH_PUT(acc01, 0, 1)
+    DAG_SH_PUT(acc10, 1, 0)
+    DAG_SH_PUT(acc11, 1, 1)
+#undef DAG_SH_PUT
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");          // (also keeps the compiler from moving the reads below over the 2-byte writes)
+    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void*)tile, (short)0, (int)kShTile, 0x00020000);
+    const int voff = L.wc * kShHalf + L.wr * (kShHalf / 2) + L.lane * 16;
+#pragma unroll
+    for (int n = 0; n < 8; ++n) {
+        const dag_u32x4 vh = *reinterpret_cast<const dag_u32x4*>(reinterpret_cast<const char*>(hi) + n * 1024 + L.lane * 16);
+        const dag_u32x4 vl = *reinterpret_cast<const dag_u32x4*>(reinterpret_cast<const char*>(lo) + n * 1024 + L.lane * 16);
+        __builtin_amdgcn_raw_buffer_store_b128(vh, rs, voff, n * 1024, 16);
+        __builtin_amdgcn_raw_buffer_store_b128(vl, rs, voff, kShPlane + n * 1024, 16);
+    }
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");          // the staging reads are back: the pieces may be rewritten
+}
+
 // The tile held in the accumulators becomes the operand image of a 128x128x128 product with ITSELF (the chain's rank-128
 // update L(j+1,j) L(j+1,j)^T): element (row r, column c) goes to K-step image c / 32 at the swizzled position the fragment reads
 // expect -- the four images fill the workgroup's LDS exactly -- and after a barrier every wave accumulates from LDS alone.
@@ -388,6 +549,8 @@ __device__ __forceinline__ const float* dag_src(const float* tile0, int64_t ld, 
 // kmid (wave-uniform, one scalar load from sy.mid per task, kfar <= kmid <= kend; no table: kfar): the block columns
 // kfar .. kmid - 1 are the row's MIDDLE stretch, split bf16 products (dag_seg_bf16x2); kmid .. kend - 1 run in fp32.
 // FAR = false ignores it too.
+// With a shadow (sy.shadow, "Shadow" above; FAR only) the far and / or middle segments (sy.shuse) read the operands' bf16
+// images instead, and a DAG_TILE task stores its tile's images in front of its publish.
 template <bool FAR>
 __device__ __forceinline__ bool dag_tile_task(const DagSys& sy, int kind, int k0, int kfar, int i, int j, DagCtl* ctl, float* lds, const DagLane& L,
                                               int* s_flag, int* s_kav, long long* tr /* thread 0, tracing: [2] += time spent polling */) {
@@ -399,6 +562,13 @@ __device__ __forceinline__ bool dag_tile_task(const DagSys& sy, int kind, int k0
     const float* Arow = sy.S + (int64_t)i * NB * sy.ld;
     const float* Brow = sy.S + (int64_t)j * NB * sy.ld;
     f32x16 acc00 = {0}, acc01 = {0}, acc10 = {0}, acc11 = {0};
+    // the operand rows' tiles in the shadow (tile k of row r: + k * kShTile), wave-uniform; null: the in-loop conversions
+    const char* shA = nullptr;
+    const char* shB = nullptr;
+    if (FAR && sy.shadow) {
+        shA = sy.shadow + sy.shrow[i] * kShTile;
+        shB = sy.shadow + sy.shrow[j] * kShTile;
+    }
     int kmid = kfar;
     if (FAR && sy.mid) {
         kmid = sy.mid[i];
@@ -421,12 +591,18 @@ __device__ __forceinline__ bool dag_tile_task(const DagSys& sy, int kind, int k0
         int kav = *s_kav;
         if (FAR && k < kfar) {                                  // a segment ends where the far stretch does
             kav = kav < kfar ? kav : kfar;
-            dag_seg_bf16(lds, L, dag_src(Arow + (int64_t)k * NB, sy.ld, L), sy.ld, dag_src(Brow + (int64_t)k * NB, sy.ld, L), sy.ld,
-                         (kav - k) * (NB / BK), acc00, acc01, acc10, acc11);
+            if (shA && (sy.shuse & 1))
+                dag_seg_bf16_sh(lds, L, dag_sh_src_far(shA + k * kShTile, L), dag_sh_src_far(shB + k * kShTile, L), (kav - k) * 2, acc00, acc01, acc10, acc11);
+            else
+                dag_seg_bf16(lds, L, dag_src(Arow + (int64_t)k * NB, sy.ld, L), sy.ld, dag_src(Brow + (int64_t)k * NB, sy.ld, L), sy.ld,
+                             (kav - k) * (NB / BK), acc00, acc01, acc10, acc11);
         } else if (FAR && k < kmid) {                           // ... and where the middle stretch does
             kav = kav < kmid ? kav : kmid;
-            dag_seg_bf16x2(lds, L, dag_src(Arow + (int64_t)k * NB, sy.ld, L), sy.ld, dag_src(Brow + (int64_t)k * NB, sy.ld, L), sy.ld,
-                           (kav - k) * (NB / BK), acc00, acc01, acc10, acc11);
+            if (shA && (sy.shuse & 2))
+                dag_seg_bf16x2_sh(lds, L, dag_sh_src_mid(shA + k * kShTile, L), dag_sh_src_mid(shB + k * kShTile, L), (kav - k) * 4, acc00, acc01, acc10, acc11);
+            else
+                dag_seg_bf16x2(lds, L, dag_src(Arow + (int64_t)k * NB, sy.ld, L), sy.ld, dag_src(Brow + (int64_t)k * NB, sy.ld, L), sy.ld,
+                               (kav - k) * (NB / BK), acc00, acc01, acc10, acc11);
         } else {
             dag_seg(lds, L, dag_src(Arow + (int64_t)k * NB, sy.ld, L), sy.ld, dag_src(Brow + (int64_t)k * NB, sy.ld, L), sy.ld, (kav - k) * (NB / BK),
                     acc00, acc01, acc10, acc11);
@@ -463,6 +639,7 @@ __device__ __forceinline__ bool dag_tile_task(const DagSys& sy, int kind, int k0
     dag_seg(lds, L, dag_src(Ct, sy.ld, L), sy.ld, dag_src(sy.tinv + (int64_t)j * NB * NB, NB, L), NB, NB / BK, acc00, acc01, acc10, acc11);
     if (t == 0) dag_drop_l1();                                  // this CU's L1 holds lines of X where L(i,j) is about to be
     dag_epilogue<false>(Cq, sy.ld, L, acc00, acc01, acc10, acc11);
+    if (FAR && sy.shadow) dag_shadow_store(lds, L, sy.shadow + (sy.shrow[i] + j) * kShTile, acc00, acc01, acc10, acc11);     // (the K-segment's last barrier is behind every wave)
     dag_publish(st + DAG_STATE_HDR + i, j + 1);
     return true;
 }
@@ -504,6 +681,7 @@ __device__ __forceinline__ void dag_chain_diag_body(const DagSys& sy, int j, int
 // stored and handed to LDS as an operand image, publish rowfin[j+1]; rank-128 update of (j+1,j+1) from LDS; poll
 // pre(j+1) only now (a dedicated chain: the flag has had the whole panel product to arrive); write the tile back for the
 // next block's waves.
+template <bool SH /* the launch may carry a shadow (every instantiation but the one that also solves) */>
 __device__ __forceinline__ bool dag_chain_panel(const DagSys& sy, int j, DagCtl* ctl, float* lds, const DagLane& L, int* s_flag, long long* ctr) {
     const int t = threadIdx.x;
     int* const st = sy.state;
@@ -513,6 +691,8 @@ __device__ __forceinline__ bool dag_chain_panel(const DagSys& sy, int j, DagCtl*
     dag_seg(lds, L, dag_src(Pt, sy.ld, L), sy.ld, dag_src(sy.tinv + (int64_t)j * NB * NB, NB, L), NB, NB / BK, acc00, acc01, acc10, acc11);
     if (t == 0) dag_drop_l1();                                  // L1 holds the tile as SUB(j) left it
     dag_epilogue<false>(Pt + (int64_t)(L.wr * 64) * sy.ld + L.wc * 64, sy.ld, L, acc00, acc01, acc10, acc11);
+    // the tile's shadow first: it stages in the very pieces of the image this wave fills next
+    if (SH && sy.shadow) dag_shadow_store(lds, L, sy.shadow + (sy.shrow[j + 1] + j) * kShTile, acc00, acc01, acc10, acc11);
     dag_acc_to_image(lds, L, acc00, acc01, acc10, acc11);
     dag_publish(st + DAG_STATE_HDR + j + 1, j + 1);             // rowfin[j+1] (its barrier: the image is complete)
     if (ctr && t == 0) ctr[8 * j + 3] = wall_clock64();
@@ -532,6 +712,7 @@ __device__ __forceinline__ bool dag_chain_panel(const DagSys& sy, int j, DagCtl*
 }
 
 // the chain of ONE system on a workgroup of its own (the systems with the most block rows: the launch ends with them)
+template <bool SH>
 __device__ __forceinline__ bool dag_chain_task(const DagSys& sy, DagCtl* ctl, int* info, float* lds, const DagLane& L, int* s_flag,
                                                long long* ctr /* tracing: [nb][8] stamps of this chain */, const struct DagSolve* sv) {
     const int t = threadIdx.x;
@@ -545,7 +726,7 @@ __device__ __forceinline__ bool dag_chain_task(const DagSys& sy, DagCtl* ctl, in
         if (t == 0 && j >= 1) ok = dag_wait_ge(sy.state + DAG_STATE_HDR + 2 * sy.nb + j, 1, ctl, L.spin);   // sub(j)
         if (ctr && t == 0) ctr[8 * j + 2] = wall_clock64();
         if (!dag_join(ok, s_flag)) return false;       // (its barrier: the diagonal-block waves' LDS reads are over)
-        if (!dag_chain_panel(sy, j, ctl, lds, L, s_flag, ctr)) return false;
+        if (!dag_chain_panel<SH>(sy, j, ctl, lds, L, s_flag, ctr)) return false;
     }
     __builtin_amdgcn_s_setprio(0);
     return true;
@@ -1085,7 +1266,7 @@ __global__ __launch_bounds__(256, 2) void potrf_dag_kernel(const DagSys* __restr
             dag_lane_coords(L, tt);
             if (ready_task) ok = dag_fwd_row_task(sy, task.z, sv, ctl, lds);
             else if ((task.x & 255) == DAG_CHAIN)
-                ok = dag_chain_task(sy, ctl, info, lds, L, &s_flag, trace ? trace + 4 * (int64_t)(ntasks + sv.qcap) + 8 * (int64_t)task.z : nullptr, &sv);
+                ok = dag_chain_task<true>(sy, ctl, info, lds, L, &s_flag, trace ? trace + 4 * (int64_t)(ntasks + sv.qcap) + 8 * (int64_t)task.z : nullptr, &sv);
             else ok = dag_tile_task<true>(sy, task.x & 255, (task.x >> 8) & 1023, task.x >> 18, task.z, task.w, ctl, lds, L, &s_flag, &s_kav, tr);
         } else if (ready_task) {
             const SolveMember mb = sv.mem[task.y];
@@ -1095,7 +1276,7 @@ __global__ __launch_bounds__(256, 2) void potrf_dag_kernel(const DagSys* __restr
             else if (sv.dtype == OISAT_F32) ok = dag_inc_task<float>(sy, mb, task.z, task.w, sv, ctl, lds);
             else ok = dag_inc_task<double>(sy, mb, task.z, task.w, sv, ctl, lds);
         } else if ((task.x & 255) == DAG_CHAIN) {
-            ok = dag_chain_task(sy, ctl, info, lds, L, &s_flag, trace ? trace + 4 * (int64_t)(ntasks + (SOLVE ? sv.qcap : 0)) + 8 * (int64_t)task.z : nullptr,
+            ok = dag_chain_task<SOLVE != DAG_SOLVE_ALL>(sy, ctl, info, lds, L, &s_flag, trace ? trace + 4 * (int64_t)(ntasks + (SOLVE ? sv.qcap : 0)) + 8 * (int64_t)task.z : nullptr,
                                 SOLVE ? &sv : (const DagSolve*)nullptr);
         } else {
             ok = dag_tile_task<SOLVE != DAG_SOLVE_ALL>(sy, task.x & 255, (task.x >> 8) & 1023, task.x >> 18, task.z, task.w, ctl, lds, L, &s_flag,
@@ -1167,6 +1348,9 @@ struct DagPlan {
     std::vector<int> far;                                       // ... and its far stretch (oisat_factor_far; no stretch: equal to first)
     std::vector<int> mid;                                       // ... and its middle stretch (oisat_factor_mid; no stretch: equal to far)
     int* mid_dev = nullptr;                                     // the device copy of mid (an enveloped plan's int32[nb]); DagSys::mid points here while a stretch exists
+    std::vector<int64_t> shrow;                                 // the shadow's row table of `first`: rowoff[r] - first[r] (dag_shadow_layout), and its device copy
+    int64_t* shrow_dev = nullptr;
+    int64_t sh_tiles = 0;                                       // tiles of that shadow: sum of r - first[r]
     size_t tasks_cap = 0;                                       // tickets tasks_dev holds (an enveloped plan: the dense list's, so a new envelope refills it)
     long long* trace_dev = nullptr;                             // OISAT_DAG_TRACE: [ntasks][4] + [chain_rows][8] stamps of the last launch
 };
@@ -1179,6 +1363,7 @@ void dag_plan_free(DagPlan* p) {
     if (p->ctl_dev) (void)hipFree(p->ctl_dev);
     if (p->queue_dev) (void)hipFree(p->queue_dev);
     if (p->mid_dev) (void)hipFree(p->mid_dev);
+    if (p->shrow_dev) (void)hipFree(p->shrow_dev);
     if (p->trace_dev) (void)hipFree(p->trace_dev);
     delete p;
 }
@@ -1368,6 +1553,40 @@ static hipError_t dag_plan_mid(DagPlan& p, const int* mid, hipStream_t stream) {
     return hipMemcpyAsync(p.sys_dev, p.sys_host.data(), sizeof(DagSys), hipMemcpyHostToDevice, stream);
 }
 
+// The shadow's addressing (oisat_factor_shadow_layout): the strictly-lower tiles (r, k), first[r] <= k < r, row after row;
+// rowoff[r] = tiles of the rows above r, tile (r, k) is number rowoff[r] + (k - first[r]).  Returns the number of tiles.
+static int64_t dag_shadow_layout(const int* first, int64_t nb, int64_t* rowoff) {
+    int64_t n = 0;
+    for (int64_t r = 0; r < nb; ++r) {
+        rowoff[r] = n;
+        n += r - first[r];
+    }
+    return n;
+}
+
+// ... of an enveloped plan's `first`, to the device (at creation and with every new envelope; the caller has synchronised as
+// for dag_plan_mid).  Whether a launch HAS a shadow is decided per call: dag_plan_shadow.
+static hipError_t dag_plan_shrow(DagPlan& p, hipStream_t stream) {
+    const size_t nb = p.first.size();
+    p.shrow.resize(nb);
+    p.sh_tiles = dag_shadow_layout(p.first.data(), (int64_t)nb, p.shrow.data());
+    for (size_t r = 0; r < nb; ++r) p.shrow[r] -= p.first[r];
+    return hipMemcpyAsync(p.shrow_dev, p.shrow.data(), sizeof(int64_t) * nb, hipMemcpyHostToDevice, stream);
+}
+
+// This call's shadow (null: none) and its readers (DagSys::shuse) into the plan's system; a change waits for the launches
+// that read the system's words as they are.
+static hipError_t dag_plan_shadow(DagPlan& p, char* shadow, int use, hipStream_t stream) {
+    DagSys& sy = p.sys_host[0];
+    const int64_t* want = shadow ? p.shrow_dev : nullptr;
+    if (sy.shadow == shadow && sy.shrow == want && sy.shuse == use) return hipSuccess;
+    if (hipError_t e = hipStreamSynchronize(stream)) return e;
+    sy.shadow = shadow;
+    sy.shrow = want;
+    sy.shuse = use;
+    return hipMemcpyAsync(p.sys_dev, p.sys_host.data(), sizeof(DagSys), hipMemcpyHostToDevice, stream);
+}
+
 // systems in table order (largest first)
 // The progress words and the control block are zeroed ON `stream` (the stream the plan's launches go to): a plain hipMemset is
 // ordered in the NULL stream only, which the handles' non-blocking streams do not wait for -- a launch could start on
@@ -1421,6 +1640,7 @@ DagPlan* dag_plan_create(const std::vector<BatchMat>& table, hipStream_t stream,
               hipMalloc((void**)&p->state_dev, sizeof(int) * words) == hipSuccess &&
               hipMalloc((void**)&p->ctl_dev, sizeof(DagCtl)) == hipSuccess &&
               (p->first.empty() || hipMalloc((void**)&p->mid_dev, sizeof(int) * p->first.size()) == hipSuccess) &&
+              (p->first.empty() || hipMalloc((void**)&p->shrow_dev, sizeof(int64_t) * p->first.size()) == hipSuccess) &&
               (p->qcap == 0 || (p->qcap < (int64_t)INT32_MAX / 4 && hipMalloc((void**)&p->queue_dev, 16 * (size_t)p->qcap) == hipSuccess));
     if (ok && p->qcap > 0) ok = hipMemsetAsync(p->queue_dev, 0, 16 * (size_t)p->qcap, stream) == hipSuccess;
     if (ok) {
@@ -1430,7 +1650,7 @@ DagPlan* dag_plan_create(const std::vector<BatchMat>& table, hipStream_t stream,
              hipMemcpy(p->tasks_dev, tasks.data(), sizeof(int4) * tasks.size(), hipMemcpyHostToDevice) == hipSuccess &&
              hipMemsetAsync(p->state_dev, 0, sizeof(int) * words, stream) == hipSuccess &&
              hipMemsetAsync(p->ctl_dev, 0, sizeof(DagCtl), stream) == hipSuccess;
-        if (ok && !p->first.empty()) ok = dag_plan_mid(*p, mid, stream) == hipSuccess;
+        if (ok && !p->first.empty()) ok = dag_plan_mid(*p, mid, stream) == hipSuccess && dag_plan_shrow(*p, stream) == hipSuccess;
     }
     if (!ok) {
         dag_plan_free(p);
@@ -1461,6 +1681,7 @@ int dag_plan_refill(DagPlan& p, const int* first, const int* far, const int* mid
     if (p.trace_dev) { (void)hipFree(p.trace_dev); p.trace_dev = nullptr; }      // (profiling aid: sized by the ticket count)
     HIP_TRY(hipMemcpyAsync(p.tasks_dev, p.tasks_host.data(), sizeof(int4) * p.tasks_host.size(), hipMemcpyHostToDevice, stream));
     HIP_TRY(dag_plan_mid(p, mid, stream));
+    HIP_TRY(dag_plan_shrow(p, stream));
     return OISAT_OK;
 }
 

@@ -122,8 +122,8 @@ struct oisat_ctx {
     std::vector<ProfPending> pending;
     std::vector<hipEvent_t> free_events;
     // grow-only device workspaces (never freed/reallocated inside a timed region once warm)
-    void* ws[10] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    size_t ws_bytes[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    void* ws[11] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    size_t ws_bytes[11] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
     // last scaling sweep uploaded into workspace slot 0 (oi_diag.hip)
     double scales_host[OISAT_MAX_SCALES] = {0};
     int scales_n = 0;
@@ -147,6 +147,11 @@ struct oisat_ctx {
     int64_t obs_perm_m = 0;
     std::vector<int32_t> factor_far;    // oisat_set_factor_far: the far stretch of the NEXT enveloped factorization (one-shot)
     std::vector<int32_t> factor_mid;    // oisat_set_factor_mid: ... and its middle stretch (one-shot)
+    // the factor's shadow (dense_dag.inc "Shadow": bf16 images of the final tiles, workspace slot 10)
+    int64_t shadow_cap = -1;            // oisat_set_factor_shadow_cap: most bytes it may take, -1 = no limit
+    const char* shadow_last = nullptr;  // the shadow the last factorization on this handle filled (nullptr: it had none) ...
+    std::vector<int32_t> shadow_first;  // ... its envelope ...
+    std::vector<int64_t> shadow_shrow;  // ... and its row table, rowoff[r] - first[r] (oisat_factor_shadow_tile)
     int dag_mode = -1;                  // oisat_set_task_graph: -1 = by size (and OISAT_DAG), 0 = recursion only, 1 = task graph wherever it applies
     DagSingle dag_cache[8];
     uint64_t dag_clock = 0;

@@ -52,8 +52,8 @@ extern "C" void oisat_shutdown(oisat_ctx* h) {
         (void)hipEventDestroy(p.b);
     }
     for (auto ev : h->free_events) (void)hipEventDestroy(ev);
-    for (int i = 0; i < 10; ++i)
-        if (h->ws[i]) (void)hipFree(h->ws[i]);
+    for (void* w : h->ws)
+        if (w) (void)hipFree(w);
     if (h->pinned) (void)hipHostFree(h->pinned);
     if (h->own_stream) (void)hipStreamDestroy(h->own_stream);
     if (h->aux_stream) (void)hipStreamDestroy(h->aux_stream);

@@ -102,6 +102,9 @@ SIGNATURES = {
     "oisat_set_factor_far": (C.c_int, [_ptr, _ptr, _i64]),
     "oisat_factor_mid": (C.c_int, [_ptr, _i64, C.c_double, _ptr, _ptr, _ptr]),
     "oisat_set_factor_mid": (C.c_int, [_ptr, _ptr, _i64]),
+    "oisat_factor_shadow_layout": (C.c_int, [C.c_int, _ptr, _ptr, C.POINTER(_i64)]),
+    "oisat_set_factor_shadow_cap": (C.c_int, [_c_ctx, _i64]),
+    "oisat_factor_shadow_tile": (C.c_int, [_c_ctx, C.c_int, C.c_int, _ptr, _ptr]),
     "oisat_set_correlation": (C.c_int, [_c_ctx, C.c_int]),
     "oisat_corr_eval": (C.c_int, [C.c_int, C.c_double, _ptr, _i64, _ptr]),
     "oisat_corr_cut_chord": (C.c_int, [C.c_int, C.c_double, C.c_double, C.POINTER(C.c_double)]),
