@@ -103,6 +103,8 @@ __device__ __forceinline__ int64_t xcd_chunk_remap(int64_t v, int64_t total) {
     return (g << 9) + (x << 6) + sidx;
 }
 
+#include "dense_kloop.inc"                                      // (dag_seg: the K-loop below as a function, for dense_dag.inc)
+
 // ---- gemm_nt_big: one tile per workgroup, for K >= 2048 --------------------------------------------------------------
 // The kernel the headline factorization spends 95 % of its time in (round 1's gemm_nt, unchanged): with 64+ K-steps per
 // tile the 22 us of per-tile overhead are < 10 %, and this instruction schedule of the K-loop sustains 140 TFLOP/s at
@@ -2269,14 +2271,19 @@ static int factor_shadow_mode() {
     return -1;
 }
 
-// first / env_dev: nullptr (dense), or the envelope of S (host: first[mpb]; device: first[mpb] | last[mpb], oisat_envelope)
+struct PotrfEnv {                // the envelope of S and its stretches; all null: dense
+    const int32_t* first = nullptr;     // host first[mpb] ...
+    const int32_t* env_dev = nullptr;   // ... and device first[mpb] | last[mpb] (oisat_envelope)
+    const int32_t* far = nullptr;       // host int32[mpb], with first, or null: the far stretch of every block row (oisat_factor_far), bf16 K-blocks in the task graph
+    const int32_t* mid = nullptr;       // likewise: the middle stretch behind it (oisat_factor_mid), split bf16 K-blocks
+};
 // fwd_d (device double[m]) or nullptr: the right-hand side whose first forward sweep rides in the task-graph launch
 // (oisat_potrf_env_fwd).  schedule_out (optional): OISAT_SCHEDULE_* of what ran.
-// far (host int32[mpb], with first) or nullptr: the far stretch of every block row (oisat_factor_far), bf16 K-blocks in the task graph
-// mid (likewise) or nullptr: the middle stretch behind it (oisat_factor_mid), split bf16 K-blocks
-static int potrf_impl(oisat_ctx* h, float* S, int64_t m, int64_t ld, int* info_host, const int32_t* first, const int32_t* env_dev,
-                      const double* fwd_d = nullptr, int* schedule_out = nullptr, const int32_t* far = nullptr, const int32_t* mid = nullptr) {
+static int potrf_impl(oisat_ctx* h, float* S, int64_t m, int64_t ld, int* info_host, const PotrfEnv& env, const double* fwd_d = nullptr,
+                      int* schedule_out = nullptr) {
     ARG_CHECK(h && S && m > 0);
+    const int32_t* const first = env.first;
+    const int32_t* const env_dev = env.env_dev;
     h->factor.fwd_d = nullptr;                                  // whatever comes of this call, the last factor's forward vector is history
     h->shadow_last = nullptr;                                   // ... and so is its shadow
     if (schedule_out) *schedule_out = OISAT_SCHEDULE_OTHER;
@@ -2316,13 +2323,8 @@ static int potrf_impl(oisat_ctx* h, float* S, int64_t m, int64_t ld, int* info_h
         DagSingle* hit = nullptr;
         for (DagSingle& c : h->dag_cache)
             if (c.plan && c.S == S && c.tinv == tinv && c.ld == ld && c.mpb == mpb && c.enveloped == (first != nullptr) && c.fwd == ride) hit = &c;
-        if (hit && first) {
-            DagPlan& pl = *(DagPlan*)hit->plan;
-            if (memcmp(pl.first.data(), first, sizeof(int) * (size_t)mpb) != 0 ||
-                memcmp(pl.far.data(), far ? far : first, sizeof(int) * (size_t)mpb) != 0 ||
-                memcmp(pl.mid.data(), mid ? mid : far ? far : first, sizeof(int) * (size_t)mpb) != 0)
-                if (int rf = dag_plan_refill(pl, first, far, mid, h->stream)) return rf;
-        }
+        if (hit && first && !((DagPlan*)hit->plan)->bands.equals((size_t)mpb, first, env.far, env.mid))
+            if (int rf = dag_plan_refill(*(DagPlan*)hit->plan, DagBands((int)mpb, first, env.far, env.mid), h->stream)) return rf;
         if (!hit) {
             DagSingle* slot = nullptr;
             for (DagSingle& c : h->dag_cache)
@@ -2340,8 +2342,8 @@ static int potrf_impl(oisat_ctx* h, float* S, int64_t m, int64_t ld, int* info_h
                 shape.refine = 0;
                 shape.fwd_only = true;
             }
-            slot->plan = dag_plan_create(std::vector<BatchMat>{BatchMat{S, tinv, ld, m, (int)mpb, 0}}, h->stream, shape, first, first ? far : nullptr,
-                                         first ? mid : nullptr);
+            slot->plan = dag_plan_create(std::vector<BatchMat>{BatchMat{S, tinv, ld, m, (int)mpb, 0}}, h->stream, shape,
+                                         first ? DagBands((int)mpb, first, env.far, env.mid) : DagBands());
             if (!slot->plan) return OISAT_ENOMEM;
             slot->S = S; slot->tinv = tinv; slot->ld = ld; slot->mpb = mpb; slot->enveloped = first != nullptr; slot->fwd = ride;
             hit = slot;
@@ -2353,11 +2355,11 @@ static int potrf_impl(oisat_ctx* h, float* S, int64_t m, int64_t ld, int* info_h
         // oisat_set_factor_shadow_cap allows): the launch converts in its K-loops as before, the same bits; that is not an error.
         char* shadow = nullptr;
         int shadow_use = 0;
-        if (first && (far || mid)) {
+        if (first && (env.far || env.mid)) {
             const int mode = factor_shadow_mode();
             ARG_CHECK(mode >= 0 && "OISAT_FACTOR_SHADOW is 0, 1, far or mid");
             bool any = false;
-            for (int64_t b = 0; b < mpb; ++b) any = any || pl.mid[b] > pl.first[b];
+            for (int64_t b = 0; b < mpb; ++b) any = any || pl.bands.mid[b] > pl.bands.first[b];
             const size_t bytes = (size_t)pl.sh_tiles * (size_t)kShTile;
             if (mode > 0 && any && (h->shadow_cap < 0 || bytes <= (size_t)h->shadow_cap)) {
                 shadow = (char*)oisat_ws(h, 10, bytes);
@@ -2392,7 +2394,7 @@ static int potrf_impl(oisat_ctx* h, float* S, int64_t m, int64_t ld, int* info_h
         if (schedule_out) *schedule_out = !first ? OISAT_SCHEDULE_OTHER : ride ? OISAT_SCHEDULE_ENV_DAG_FWD : OISAT_SCHEDULE_ENV_DAG;
         if (rc == OISAT_OK && shadow) {                         // what oisat_factor_shadow_tile reads back
             h->shadow_last = shadow;
-            h->shadow_first = pl.first;
+            h->shadow_first = pl.bands.first;
             h->shadow_shrow = pl.shrow;
         }
     } else {
@@ -2433,7 +2435,7 @@ static int potrf_impl(oisat_ctx* h, float* S, int64_t m, int64_t ld, int* info_h
 }
 
 extern "C" int oisat_potrf(oisat_ctx* h, float* S, int64_t m, int64_t ld, int* info_host) {
-    return potrf_impl(h, S, m, ld, info_host, nullptr, nullptr);
+    return potrf_impl(h, S, m, ld, info_host, PotrfEnv{});
 }
 
 // OISAT_ENVELOPE=0: the enveloped entry points behave as their dense counterparts (A/B timing, tests); read at every call
@@ -2490,9 +2492,32 @@ static int64_t envelope_ksteps(const int32_t* first, int64_t nb) {
 
 static bool corr_kind_ok(int kind) { return kind == OISAT_CORR_GAUSSIAN || kind == OISAT_CORR_GASPARI_COHN; }
 
+static bool lat_sorted_ok(const double* lat_sorted, int64_t m) {
+    for (int64_t i = 1; i < m; ++i)
+        if (!(lat_sorted[i] >= lat_sorted[i - 1])) return false;
+    return true;
+}
+
+// <n> bits from the environment variable `name` (read at every call, like OISAT_ENVELOPE): lo <= n <= kCutBits into *bits and
+// *set = true; unset or empty: *bits stays
+static int env_bits(const char* name, double lo, double* bits, bool* set) {
+    const char* e = getenv(name);
+    *set = e && *e;
+    if (!*set) return OISAT_OK;
+    char* end = nullptr;
+    *bits = strtod(e, &end);
+    ARG_CHECK(end != e && *end == '\0' && *bits >= lo && *bits <= kCutBits);
+    return OISAT_OK;
+}
+
+// the default rule (kFactorMinKstepsPerRow): the narrow table `first` pays
+static bool narrow_table_pays(const int32_t* first, int64_t nb) {
+    return (double)envelope_ksteps(first, nb) > kFactorMinKstepsPerRow * (double)nb;
+}
+
 extern "C" int oisat_envelope_corr(int kind, const double* lat_sorted, int64_t m, double g, int32_t* env_out) {
     ARG_CHECK(corr_kind_ok(kind) && lat_sorted && env_out && m > 0 && g >= 0.0);
-    for (int64_t i = 1; i < m; ++i) ARG_CHECK(lat_sorted[i] >= lat_sorted[i - 1]);
+    ARG_CHECK(lat_sorted_ok(lat_sorted, m));
     envelope_table(kind, lat_sorted, m, g, kCutBits, env_out);  // the same cut-off as the float64 residual and the increment
     return OISAT_OK;
 }
@@ -2507,20 +2532,13 @@ extern "C" int oisat_envelope(const double* lat_sorted, int64_t m, double g, int
 // its far table is empty (far = first).  The two environment variables still force their rules, through cut_chord.
 extern "C" int oisat_factor_envelope_corr(int kind, const double* lat_sorted, int64_t m, double g, int32_t* env_out) {
     ARG_CHECK(corr_kind_ok(kind) && lat_sorted && env_out && m > 0 && g >= 0.0);
-    for (int64_t i = 1; i < m; ++i) ARG_CHECK(lat_sorted[i] >= lat_sorted[i - 1]);
+    ARG_CHECK(lat_sorted_ok(lat_sorted, m));
     double bits = kFactorCutBits;
     bool forced = false;
-    const char* e = getenv("OISAT_FACTOR_CUT_BITS");            // read at every call, like OISAT_ENVELOPE
-    if (e && *e) {
-        char* end = nullptr;
-        bits = strtod(e, &end);
-        ARG_CHECK(end != e && *end == '\0' && bits >= 1.0 && bits <= kCutBits);
-        forced = true;
-    }
-    const int64_t nb = cdiv(m, NB);
+    if (int rc = env_bits("OISAT_FACTOR_CUT_BITS", 1.0, &bits, &forced)) return rc;
     if (kind == OISAT_CORR_GASPARI_COHN && !forced) bits = kCutBits;
     envelope_table(kind, lat_sorted, m, g, bits, env_out);
-    if (kind == OISAT_CORR_GAUSSIAN && !forced && (double)envelope_ksteps(env_out, nb) <= kFactorMinKstepsPerRow * (double)nb)
+    if (kind == OISAT_CORR_GAUSSIAN && !forced && !narrow_table_pays(env_out, cdiv(m, NB)))
         envelope_table(kind, lat_sorted, m, g, kCutBits, env_out);     // chain-bound: nothing to win, keep the float64 sums' table
     return OISAT_OK;
 }
@@ -2544,36 +2562,37 @@ extern "C" int oisat_factor_envelope(const double* lat_sorted, int64_t m, double
 // potrf_dag 84.0 -> 67.2 ms, the step 100.6 -> 83.8 ms.
 constexpr double kFactorFarBits = 18.0;
 
-extern "C" int oisat_factor_far_corr(int kind, const double* lat_sorted, int64_t m, double g, const int32_t* first, int32_t* far_out) {
-    ARG_CHECK(corr_kind_ok(kind) && lat_sorted && first && far_out && m > 0 && g >= 0.0);
-    for (int64_t i = 1; i < m; ++i) ARG_CHECK(lat_sorted[i] >= lat_sorted[i - 1]);
+// A stretch of the factor's K-loops as a table: out[i] = the table of cut-off 2^-bits clamped into [lower[i], i] -- lower: the table
+// below it, `first` for the far stretch, `far` for the middle one -- or lower[i] where the stretch is off.  bits: `def` under the
+// default rule -- on exactly where the narrow table is: Gaussian, tile-work-bound, no forced OISAT_FACTOR_CUT_BITS --, or the <n>
+// of the variable `var`: 0 = off, 1 .. 52 forces 2^-n at every enveloped size.  Never on under OISAT_ENVELOPE=0.
+static int stretch_table(const char* var, double def, int kind, const double* lat_sorted, int64_t m, double g, const int32_t* lower, int32_t* out) {
     const int64_t nb = cdiv(m, NB);
-    ARG_CHECK(envelope_table_ok(first, nb));
-    double bits = kFactorFarBits;
-    bool on = false;
-    const char* e = getenv("OISAT_FACTOR_FAR_BITS");
-    if (e && *e) {
-        char* end = nullptr;
-        bits = strtod(e, &end);
-        ARG_CHECK(end != e && *end == '\0' && bits >= 0.0 && bits <= kCutBits);
+    double bits = def;
+    bool on = false, forced = false;
+    if (int rc = env_bits(var, 0.0, &bits, &forced)) return rc;
+    std::vector<int32_t> t(2 * (size_t)nb);
+    if (forced) {
         on = bits >= 1.0;
         ARG_CHECK(on || bits == 0.0);
     } else {
         const char* c = getenv("OISAT_FACTOR_CUT_BITS");
         if (!(c && *c) && kind == OISAT_CORR_GAUSSIAN) {        // the default rule's own choice: the narrow table, or not
-            std::vector<int32_t> narrow(2 * (size_t)nb);
-            envelope_table(kind, lat_sorted, m, g, kFactorCutBits, narrow.data());
-            on = (double)envelope_ksteps(narrow.data(), nb) > kFactorMinKstepsPerRow * (double)nb;
+            envelope_table(kind, lat_sorted, m, g, kFactorCutBits, t.data());
+            on = narrow_table_pays(t.data(), nb);
         }
     }
-    if (on && !oisat_envelope_off()) {
-        std::vector<int32_t> t(2 * (size_t)nb);
-        envelope_table(kind, lat_sorted, m, g, bits, t.data());
-        for (int64_t i = 0; i < nb; ++i) far_out[i] = std::min<int32_t>(std::max(t[i], first[i]), (int32_t)i);
-    } else {
-        for (int64_t i = 0; i < nb; ++i) far_out[i] = first[i];
-    }
+    on = on && !oisat_envelope_off();
+    if (on) envelope_table(kind, lat_sorted, m, g, bits, t.data());
+    for (int64_t i = 0; i < nb; ++i) out[i] = on ? std::min<int32_t>(std::max(t[i], lower[i]), (int32_t)i) : lower[i];
     return OISAT_OK;
+}
+
+extern "C" int oisat_factor_far_corr(int kind, const double* lat_sorted, int64_t m, double g, const int32_t* first, int32_t* far_out) {
+    ARG_CHECK(corr_kind_ok(kind) && lat_sorted && first && far_out && m > 0 && g >= 0.0);
+    ARG_CHECK(lat_sorted_ok(lat_sorted, m));
+    ARG_CHECK(envelope_table_ok(first, cdiv(m, NB)));
+    return stretch_table("OISAT_FACTOR_FAR_BITS", kFactorFarBits, kind, lat_sorted, m, g, first, far_out);
 }
 
 extern "C" int oisat_factor_far(const double* lat_sorted, int64_t m, double g, const int32_t* first, int32_t* far_out) {
@@ -2617,35 +2636,11 @@ constexpr double kFactorMidBits = 8.0;
 extern "C" int oisat_factor_mid_corr(int kind, const double* lat_sorted, int64_t m, double g, const int32_t* first, const int32_t* far,
                                      int32_t* mid_out) {
     ARG_CHECK(corr_kind_ok(kind) && lat_sorted && first && far && mid_out && m > 0 && g >= 0.0);
-    for (int64_t i = 1; i < m; ++i) ARG_CHECK(lat_sorted[i] >= lat_sorted[i - 1]);
+    ARG_CHECK(lat_sorted_ok(lat_sorted, m));
     const int64_t nb = cdiv(m, NB);
     ARG_CHECK(envelope_table_ok(first, nb));
     for (int64_t i = 0; i < nb; ++i) ARG_CHECK(far[i] >= first[i] && far[i] <= i);
-    double bits = kFactorMidBits;
-    bool on = false;
-    const char* e = getenv("OISAT_FACTOR_MID_BITS");
-    if (e && *e) {
-        char* end = nullptr;
-        bits = strtod(e, &end);
-        ARG_CHECK(end != e && *end == '\0' && bits >= 0.0 && bits <= kCutBits);
-        on = bits >= 1.0;
-        ARG_CHECK(on || bits == 0.0);
-    } else {
-        const char* c = getenv("OISAT_FACTOR_CUT_BITS");
-        if (!(c && *c) && kind == OISAT_CORR_GAUSSIAN) {        // the far stretch's default rule
-            std::vector<int32_t> narrow(2 * (size_t)nb);
-            envelope_table(kind, lat_sorted, m, g, kFactorCutBits, narrow.data());
-            on = (double)envelope_ksteps(narrow.data(), nb) > kFactorMinKstepsPerRow * (double)nb;
-        }
-    }
-    if (on && !oisat_envelope_off()) {
-        std::vector<int32_t> t(2 * (size_t)nb);
-        envelope_table(kind, lat_sorted, m, g, bits, t.data());
-        for (int64_t i = 0; i < nb; ++i) mid_out[i] = std::min<int32_t>(std::max(t[i], far[i]), (int32_t)i);
-    } else {
-        for (int64_t i = 0; i < nb; ++i) mid_out[i] = far[i];
-    }
-    return OISAT_OK;
+    return stretch_table("OISAT_FACTOR_MID_BITS", kFactorMidBits, kind, lat_sorted, m, g, far, mid_out);
 }
 
 extern "C" int oisat_factor_mid(const double* lat_sorted, int64_t m, double g, const int32_t* first, const int32_t* far, int32_t* mid_out) {
@@ -2709,32 +2704,29 @@ extern "C" int oisat_dag_task_order_env(int nb, const int32_t* first, const int3
     return OISAT_OK;
 }
 
-extern "C" int oisat_potrf_env(oisat_ctx* h, float* S, int64_t m, int64_t ld, const int32_t* first, const int32_t* env_dev,
-                               int* info_host) {
+// the two enveloped entry points: fwd = oisat_potrf_env_fwd, whose d is required
+static int potrf_env_entry(oisat_ctx* h, float* S, int64_t m, int64_t ld, const int32_t* first, const int32_t* env_dev, bool fwd, const double* d,
+                           int* info_host, int* schedule_out) {
     ARG_CHECK(h != nullptr);
     std::vector<int32_t> far, mid;
     far.swap(h->factor_far);                                    // one-shot, whatever this call's outcome
     mid.swap(h->factor_mid);                                    // likewise
-    ARG_CHECK(first && env_dev && m > 0);
+    ARG_CHECK(first && env_dev && (!fwd || d) && m > 0);
     ARG_CHECK(envelope_table_ok(first, cdiv(m, NB)) && far_table_ok(far, first, cdiv(m, NB)) &&
               mid_table_ok(mid, far, first, cdiv(m, NB)));
-    if (oisat_envelope_off()) return potrf_impl(h, S, m, ld, info_host, nullptr, nullptr);
-    return potrf_impl(h, S, m, ld, info_host, first, env_dev, nullptr, nullptr, far.empty() ? nullptr : far.data(),
-                      mid.empty() ? nullptr : mid.data());
+    PotrfEnv env;
+    if (!oisat_envelope_off()) env = PotrfEnv{first, env_dev, far.empty() ? nullptr : far.data(), mid.empty() ? nullptr : mid.data()};
+    return potrf_impl(h, S, m, ld, info_host, env, d, schedule_out);
+}
+
+extern "C" int oisat_potrf_env(oisat_ctx* h, float* S, int64_t m, int64_t ld, const int32_t* first, const int32_t* env_dev,
+                               int* info_host) {
+    return potrf_env_entry(h, S, m, ld, first, env_dev, false, nullptr, info_host, nullptr);
 }
 
 extern "C" int oisat_potrf_env_fwd(oisat_ctx* h, float* S, int64_t m, int64_t ld, const int32_t* first, const int32_t* env_dev,
                                    const double* d, int* info_host, int* schedule_out) {
-    ARG_CHECK(h != nullptr);
-    std::vector<int32_t> far, mid;
-    far.swap(h->factor_far);                                    // one-shot, whatever this call's outcome
-    mid.swap(h->factor_mid);                                    // likewise
-    ARG_CHECK(first && env_dev && d && m > 0);
-    ARG_CHECK(envelope_table_ok(first, cdiv(m, NB)) && far_table_ok(far, first, cdiv(m, NB)) &&
-              mid_table_ok(mid, far, first, cdiv(m, NB)));
-    if (oisat_envelope_off()) return potrf_impl(h, S, m, ld, info_host, nullptr, nullptr, d, schedule_out);
-    return potrf_impl(h, S, m, ld, info_host, first, env_dev, d, schedule_out, far.empty() ? nullptr : far.data(),
-                      mid.empty() ? nullptr : mid.data());
+    return potrf_env_entry(h, S, m, ld, first, env_dev, true, d, info_host, schedule_out);
 }
 
 extern "C" int oisat_potrs(oisat_ctx* h, const float* L, int64_t m, int64_t ld, double* z_inout) {

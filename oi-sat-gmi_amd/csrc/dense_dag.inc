@@ -65,14 +65,6 @@ struct DagCtl {                  // zero when a launch starts
     int cu_role[DAG_CU_KEYS];            // what the FIRST workgroup of a CU drew: 1 = bulk task, 2 = a chain that wants its CU alone
 };
 
-struct DagLane {                 // a thread's fixed coordinates in the 128x128 tile GEMM (as in gemm_nt_big_kernel)
-    int lane, wid, wr, wc, rl, lc, frow, fh, sw, arow, brow;
-    int flags;                   // 0 in the product.  Only the -DOISAT_TEST_HOOKS build of the library (liboisat_hip_testhooks.so, loaded
-                                 // by tests/test_gpu_dag.py alone) reads OISAT_DAG_FLAGS: 128 = fault injection -- no chain announces a
-                                 // diagonal block from block 3 on (the waiters time out); 256 = polls give up after 4096 spins
-    unsigned spin;               // polls before a wait gives up (kDagSpinMax)
-};
-
 // thread 0: wait until *p >= v (agent-scope polls); false = time-out or another workgroup's error
 __device__ __forceinline__ bool dag_wait_ge(const int* p, int v, DagCtl* ctl, unsigned spin_max) {
     unsigned spins = 0;
@@ -127,63 +119,6 @@ __device__ __forceinline__ void dag_publish(int* p, int v) {
     if (threadIdx.x == 0) __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
-#define DAG_MFMA4(A0, A1, B0, B1, c)                                                            \
-    acc00 = __builtin_amdgcn_mfma_f32_32x32x2f32(A0.c, B0.c, acc00, 0, 0, 0);                   \
-    acc01 = __builtin_amdgcn_mfma_f32_32x32x2f32(A0.c, B1.c, acc01, 0, 0, 0);                   \
-    acc10 = __builtin_amdgcn_mfma_f32_32x32x2f32(A1.c, B0.c, acc10, 0, 0, 0);                   \
-    acc11 = __builtin_amdgcn_mfma_f32_32x32x2f32(A1.c, B1.c, acc11, 0, 0, 0);
-#define DAG_MFMA16(A0, A1, B0, B1)                                                              \
-    DAG_MFMA4(A0, A1, B0, B1, x) DAG_MFMA4(A0, A1, B0, B1, y) DAG_MFMA4(A0, A1, B0, B1, z) DAG_MFMA4(A0, A1, B0, B1, w)
-
-// acc += A[128 x 32 nkt] * B[128 x 32 nkt]^T: the K-loop of gemm_nt_big_kernel (double-buffered LDS-DMA image, fragments one MFMA
-// group ahead, one barrier per K-step) as a function over a K-segment.  Ad / Bd: this lane's DMA source (row wid*32 + rl of
-// the operand tile, logical chunk lc) at the segment's first column.  On entry no wave reads or fills the LDS image; the
-// same holds on return.
-__device__ __forceinline__ void dag_seg(float* __restrict__ lds, const DagLane& L, const float* Ad, int64_t lda, const float* Bd, int64_t ldb,
-                                        int nkt, f32x16& acc00, f32x16& acc01, f32x16& acc10, f32x16& acc11) {
-    typedef __attribute__((address_space(1))) const void* gptr_t;
-    typedef __attribute__((address_space(3))) void* lptr_t;
-    constexpr int IMG = NB * BK;                                // one operand image; lds = [buf][A|B][IMG]
-#define DAG_DMA(buf, k0)                                                                                           \
-    do {                                                                                                           \
-        _Pragma("unroll") for (int i = 0; i < 4; ++i) {                                                            \
-            __builtin_amdgcn_global_load_lds((gptr_t)(Ad + (int64_t)(8 * i) * lda + (k0)),                         \
-                                             (lptr_t)(lds + ((buf) * 2 + 0) * IMG + (L.wid * 32 + 8 * i) * BK), 16, 0, 0); \
-            __builtin_amdgcn_global_load_lds((gptr_t)(Bd + (int64_t)(8 * i) * ldb + (k0)),                         \
-                                             (lptr_t)(lds + ((buf) * 2 + 1) * IMG + (L.wid * 32 + 8 * i) * BK), 16, 0, 0); \
-        }                                                                                                          \
-    } while (0)
-#define DAG_FRAG(A0, A1, B0, B1, buf, s)                                                                               \
-    do {                                                                                                           \
-        A0 = *reinterpret_cast<const float4*>(lds + ((buf) * 2 + 0) * IMG + L.arow + 4 * ((2 * (s) + L.fh) ^ L.sw));            \
-        A1 = *reinterpret_cast<const float4*>(lds + ((buf) * 2 + 0) * IMG + L.arow + 32 * BK + 4 * ((2 * (s) + L.fh) ^ L.sw));  \
-        B0 = *reinterpret_cast<const float4*>(lds + ((buf) * 2 + 1) * IMG + L.brow + 4 * ((2 * (s) + L.fh) ^ L.sw));            \
-        B1 = *reinterpret_cast<const float4*>(lds + ((buf) * 2 + 1) * IMG + L.brow + 32 * BK + 4 * ((2 * (s) + L.fh) ^ L.sw));  \
-    } while (0)
-    float4 fa0, fa1, fb0, fb1, ga0, ga1, gb0, gb1;
-    DAG_DMA(0, 0);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    DAG_FRAG(fa0, fa1, fb0, fb1, 0, 0);
-    for (int kt = 0; kt < nkt; ++kt) {
-        const int cur = kt & 1;
-        const bool more = kt + 1 < nkt;
-        if (more) DAG_DMA(cur ^ 1, (kt + 1) * BK);              // the other buffer is free since the last barrier
-        DAG_FRAG(ga0, ga1, gb0, gb1, cur, 1);
-        DAG_MFMA16(fa0, fa1, fb0, fb1)                         // s = 0
-        DAG_FRAG(fa0, fa1, fb0, fb1, cur, 2);
-        DAG_MFMA16(ga0, ga1, gb0, gb1)                         // s = 1
-        DAG_FRAG(ga0, ga1, gb0, gb1, cur, 3);
-        DAG_MFMA16(fa0, fa1, fb0, fb1)                         // s = 2
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");        // this wave's DMA pieces of K-step kt+1 have landed ...
-        __syncthreads();                                        // ... everyone else's too; every read of K-step kt has been issued
-        if (more) DAG_FRAG(fa0, fa1, fb0, fb1, cur ^ 1, 0);
-        DAG_MFMA16(ga0, ga1, gb0, gb1)                         // s = 3
-    }
-#undef DAG_DMA
-#undef DAG_FRAG
-}
-
 // The same K-segment on the bf16 matrix pipe -- the FAR stretch of a bulk task's K-loop (kfar, "Far stretch" at
 // dag_task_order): over the SAME fp32 LDS image and the same LDS-DMA fill as dag_seg, nothing changes in memory.  A K-step
 // of 32 is two k-chunks of 16.  v_mfma_f32_32x32x16_bf16 takes A[row lane & 31][k = 8 (lane >> 5) + e], e = 0 .. 7, from
@@ -204,6 +139,111 @@ __device__ __forceinline__ dag_bf16x8 dag_pack8(const float4& a, const float4& b
     const dag_u32x4 u = {dag_pk_bf16(a.x, a.y), dag_pk_bf16(a.z, a.w), dag_pk_bf16(b.x, b.y), dag_pk_bf16(b.z, b.w)};
     return __builtin_bit_cast(dag_bf16x8, u);
 }
+
+// ... and as SPLIT bf16 products -- the MIDDLE stretch of a bulk task's K-loop (kmid, "Middle stretch" at dag_task_order):
+// the far stretch's LDS image, LDS-DMA fill, barriers and fragment reads, but every operand fragment a becomes
+// two bf16 fragments, hi = bf16(a) (round to nearest even, the far stretch's own rounding) and lo = bf16(a - float(hi)) --
+// a - float(hi) is exact in fp32 -- and a product a b^T becomes lo hi^T + hi lo^T + hi hi^T: relative error ~2^-16 per term
+// (the dropped lo lo^T and the rounding of lo) where the far stretch has 2^-8.  Twelve MFMAs per k-chunk into the same four
+// accumulators, in ONE order: a_lo b_hi^T of the quadrants 00, 01, 10, 11, then a_hi b_lo^T of the four, then a_hi b_hi^T of
+// the four -- every accumulator takes its small terms first, and no MFMA waits for the one issued in front of it.  3/16 of
+// dag_seg's MFMA cycles per K-step; the split is VALU work, ~3 instructions per operand element (unpack, subtract, pack),
+// operand by operand so that the raw fp32 fragment of one operand is dead before the next is split.
+__device__ __forceinline__ unsigned dag_pk_bf16_lo(float x, float y, unsigned hi /* dag_pk_bf16(x, y) */) {
+    return dag_pk_bf16(x - __builtin_bit_cast(float, hi << 16), y - __builtin_bit_cast(float, hi & 0xffff0000u));
+}
+__device__ __forceinline__ void dag_split8(const float4& a, const float4& b, dag_bf16x8& hi, dag_bf16x8& lo) {
+    const dag_u32x4 h = {dag_pk_bf16(a.x, a.y), dag_pk_bf16(a.z, a.w), dag_pk_bf16(b.x, b.y), dag_pk_bf16(b.z, b.w)};
+    const dag_u32x4 l = {dag_pk_bf16_lo(a.x, a.y, h.x), dag_pk_bf16_lo(a.z, a.w, h.y), dag_pk_bf16_lo(b.x, b.y, h.z), dag_pk_bf16_lo(b.z, b.w, h.w)};
+    hi = __builtin_bit_cast(dag_bf16x8, h);
+    lo = __builtin_bit_cast(dag_bf16x8, l);
+}
+
+// ---- Shadow: the bf16 images of the final tiles, made once -----------------------------------------------------------------
+// A finished tile L(r,k) is an operand of up to a band's width of later tasks, and every one of them rounded it (far) or
+// split it (middle) again in its K-loop: 96 VALU instructions per lane and k-chunk in front of the middle stretch's MFMAs,
+// and four bytes fetched per element where the far stretch needs two.  hi = bf16(a) and lo = bf16(a - float(hi)) are pure
+// functions of the final tile, so the task that stores a final off-diagonal tile stores them too (dag_shadow_store) and the
+// two stretches DMA them (dag_seg_sh): the same operand bits into the same MFMAs in the same order as the in-loop
+// conversions (dag_seg_bf16 / dag_seg_bf16x2) -- the factor does not change by a bit.
+// Layout of a shadow tile (kShTile = 64 KiB, tiles of a block row consecutive in k; DagSys::shadow): two PLANES, hi then lo,
+// each [half h = 0, 1][row 0 .. 127][64 columns 64 h .. 64 h + 63] in bf16 -- rows of 128 bytes, a 64-column step of 16 KiB
+// contiguous.  Only LDS-DMA reads it and every lane gives its own 16-byte source, so
+//   * a FAR K-step is 64 columns deep in the LDS footprint of dag_seg's 32: one contiguous 16 KiB step of the hi plane per
+//     operand, whole cache lines, half the round trips of the in-loop conversion and half its bytes; the image row is 8 chunks
+//     of 8 columns, k-chunk c of a lane is the logical chunk 2 c + fh: one ds_read_b128 where the conversion has two and four packs;
+//   * a MIDDLE K-step stays 32 columns: an image row is hi of the 32 columns (logical chunks 0 .. 3, 64 bytes of the hi plane's
+//     row) | their lo (chunks 4 .. 7, from the lo plane); k-chunk c is the chunks 2 c + fh and 4 + 2 c + fh.
+// Both images keep dag_seg's 16-byte XOR swizzle (physical chunk = logical ^ (row & 7)), and the fragment reads are
+// dag_seg's pattern with another constant under the XOR -- a bijection of the chunks of a row, so the reads are spread over
+// the 64 banks exactly as swz_sweep found for the fp32 image.  No cache line holds parts of two tiles.
+// Tried and not kept: the images BEHIND the publish of rowfin, announced by a progress word of their own that the shadow
+// segments poll instead, with the chain's images converted from its LDS image under the rank-128 update's MFMAs.  The chain's
+// panel step went back from 15.3 to 12.8 us, but its rank-128 update rose from 7.8 to 10.3 us and its diagonal block from 22.9
+// to 24.8 us: the headline step was the same to 0.1 ms, for a fourth progress array and a second writer.
+constexpr int64_t kShTile = 65536;                              // bytes of a shadow tile
+constexpr int kShPlane = 32768, kShHalf = 16384;                // ... of a plane, of a 64-column half of a plane
+// lane's DMA source inside the shadow tile at `tile` (row wid*32 + rl, logical chunk lc of the image row): far | middle (SPLIT)
+template <bool SPLIT>
+__device__ __forceinline__ const char* dag_sh_src(const char* tile, const DagLane& L) {
+    return tile + (L.wid * 32 + L.rl) * 128 + (SPLIT ? 16 * (L.lc & 3) + (L.lc >> 2) * kShPlane : 16 * L.lc);
+}
+
+// One K-segment over the shadow: SPLIT = the middle stretch's split products (else the far stretch's single ones).  Ad / Bd:
+// dag_sh_src<SPLIT> of the segment's first tile of each operand row.  A far K-step is 64 columns (two per tile, four k-chunks),
+// a middle one 32 (four per tile, two k-chunks).  Barriers and look-ahead as in dag_seg_bf16, the twelve MFMAs of a split
+// k-chunk in dag_seg_bf16x2's order.
+template <bool SPLIT>
+__device__ __forceinline__ int64_t dag_sh_step(int kt) {        // byte offset of K-step kt from the segment's first
+    if (!SPLIT) return (int64_t)(kt >> 1) * kShTile + (kt & 1) * kShHalf;
+    return (int64_t)(kt >> 2) * kShTile + ((kt >> 1) & 1) * kShHalf + (kt & 1) * 64;
+}
+// the bf16 fragment(s) of k-chunk c of an operand row (`row`: the row's start in an operand image; logical chunk q holds 8 columns)
+template <bool SPLIT>
+__device__ __forceinline__ void dag_sh_frag(const float* row, const DagLane& L, int c, dag_bf16x8& hi, dag_bf16x8& lo) {
+    hi = *reinterpret_cast<const dag_bf16x8*>(row + 4 * ((2 * c + L.fh) ^ L.sw));
+    if (SPLIT) lo = *reinterpret_cast<const dag_bf16x8*>(row + 4 * ((4 + 2 * c + L.fh) ^ L.sw));
+}
+#define DAG_MFMA4_BF16(A0, A1, B0, B1)                                                          \
+    acc00 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A0, B0, acc00, 0, 0, 0);                    \
+    acc01 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A0, B1, acc01, 0, 0, 0);                    \
+    acc10 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A1, B0, acc10, 0, 0, 0);                    \
+    acc11 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A1, B1, acc11, 0, 0, 0);
+template <bool SPLIT>
+__device__ __forceinline__ void dag_seg_sh(float* __restrict__ lds, const DagLane& L, const char* Ad, const char* Bd, int nkt, f32x16& acc00,
+                                           f32x16& acc01, f32x16& acc10, f32x16& acc11) {
+    constexpr int64_t sa = 128, sb = 128;                       // bytes between the rows of a shadow plane
+    constexpr int IMG = NB * BK;
+    constexpr int NCHUNK = SPLIT ? 2 : 4;                // k-chunks of 16 columns per K-step
+    dag_dma(lds, 0, L, Ad, sa, Bd, sb);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    for (int kt = 0; kt < nkt; ++kt) {
+        const int cur = kt & 1;
+        if (kt + 1 < nkt) {                                     // the other buffer is free since the last barrier
+            const int64_t off = dag_sh_step<SPLIT>(kt + 1);
+            dag_dma(lds, cur ^ 1, L, Ad + off, sa, Bd + off, sb);
+        }
+#pragma unroll
+        for (int c = 0; c < NCHUNK; ++c) {
+            const float* A = lds + (cur * 2 + 0) * IMG;
+            const float* B = lds + (cur * 2 + 1) * IMG;
+            dag_bf16x8 a0, a0l, a1, a1l, b0, b0l, b1, b1l;
+            dag_sh_frag<SPLIT>(A + L.arow, L, c, a0, a0l);
+            dag_sh_frag<SPLIT>(A + L.arow + 32 * BK, L, c, a1, a1l);
+            dag_sh_frag<SPLIT>(B + L.brow, L, c, b0, b0l);
+            dag_sh_frag<SPLIT>(B + L.brow + 32 * BK, L, c, b1, b1l);
+            if (SPLIT) {
+                DAG_MFMA4_BF16(a0l, a1l, b0, b1)
+                DAG_MFMA4_BF16(a0, a1, b0l, b1l)
+            }
+            DAG_MFMA4_BF16(a0, a1, b0, b1)
+        }
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");        // this wave's DMA pieces of K-step kt+1 have landed ...
+        __syncthreads();                                        // ... everyone else's too; every read of K-step kt is back
+    }
+}
+#undef DAG_MFMA4_BF16
 __device__ __forceinline__ void dag_seg_bf16(float* __restrict__ lds, const DagLane& L, const float* Ad, int64_t lda, const float* Bd, int64_t ldb,
                                              int nkt, f32x16& acc00, f32x16& acc01, f32x16& acc10, f32x16& acc11) {
     typedef __attribute__((address_space(1))) const void* gptr_t;
@@ -250,25 +290,6 @@ __device__ __forceinline__ void dag_seg_bf16(float* __restrict__ lds, const DagL
         __syncthreads();                                        // ... everyone else's too; every read of K-step kt is back
     }
 #undef DAG_CHUNK
-}
-
-// The same K-segment as SPLIT bf16 products -- the MIDDLE stretch of a bulk task's K-loop (kmid, "Middle stretch" at
-// dag_task_order): dag_seg_bf16's LDS image, LDS-DMA fill, barriers and fragment reads, but every operand fragment a becomes
-// two bf16 fragments, hi = bf16(a) (round to nearest even, the far stretch's own rounding) and lo = bf16(a - float(hi)) --
-// a - float(hi) is exact in fp32 -- and a product a b^T becomes lo hi^T + hi lo^T + hi hi^T: relative error ~2^-16 per term
-// (the dropped lo lo^T and the rounding of lo) where dag_seg_bf16 has 2^-8.  Twelve MFMAs per k-chunk into the same four
-// accumulators, in ONE order: a_lo b_hi^T of the quadrants 00, 01, 10, 11, then a_hi b_lo^T of the four, then a_hi b_hi^T of
-// the four -- every accumulator takes its small terms first, and no MFMA waits for the one issued in front of it.  3/16 of
-// dag_seg's MFMA cycles per K-step; the split is VALU work, ~3 instructions per operand element (unpack, subtract, pack),
-// operand by operand so that the raw fp32 fragment of one operand is dead before the next is split.
-__device__ __forceinline__ unsigned dag_pk_bf16_lo(float x, float y, unsigned hi /* dag_pk_bf16(x, y) */) {
-    return dag_pk_bf16(x - __builtin_bit_cast(float, hi << 16), y - __builtin_bit_cast(float, hi & 0xffff0000u));
-}
-__device__ __forceinline__ void dag_split8(const float4& a, const float4& b, dag_bf16x8& hi, dag_bf16x8& lo) {
-    const dag_u32x4 h = {dag_pk_bf16(a.x, a.y), dag_pk_bf16(a.z, a.w), dag_pk_bf16(b.x, b.y), dag_pk_bf16(b.z, b.w)};
-    const dag_u32x4 l = {dag_pk_bf16_lo(a.x, a.y, h.x), dag_pk_bf16_lo(a.z, a.w, h.y), dag_pk_bf16_lo(b.x, b.y, h.z), dag_pk_bf16_lo(b.z, b.w, h.w)};
-    hi = __builtin_bit_cast(dag_bf16x8, h);
-    lo = __builtin_bit_cast(dag_bf16x8, l);
 }
 __device__ __forceinline__ void dag_seg_bf16x2(float* __restrict__ lds, const DagLane& L, const float* Ad, int64_t lda, const float* Bd, int64_t ldb,
                                                int nkt, f32x16& acc00, f32x16& acc01, f32x16& acc10, f32x16& acc11) {
@@ -317,119 +338,6 @@ __device__ __forceinline__ void dag_seg_bf16x2(float* __restrict__ lds, const Da
 #undef DAG_SPLIT
 #undef DAG_CHUNK
 }
-
-// ---- Shadow: the bf16 images of the final tiles, made once -----------------------------------------------------------------
-// A finished tile L(r,k) is an operand of up to a band's width of later tasks, and every one of them rounded it (far) or
-// split it (middle) again in its K-loop: 96 VALU instructions per lane and k-chunk in front of the middle stretch's MFMAs,
-// and four bytes fetched per element where the far stretch needs two.  hi = bf16(a) and lo = bf16(a - float(hi)) are pure
-// functions of the final tile, so the task that stores a final off-diagonal tile stores them too (dag_shadow_store) and the
-// two stretches DMA them (dag_seg_bf16_sh, dag_seg_bf16x2_sh): the same operand bits into the same MFMAs in the same order
-// as dag_seg_bf16 / dag_seg_bf16x2 -- the factor does not change by a bit.
-// Layout of a shadow tile (kShTile = 64 KiB, tiles of a block row consecutive in k; DagSys::shadow): two PLANES, hi then lo,
-// each [half h = 0, 1][row 0 .. 127][64 columns 64 h .. 64 h + 63] in bf16 -- rows of 128 bytes, a 64-column step of 16 KiB
-// contiguous.  Only LDS-DMA reads it and every lane gives its own 16-byte source, so
-//   * a FAR K-step is 64 columns deep in the LDS footprint of dag_seg's 32: one contiguous 16 KiB step of the hi plane per
-//     operand, whole cache lines, half the round trips of dag_seg_bf16 and half its bytes; the image row is 8 chunks of 8
-//     columns, k-chunk c of a lane is the logical chunk 2 c + fh: one ds_read_b128 where dag_seg_bf16 has two and four packs;
-//   * a MIDDLE K-step stays 32 columns: an image row is hi of the 32 columns (logical chunks 0 .. 3, 64 bytes of the hi plane's
-//     row) | their lo (chunks 4 .. 7, from the lo plane); k-chunk c is the chunks 2 c + fh and 4 + 2 c + fh.
-// Both images keep dag_seg's 16-byte XOR swizzle (physical chunk = logical ^ (row & 7)), and the fragment reads are
-// dag_seg's pattern with another constant under the XOR -- a bijection of the chunks of a row, so the reads are spread over
-// the 64 banks exactly as swz_sweep found for the fp32 image.  No cache line holds parts of two tiles.
-// Tried and not kept: the images BEHIND the publish of rowfin, announced by a progress word of their own that the shadow
-// segments poll instead, with the chain's images converted from its LDS image under the rank-128 update's MFMAs.  The chain's
-// panel step went back from 15.3 to 12.8 us, but its rank-128 update rose from 7.8 to 10.3 us and its diagonal block from 22.9
-// to 24.8 us: the headline step was the same to 0.1 ms, for a fourth progress array and a second writer.
-constexpr int64_t kShTile = 65536;                              // bytes of a shadow tile
-constexpr int kShPlane = 32768, kShHalf = 16384;                // ... of a plane, of a 64-column half of a plane
-// lane's DMA source inside the shadow tile at `tile` (row wid*32 + rl, logical chunk lc of the image row): far, middle
-__device__ __forceinline__ const char* dag_sh_src_far(const char* tile, const DagLane& L) { return tile + (L.wid * 32 + L.rl) * 128 + 16 * L.lc; }
-__device__ __forceinline__ const char* dag_sh_src_mid(const char* tile, const DagLane& L) {
-    return tile + (L.wid * 32 + L.rl) * 128 + 16 * (L.lc & 3) + (L.lc >> 2) * kShPlane;
-}
-#define DAG_SH_DMA(buf, off)                                                                                       \
-    do {                                                                                                           \
-        _Pragma("unroll") for (int i = 0; i < 4; ++i) {                                                            \
-            __builtin_amdgcn_global_load_lds((gptr_t)(Ad + (off) + 8 * i * 128),                                   \
-                                             (lptr_t)(lds + ((buf) * 2 + 0) * IMG + (L.wid * 32 + 8 * i) * BK), 16, 0, 0); \
-            __builtin_amdgcn_global_load_lds((gptr_t)(Bd + (off) + 8 * i * 128),                                   \
-                                             (lptr_t)(lds + ((buf) * 2 + 1) * IMG + (L.wid * 32 + 8 * i) * BK), 16, 0, 0); \
-        }                                                                                                          \
-    } while (0)
-// the bf16 fragment (8 columns) at logical chunk q of row `row` of an operand image
-#define DAG_SH_RD(buf, op, row, q) (*reinterpret_cast<const dag_bf16x8*>(lds + ((buf) * 2 + (op)) * IMG + (row) + 4 * ((q) ^ L.sw)))
-// The far stretch over the shadow.  Ad / Bd: dag_sh_src_far of the segment's first tile of each operand row; nkt K-steps of
-// 64 columns (two per tile).  Barriers and look-ahead as in dag_seg_bf16.
-__device__ __forceinline__ void dag_seg_bf16_sh(float* __restrict__ lds, const DagLane& L, const char* Ad, const char* Bd, int nkt,
-                                                f32x16& acc00, f32x16& acc01, f32x16& acc10, f32x16& acc11) {
-    typedef __attribute__((address_space(1))) const void* gptr_t;
-    typedef __attribute__((address_space(3))) void* lptr_t;
-    constexpr int IMG = NB * BK;
-#define DAG_CHUNK(buf, c)                                                                                          \
-    do {                                                                                                           \
-        const dag_bf16x8 a0 = DAG_SH_RD(buf, 0, L.arow, 2 * (c) + L.fh), a1 = DAG_SH_RD(buf, 0, L.arow + 32 * BK, 2 * (c) + L.fh); \
-        const dag_bf16x8 b0 = DAG_SH_RD(buf, 1, L.brow, 2 * (c) + L.fh), b1 = DAG_SH_RD(buf, 1, L.brow + 32 * BK, 2 * (c) + L.fh); \
-        acc00 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0, b0, acc00, 0, 0, 0);                                   \
-        acc01 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0, b1, acc01, 0, 0, 0);                                   \
-        acc10 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, b0, acc10, 0, 0, 0);                                   \
-        acc11 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, b1, acc11, 0, 0, 0);                                   \
-    } while (0)
-    DAG_SH_DMA(0, 0);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    for (int kt = 0; kt < nkt; ++kt) {
-        const int cur = kt & 1, nx = kt + 1;
-        if (nx < nkt) DAG_SH_DMA(cur ^ 1, (int64_t)(nx >> 1) * kShTile + (nx & 1) * kShHalf);      // the other buffer is free since the last barrier
-        DAG_CHUNK(cur, 0);
-        DAG_CHUNK(cur, 1);
-        DAG_CHUNK(cur, 2);
-        DAG_CHUNK(cur, 3);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");        // this wave's DMA pieces of K-step kt+1 have landed ...
-        __syncthreads();                                        // ... everyone else's too; every read of K-step kt is back
-    }
-#undef DAG_CHUNK
-}
-// The middle stretch over the shadow.  Ad / Bd: dag_sh_src_mid; nkt K-steps of 32 columns (four per tile).  The twelve MFMAs
-// of a k-chunk in dag_seg_bf16x2's order.
-__device__ __forceinline__ void dag_seg_bf16x2_sh(float* __restrict__ lds, const DagLane& L, const char* Ad, const char* Bd, int nkt,
-                                                  f32x16& acc00, f32x16& acc01, f32x16& acc10, f32x16& acc11) {
-    typedef __attribute__((address_space(1))) const void* gptr_t;
-    typedef __attribute__((address_space(3))) void* lptr_t;
-    constexpr int IMG = NB * BK;
-#define DAG_CHUNK(buf, c)                                                                                          \
-    do {                                                                                                           \
-        const dag_bf16x8 a0 = DAG_SH_RD(buf, 0, L.arow, 2 * (c) + L.fh), a1 = DAG_SH_RD(buf, 0, L.arow + 32 * BK, 2 * (c) + L.fh); \
-        const dag_bf16x8 b0 = DAG_SH_RD(buf, 1, L.brow, 2 * (c) + L.fh), b1 = DAG_SH_RD(buf, 1, L.brow + 32 * BK, 2 * (c) + L.fh); \
-        const dag_bf16x8 a0l = DAG_SH_RD(buf, 0, L.arow, 4 + 2 * (c) + L.fh), a1l = DAG_SH_RD(buf, 0, L.arow + 32 * BK, 4 + 2 * (c) + L.fh); \
-        const dag_bf16x8 b0l = DAG_SH_RD(buf, 1, L.brow, 4 + 2 * (c) + L.fh), b1l = DAG_SH_RD(buf, 1, L.brow + 32 * BK, 4 + 2 * (c) + L.fh); \
-        acc00 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0l, b0, acc00, 0, 0, 0);                                  \
-        acc01 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0l, b1, acc01, 0, 0, 0);                                  \
-        acc10 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1l, b0, acc10, 0, 0, 0);                                  \
-        acc11 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1l, b1, acc11, 0, 0, 0);                                  \
-        acc00 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0, b0l, acc00, 0, 0, 0);                                  \
-        acc01 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0, b1l, acc01, 0, 0, 0);                                  \
-        acc10 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, b0l, acc10, 0, 0, 0);                                  \
-        acc11 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, b1l, acc11, 0, 0, 0);                                  \
-        acc00 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0, b0, acc00, 0, 0, 0);                                   \
-        acc01 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0, b1, acc01, 0, 0, 0);                                   \
-        acc10 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, b0, acc10, 0, 0, 0);                                   \
-        acc11 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, b1, acc11, 0, 0, 0);                                   \
-    } while (0)
-    DAG_SH_DMA(0, 0);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    for (int kt = 0; kt < nkt; ++kt) {
-        const int cur = kt & 1, nx = kt + 1;
-        if (nx < nkt) DAG_SH_DMA(cur ^ 1, (int64_t)(nx >> 2) * kShTile + ((nx >> 1) & 1) * kShHalf + (nx & 1) * 64);
-        DAG_CHUNK(cur, 0);
-        DAG_CHUNK(cur, 1);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");        // this wave's DMA pieces of K-step kt+1 have landed ...
-        __syncthreads();                                        // ... everyone else's too; every read of K-step kt is back
-    }
-#undef DAG_CHUNK
-}
-#undef DAG_SH_DMA
-#undef DAG_SH_RD
 
 // The writer: the final tile held in the accumulators -> its two planes at `tile` (a shadow tile).  Through LDS, so that the
 // stores are coalesced 16-byte ones: a wave's 64 x 64 quadrant is 64 whole 128-byte rows of half wc of each plane, 8 KiB
@@ -534,11 +442,6 @@ __device__ __forceinline__ void dag_epilogue(float* Cg /* the wave's 64x64 quadr
 #undef DAG_SOFF
 }
 
-// lane's DMA source of operand tile `tile0` (a 128-row tile starting at row-major address tile0, leading dimension ld)
-__device__ __forceinline__ const float* dag_src(const float* tile0, int64_t ld, const DagLane& L) {
-    return tile0 + (int64_t)(L.wid * 32 + L.rl) * ld + 4 * L.lc;
-}
-
 // bulk task on tile (i, j) of system sy: kind DAG_TILE (i >= j + 2: k < j, then the panel product, publishes rowfin[i] = j + 1),
 // DAG_SUB (i = j + 1: k < j, leaves the updated tile, publishes sub[j]), DAG_PRE (i = j: k < j - 1, publishes pre[j]).
 // k0 (wave-uniform, from the ticket): the K-loop's first block column -- 0, or first[i] of an ENVELOPED system ("Envelope" at
@@ -592,14 +495,16 @@ __device__ __forceinline__ bool dag_tile_task(const DagSys& sy, int kind, int k0
         if (FAR && k < kfar) {                                  // a segment ends where the far stretch does
             kav = kav < kfar ? kav : kfar;
             if (shA && (sy.shuse & 1))
-                dag_seg_bf16_sh(lds, L, dag_sh_src_far(shA + k * kShTile, L), dag_sh_src_far(shB + k * kShTile, L), (kav - k) * 2, acc00, acc01, acc10, acc11);
+                dag_seg_sh<false>(lds, L, dag_sh_src<false>(shA + k * kShTile, L), dag_sh_src<false>(shB + k * kShTile, L), (kav - k) * 2,
+                                        acc00, acc01, acc10, acc11);
             else
                 dag_seg_bf16(lds, L, dag_src(Arow + (int64_t)k * NB, sy.ld, L), sy.ld, dag_src(Brow + (int64_t)k * NB, sy.ld, L), sy.ld,
                              (kav - k) * (NB / BK), acc00, acc01, acc10, acc11);
         } else if (FAR && k < kmid) {                           // ... and where the middle stretch does
             kav = kav < kmid ? kav : kmid;
             if (shA && (sy.shuse & 2))
-                dag_seg_bf16x2_sh(lds, L, dag_sh_src_mid(shA + k * kShTile, L), dag_sh_src_mid(shB + k * kShTile, L), (kav - k) * 4, acc00, acc01, acc10, acc11);
+                dag_seg_sh<true>(lds, L, dag_sh_src<true>(shA + k * kShTile, L), dag_sh_src<true>(shB + k * kShTile, L), (kav - k) * 4,
+                                       acc00, acc01, acc10, acc11);
             else
                 dag_seg_bf16x2(lds, L, dag_src(Arow + (int64_t)k * NB, sy.ld, L), sy.ld, dag_src(Brow + (int64_t)k * NB, sy.ld, L), sy.ld,
                                (kav - k) * (NB / BK), acc00, acc01, acc10, acc11);
@@ -1102,20 +1007,6 @@ __device__ __forceinline__ bool dag_inc_task(const DagSys& sy, const SolveMember
     return true;
 }
 
-__device__ __forceinline__ void dag_lane_coords(DagLane& L, int t) {      // (the kernel's own first lines, for DAG_SOLVE_FWD's task loop)
-    L.lane = t & 63;
-    L.wid = __builtin_amdgcn_readfirstlane(t >> 6);
-    L.wr = L.wid >> 1;
-    L.wc = L.wid & 1;
-    L.rl = L.lane >> 3;
-    L.lc = (L.lane & 7) ^ L.rl;
-    L.frow = L.lane & 31;
-    L.fh = L.lane >> 5;
-    L.sw = L.frow & 7;
-    L.arow = (L.wr * 64 + L.frow) * BK;
-    L.brow = (L.wc * 64 + L.frow) * BK;
-}
-
 // SOLVE = DAG_SOLVE_ALL: the launch also runs the systems' solve tasks (oisat_batch_analyse); the workgroup's LDS then also
 // serves a sweep row's 128 x 129 block image + vectors (68 KB instead of 64: still two workgroups per CU).
 // SOLVE = DAG_SOLVE_FWD: ONE system, and of its solve only the rows of the first forward sweep (dag_fwd_row_task) -- an
@@ -1138,7 +1029,7 @@ __global__ __launch_bounds__(256, 2) void potrf_dag_kernel(const DagSys* __restr
     __shared__ int s_ticket, s_flag, s_kav;
     static_assert(2 * D3_PBUF + 7 * D3_TILE + 2 * D3_TILE + 16 * D3_SLD <= 2 * 2 * NB * BK, "diagonal-block LDS fits into the GEMM image");
     const int t = threadIdx.x;
-    DagLane L;
+    DagLane L;                                                  // (dag_lane_coords, written out: through the call <1> spills 7 VGPRs more)
     L.lane = t & 63;
     L.wid = __builtin_amdgcn_readfirstlane(t >> 6);
     L.wr = L.wid >> 1;
@@ -1326,10 +1217,27 @@ __global__ __launch_bounds__(256, 2) void potrf_dag_kernel(const DagSys* __restr
         }
     }
 }
-#undef DAG_MFMA4
+#undef DAG_MFMA4                                                // (defined in dense_kloop.inc for dag_seg; dag_self_product above is their other user)
 #undef DAG_MFMA16
 
 // ---- host: the plan of a task-graph launch ---------------------------------------------------------------------------
+// The envelope an enveloped single-system plan was made for and its stretches, normalised: no far stretch (oisat_factor_far) is
+// far = first, no middle stretch (oisat_factor_mid) is mid = far.  Empty: a dense plan.
+struct DagBands {
+    std::vector<int> first, far, mid;
+    DagBands() {}
+    DagBands(int nb, const int* first_, const int* far_, const int* mid_)
+        : first(first_, first_ + nb), far(far_ ? std::vector<int>(far_, far_ + nb) : first), mid(mid_ ? std::vector<int>(mid_, mid_ + nb) : far) {}
+    bool operator==(const DagBands& o) const { return first == o.first && far == o.far && mid == o.mid; }
+    // ... against a caller's raw tables of nb rows, normalised the same way, without building one
+    bool equals(size_t nb, const int* first_, const int* far_, const int* mid_) const {
+        far_ = far_ ? far_ : first_;
+        mid_ = mid_ ? mid_ : far_;
+        return first.size() == nb && std::equal(first.begin(), first.end(), first_) && std::equal(far.begin(), far.end(), far_) &&
+               std::equal(mid.begin(), mid.end(), mid_);
+    }
+};
+
 struct DagPlan {
     DagSys* sys_dev = nullptr;
     int4* tasks_dev = nullptr;
@@ -1344,10 +1252,8 @@ struct DagPlan {
     unsigned long long* queue_dev = nullptr;
     std::vector<DagSys> sys_host;
     std::vector<int4> tasks_host;
-    std::vector<int> first;                                     // the envelope this single-system plan's ticket list was made for (empty: dense)
-    std::vector<int> far;                                       // ... and its far stretch (oisat_factor_far; no stretch: equal to first)
-    std::vector<int> mid;                                       // ... and its middle stretch (oisat_factor_mid; no stretch: equal to far)
-    int* mid_dev = nullptr;                                     // the device copy of mid (an enveloped plan's int32[nb]); DagSys::mid points here while a stretch exists
+    DagBands bands;                                             // what this plan's ticket list was made for
+    int* mid_dev = nullptr;                                     // the device copy of bands.mid (an enveloped plan's int32[nb]); DagSys::mid points here while a stretch exists
     std::vector<int64_t> shrow;                                 // the shadow's row table of `first`: rowoff[r] - first[r] (dag_shadow_layout), and its device copy
     int64_t* shrow_dev = nullptr;
     int64_t sh_tiles = 0;                                       // tiles of that shadow: sum of r - first[r]
@@ -1393,7 +1299,7 @@ constexpr int kDagWave0Max = 64;                                // wave 0 holds 
 // Middle stretch (oisat_factor_mid: mid[i] = first block column of block row i that is NOT middle, far[i] <= mid[i] <= i): the
 // K-blocks kfar .. kmid - 1 of a bulk task run as split bf16 products (dag_seg_bf16x2).  Ten more bits do not fit the ticket's
 // first word, and the words stay what they are: the table itself goes to the device (DagPlan::mid_dev, uploaded with the ticket
-// list by dag_plan_mid) and a task clamps kmid = mid[i] into [kfar, kend] with one scalar load.  The ticket ORDER does not
+// list by dag_plan_install) and a task clamps kmid = mid[i] into [kfar, kend] with one scalar load.  The ticket ORDER does not
 // depend on it.
 constexpr int kDagEnvMaxBlocks = 1024;
 void dag_task_order(const std::vector<int>& nb_of, int wave_arg, DagOrder& out, const int* first = nullptr, const int* far = nullptr) {
@@ -1537,22 +1443,6 @@ static inline void dag_queue_entries(const std::vector<int>& nb_of, const DagSol
 static inline bool dag_fits(int max_wave_chains, int slots) { return 4 * max_wave_chains <= slots; }
 static inline int dag_slots(const oisat_ctx* h) { return 2 * (h->cu_count > 0 ? h->cu_count : 256); }
 
-// The middle table of an enveloped single-system plan: host copy (mid == nullptr: far, no stretch), device copy, and the
-// system's pointer to it -- null while no row has a middle block.  Enqueued on `stream`; the host vectors are the sources of
-// the copies, so the caller has synchronised with whatever copy of them was in flight.
-static hipError_t dag_plan_mid(DagPlan& p, const int* mid, hipStream_t stream) {
-    const size_t nb = p.first.size();
-    p.mid.assign(mid ? mid : p.far.data(), (mid ? mid : p.far.data()) + nb);
-    bool any = false;
-    for (size_t i = 0; i < nb; ++i) any = any || p.mid[i] > p.far[i];
-    const int* want = any ? p.mid_dev : nullptr;
-    if (any)
-        if (hipError_t e = hipMemcpyAsync(p.mid_dev, p.mid.data(), sizeof(int) * nb, hipMemcpyHostToDevice, stream)) return e;
-    if (p.sys_host[0].mid == want) return hipSuccess;
-    p.sys_host[0].mid = want;
-    return hipMemcpyAsync(p.sys_dev, p.sys_host.data(), sizeof(DagSys), hipMemcpyHostToDevice, stream);
-}
-
 // The shadow's addressing (oisat_factor_shadow_layout): the strictly-lower tiles (r, k), first[r] <= k < r, row after row;
 // rowoff[r] = tiles of the rows above r, tile (r, k) is number rowoff[r] + (k - first[r]).  Returns the number of tiles.
 static int64_t dag_shadow_layout(const int* first, int64_t nb, int64_t* rowoff) {
@@ -1564,38 +1454,63 @@ static int64_t dag_shadow_layout(const int* first, int64_t nb, int64_t* rowoff) 
     return n;
 }
 
-// ... of an enveloped plan's `first`, to the device (at creation and with every new envelope; the caller has synchronised as
-// for dag_plan_mid).  Whether a launch HAS a shadow is decided per call: dag_plan_shadow.
-static hipError_t dag_plan_shrow(DagPlan& p, hipStream_t stream) {
-    const size_t nb = p.first.size();
-    p.shrow.resize(nb);
-    p.sh_tiles = dag_shadow_layout(p.first.data(), (int64_t)nb, p.shrow.data());
-    for (size_t r = 0; r < nb; ++r) p.shrow[r] -= p.first[r];
-    return hipMemcpyAsync(p.shrow_dev, p.shrow.data(), sizeof(int64_t) * nb, hipMemcpyHostToDevice, stream);
+// What changes in DagSys[0] of a single-system plan after its creation -- the middle table's pointer, this call's shadow (null:
+// none), its row table and its readers (DagSys::shuse) --, uploaded on `stream` when the host copy differs.  wait: launches that
+// read the system's words as they are may be in flight, and a change waits for them.
+static hipError_t dag_plan_sys0(DagPlan& p, const int* mid, char* shadow, const int64_t* shrow, int shuse, bool wait, hipStream_t stream) {
+    DagSys& sy = p.sys_host[0];
+    if (sy.mid == mid && sy.shadow == shadow && sy.shrow == shrow && sy.shuse == shuse) return hipSuccess;
+    if (wait)
+        if (hipError_t e = hipStreamSynchronize(stream)) return e;
+    sy.mid = mid;
+    sy.shadow = shadow;
+    sy.shrow = shrow;
+    sy.shuse = shuse;
+    return hipMemcpyAsync(p.sys_dev, p.sys_host.data(), sizeof(DagSys), hipMemcpyHostToDevice, stream);
 }
 
 // This call's shadow (null: none) and its readers (DagSys::shuse) into the plan's system; a change waits for the launches
 // that read the system's words as they are.
 static hipError_t dag_plan_shadow(DagPlan& p, char* shadow, int use, hipStream_t stream) {
-    DagSys& sy = p.sys_host[0];
-    const int64_t* want = shadow ? p.shrow_dev : nullptr;
-    if (sy.shadow == shadow && sy.shrow == want && sy.shuse == use) return hipSuccess;
-    if (hipError_t e = hipStreamSynchronize(stream)) return e;
-    sy.shadow = shadow;
-    sy.shrow = want;
-    sy.shuse = use;
-    return hipMemcpyAsync(p.sys_dev, p.sys_host.data(), sizeof(DagSys), hipMemcpyHostToDevice, stream);
+    return dag_plan_sys0(p, p.sys_host[0].mid, shadow, shadow ? p.shrow_dev : nullptr, use, true, stream);
+}
+
+// An order and the tables it was made for into the plan (the ticket list's upload is the caller's) and, on `stream`, an enveloped
+// plan's tables into its device buffers: the middle table, and the system's pointer to it -- null while no row has a middle block (the ticket ORDER does not depend
+// on it) --; the shadow's row table of `first`, rowoff[r] - first[r] (whether a launch HAS a shadow is decided per call).  The
+// plan's host vectors are the sources of the copies, so the caller has synchronised with whatever copy of them was in flight.
+static hipError_t dag_plan_install(DagPlan& p, DagOrder& order, const DagBands& bands, hipStream_t stream) {
+    p.tasks_host.swap(order.tasks);
+    p.ntasks = (int)p.tasks_host.size();
+    p.bands = bands;
+    p.max_wave_chains = order.max_wave_chains;
+    p.chain_rows = order.chain_rows;
+    p.reserve_chains = order.reserve_chains;
+    const size_t nb = bands.first.size();
+    if (nb == 0) return hipSuccess;
+    bool any = false;
+    for (size_t i = 0; i < nb; ++i) any = any || bands.mid[i] > bands.far[i];
+    if (any)
+        if (hipError_t e = hipMemcpyAsync(p.mid_dev, p.bands.mid.data(), sizeof(int) * nb, hipMemcpyHostToDevice, stream)) return e;
+    const DagSys& sy = p.sys_host[0];
+    if (hipError_t e = dag_plan_sys0(p, any ? p.mid_dev : nullptr, sy.shadow, sy.shrow, sy.shuse, false, stream)) return e;
+    p.shrow.resize(nb);
+    p.sh_tiles = dag_shadow_layout(p.bands.first.data(), (int64_t)nb, p.shrow.data());
+    for (size_t r = 0; r < nb; ++r) p.shrow[r] -= p.bands.first[r];
+    return hipMemcpyAsync(p.shrow_dev, p.shrow.data(), sizeof(int64_t) * nb, hipMemcpyHostToDevice, stream);
 }
 
 // systems in table order (largest first)
 // The progress words and the control block are zeroed ON `stream` (the stream the plan's launches go to): a plain hipMemset is
 // ordered in the NULL stream only, which the handles' non-blocking streams do not wait for -- a launch could start on
 // uninitialised words (wrong tickets, flags that read "ready").
-// first (single system only): its envelope; the ticket buffer is then sized for the dense list of these block rows
+// bands (single system only): its envelope and stretches; the ticket buffer is then sized for the dense list of these block rows
 DagPlan* dag_plan_create(const std::vector<BatchMat>& table, hipStream_t stream, const DagSolveShape& shape = DagSolveShape(),
-                         const int* first = nullptr, const int* far = nullptr, const int* mid = nullptr) {
+                         const DagBands& bands_arg = DagBands()) {
     DagPlan* p = new DagPlan();
     const int nsys = (int)table.size();
+    const DagBands bands = nsys == 1 ? bands_arg : DagBands();
+    const bool env = !bands.first.empty();
     p->nsys = nsys;
     p->sys_host.resize(nsys);
     std::vector<int> state_off(nsys);
@@ -1610,11 +1525,7 @@ DagPlan* dag_plan_create(const std::vector<BatchMat>& table, hipStream_t stream,
     {
         std::vector<int> nb_of(nsys);
         for (int s = 0; s < nsys; ++s) nb_of[s] = table[s].mpb;
-        dag_task_order(nb_of, 0, order, nsys == 1 ? first : nullptr, nsys == 1 && first ? far : nullptr);
-        if (first && nsys == 1) {
-            p->first.assign(first, first + nb_of[0]);
-            p->far.assign(far ? far : first, (far ? far : first) + nb_of[0]);
-        }
+        dag_task_order(nb_of, 0, order, env ? bands.first.data() : nullptr, env ? bands.far.data() : nullptr);
         if (shape.refine >= 0) {
             int64_t rows = 0, valu = 0;
             dag_queue_entries(nb_of, shape, &rows, &valu);
@@ -1624,14 +1535,8 @@ DagPlan* dag_plan_create(const std::vector<BatchMat>& table, hipStream_t stream,
     }
     p->solve_refine = shape.refine;
     p->fwd_only = shape.fwd_only;
-    std::vector<int4>& tasks = order.tasks;
-    p->max_wave_chains = order.max_wave_chains;
-    p->chain_rows = order.chain_rows;
-    p->reserve_chains = order.reserve_chains;
-    p->ntasks = (int)tasks.size();
-    p->tasks_host = tasks;
-    p->tasks_cap = tasks.size();
-    if (!p->first.empty()) {                                    // chain + PRE + SUB + every lower tile two or more below the diagonal
+    p->tasks_cap = order.tasks.size();
+    if (env) {                                                  // chain + PRE + SUB + every lower tile two or more below the diagonal
         const size_t nb = (size_t)table[0].mpb;
         p->tasks_cap = 1 + 2 * nb + nb * (nb + 1) / 2;
     }
@@ -1639,18 +1544,17 @@ DagPlan* dag_plan_create(const std::vector<BatchMat>& table, hipStream_t stream,
               hipMalloc((void**)&p->tasks_dev, sizeof(int4) * p->tasks_cap) == hipSuccess &&
               hipMalloc((void**)&p->state_dev, sizeof(int) * words) == hipSuccess &&
               hipMalloc((void**)&p->ctl_dev, sizeof(DagCtl)) == hipSuccess &&
-              (p->first.empty() || hipMalloc((void**)&p->mid_dev, sizeof(int) * p->first.size()) == hipSuccess) &&
-              (p->first.empty() || hipMalloc((void**)&p->shrow_dev, sizeof(int64_t) * p->first.size()) == hipSuccess) &&
+              (!env || hipMalloc((void**)&p->mid_dev, sizeof(int) * bands.first.size()) == hipSuccess) &&
+              (!env || hipMalloc((void**)&p->shrow_dev, sizeof(int64_t) * bands.first.size()) == hipSuccess) &&
               (p->qcap == 0 || (p->qcap < (int64_t)INT32_MAX / 4 && hipMalloc((void**)&p->queue_dev, 16 * (size_t)p->qcap) == hipSuccess));
     if (ok && p->qcap > 0) ok = hipMemsetAsync(p->queue_dev, 0, 16 * (size_t)p->qcap, stream) == hipSuccess;
     if (ok) {
         for (int s = 0; s < nsys; ++s)
             p->sys_host[s] = DagSys{table[s].S, table[s].tinv, table[s].ld, p->state_dev + state_off[s], table[s].mpb, s};
         ok = hipMemcpy(p->sys_dev, p->sys_host.data(), sizeof(DagSys) * nsys, hipMemcpyHostToDevice) == hipSuccess &&
-             hipMemcpy(p->tasks_dev, tasks.data(), sizeof(int4) * tasks.size(), hipMemcpyHostToDevice) == hipSuccess &&
+             hipMemcpy(p->tasks_dev, order.tasks.data(), sizeof(int4) * order.tasks.size(), hipMemcpyHostToDevice) == hipSuccess &&
              hipMemsetAsync(p->state_dev, 0, sizeof(int) * words, stream) == hipSuccess &&
-             hipMemsetAsync(p->ctl_dev, 0, sizeof(DagCtl), stream) == hipSuccess;
-        if (ok && !p->first.empty()) ok = dag_plan_mid(*p, mid, stream) == hipSuccess && dag_plan_shrow(*p, stream) == hipSuccess;
+             hipMemsetAsync(p->ctl_dev, 0, sizeof(DagCtl), stream) == hipSuccess && dag_plan_install(*p, order, bands, stream) == hipSuccess;
     }
     if (!ok) {
         dag_plan_free(p);
@@ -1662,26 +1566,17 @@ DagPlan* dag_plan_create(const std::vector<BatchMat>& table, hipStream_t stream,
 
 // A cached enveloped plan meets another envelope (same matrix, same block rows): new ticket list into the SAME buffers.  The
 // copy is enqueued on `stream`, behind the launches that still read the old list.
-int dag_plan_refill(DagPlan& p, const int* first, const int* far, const int* mid, hipStream_t stream) {
-    const int nb = p.sys_host[0].nb;
+int dag_plan_refill(DagPlan& p, const DagBands& bands, hipStream_t stream) {
     DagOrder order;
-    dag_task_order(std::vector<int>{nb}, 0, order, first, far);
+    dag_task_order(std::vector<int>{p.sys_host[0].nb}, 0, order, bands.first.data(), bands.far.data());
     if (order.tasks.size() > p.tasks_cap) {
         oisat_set_error("task-graph factorization: %zu tickets do not fit the plan's %zu", order.tasks.size(), p.tasks_cap);
         return OISAT_EINVAL;
     }
     HIP_TRY(hipStreamSynchronize(stream));                      // (the host list is the source of a copy that may still be in flight)
-    p.tasks_host = order.tasks;
-    p.ntasks = (int)order.tasks.size();
-    p.first.assign(first, first + nb);
-    p.far.assign(far ? far : first, (far ? far : first) + nb);
-    p.max_wave_chains = order.max_wave_chains;
-    p.chain_rows = order.chain_rows;
-    p.reserve_chains = order.reserve_chains;
     if (p.trace_dev) { (void)hipFree(p.trace_dev); p.trace_dev = nullptr; }      // (profiling aid: sized by the ticket count)
+    HIP_TRY(dag_plan_install(p, order, bands, stream));
     HIP_TRY(hipMemcpyAsync(p.tasks_dev, p.tasks_host.data(), sizeof(int4) * p.tasks_host.size(), hipMemcpyHostToDevice, stream));
-    HIP_TRY(dag_plan_mid(p, mid, stream));
-    HIP_TRY(dag_plan_shrow(p, stream));
     return OISAT_OK;
 }
 
