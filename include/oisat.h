@@ -610,7 +610,9 @@ int oisat_dag_task_order(int nsys, const int32_t* block_rows, int wave, int32_t*
 /* ... and of the ENVELOPED launch of one system of nb <= 1024 block rows (oisat_potrf_env): first = its envelope, far = its
  * far stretch (oisat_factor_far) or NULL.  A bulk task's first word is kind | k0 << 8 | kfar << 18 (ten bits each): its
  * K-loop runs over the block columns k0 = first[i] .. kend - 1 (kend = j, PRE: j - 1), the blocks k0 .. kfar - 1 of it on
- * the bf16 pipe, k0 <= kfar = clamp(far[i]) <= kend. */
+ * the bf16 pipe, k0 <= kfar = clamp(far[i]) <= kend.  Profiling aid, this query only: OISAT_DAG_ORDER_LEAD_FAR = a number in
+ * [0, 1) gives the order a far list would have at that ticket lead (tools/dag_sched_model.py); anything else is OISAT_EINVAL.
+ * No launch reads it. */
 int oisat_dag_task_order_env(int nb, const int32_t* first, const int32_t* far, int32_t* tasks_out, int64_t capacity,
                              int64_t* ntasks_out);
 

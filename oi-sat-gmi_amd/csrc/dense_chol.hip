@@ -2682,11 +2682,10 @@ extern "C" int oisat_factor_shadow_tile(oisat_ctx* h, int r, int k, uint16_t* hi
     std::vector<uint16_t> raw((size_t)kShTile / 2);
     HIP_TRY(hipMemcpyAsync(raw.data(), h->shadow_last + (h->shadow_shrow[r] + k) * kShTile, (size_t)kShTile, hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
-    for (int plane = 0; plane < 2; ++plane)                     // plane [half][row][64 columns] -> row-major 128 x 128
-        for (int half = 0; half < 2; ++half)
+    for (int plane = 0; plane < 2; ++plane)                     // plane [group][row][16 columns] -> row-major 128 x 128
+        for (int g = 0; g < NB / 16; ++g)
             for (int row = 0; row < NB; ++row)
-                memcpy((plane ? lo_out : hi_out) + row * NB + half * 64, raw.data() + (plane * kShPlane + half * kShHalf + row * 128) / 2,
-                       128);
+                memcpy((plane ? lo_out : hi_out) + row * NB + g * 16, raw.data() + (plane * kShPlane + g * kShGroup + row * 32) / 2, 32);
     return OISAT_OK;
 }
 
@@ -2696,8 +2695,16 @@ extern "C" int oisat_dag_task_order_env(int nb, const int32_t* first, const int3
     ARG_CHECK(envelope_table_ok(first, nb));
     if (far)
         for (int i = 0; i < nb; ++i) ARG_CHECK(far[i] >= first[i] && far[i] <= i);
+    // Profiling aid, this query only (no launch reads it): OISAT_DAG_ORDER_LEAD_FAR = the order a far list would have at
+    // another ticket lead, 0 <= lead < 1 -- tools/dag_sched_model.py sets a traced launch's lead beside that launch's costs.
+    double lead_far = kDagEnvLeadFar;
+    if (const char* e = getenv("OISAT_DAG_ORDER_LEAD_FAR")) {
+        char* end = nullptr;
+        lead_far = strtod(e, &end);
+        ARG_CHECK(end != e && *end == 0 && lead_far >= 0.0 && lead_far < 1.0 && "OISAT_DAG_ORDER_LEAD_FAR is a number in [0, 1)");
+    }
     DagOrder order;
-    dag_task_order(std::vector<int>{nb}, 0, order, first, far);
+    dag_task_order(std::vector<int>{nb}, 0, order, first, far, lead_far);
     *ntasks_out = (int64_t)order.tasks.size();
     if ((int64_t)order.tasks.size() > capacity) return capacity == 0 ? OISAT_OK : OISAT_EINVAL;
     memcpy(tasks_out, order.tasks.data(), sizeof(int4) * order.tasks.size());

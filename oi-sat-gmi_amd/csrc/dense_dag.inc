@@ -167,83 +167,169 @@ __device__ __forceinline__ void dag_split8(const float4& a, const float4& b, dag
 // two stretches DMA them (dag_seg_sh): the same operand bits into the same MFMAs in the same order as the in-loop
 // conversions (dag_seg_bf16 / dag_seg_bf16x2) -- the factor does not change by a bit.
 // Layout of a shadow tile (kShTile = 64 KiB, tiles of a block row consecutive in k; DagSys::shadow): two PLANES, hi then lo,
-// each [half h = 0, 1][row 0 .. 127][64 columns 64 h .. 64 h + 63] in bf16 -- rows of 128 bytes, a 64-column step of 16 KiB
-// contiguous.  Only LDS-DMA reads it and every lane gives its own 16-byte source, so
-//   * a FAR K-step is 64 columns deep in the LDS footprint of dag_seg's 32: one contiguous 16 KiB step of the hi plane per
-//     operand, whole cache lines, half the round trips of the in-loop conversion and half its bytes; the image row is 8 chunks
-//     of 8 columns, k-chunk c of a lane is the logical chunk 2 c + fh: one ds_read_b128 where the conversion has two and four packs;
-//   * a MIDDLE K-step stays 32 columns: an image row is hi of the 32 columns (logical chunks 0 .. 3, 64 bytes of the hi plane's
-//     row) | their lo (chunks 4 .. 7, from the lo plane); k-chunk c is the chunks 2 c + fh and 4 + 2 c + fh.
-// Both images keep dag_seg's 16-byte XOR swizzle (physical chunk = logical ^ (row & 7)), and the fragment reads are
-// dag_seg's pattern with another constant under the XOR -- a bijection of the chunks of a row, so the reads are spread over
-// the 64 banks exactly as swz_sweep found for the fp32 image.  No cache line holds parts of two tiles.
+// each [group g = 0 .. 7][row 0 .. 127][16 columns 16 g .. 16 g + 15] in bf16 -- a group is 4 KiB contiguous, 32 bytes per
+// row.  Only LDS-DMA reads it, in UNITS of 16 KiB of LDS, [A | B][128 rows x 64 bytes], whose source is contiguous per operand:
+//   * a FAR unit is 32 columns of the hi plane, two consecutive groups (8 KiB contiguous): the image row is 4 chunks of 8
+//     columns, k-chunk c = 0, 1 of a lane is the logical chunk 2 c + fh -- one ds_read_b128 where the conversion has two and
+//     four packs, and two bytes fetched per element where it has four;
+//   * a MIDDLE unit is 16 columns: group g of the hi plane (logical chunks 0, 1 of the image row) | group g of the lo plane
+//     (chunks 2, 3); its one k-chunk is the chunks fh (hi) and 2 + fh (lo).
+// A tile is 4 far units or 8 middle ones.  The LDS side of an LDS-DMA is lane-linear, so the swizzle is on the SOURCE: lane l
+// of a piece of 16 rows lands at physical chunk l & 3 of row l >> 2 and fetches the logical chunk (l & 3) ^ ((row >> 2) & 3);
+// a fragment read takes logical chunk q of its row at physical chunk q ^ ((row >> 2) & 3).  Checked by enumeration against
+// the lane groups a ds_read_b128 is served in ({0-3, 12-15, 20-27}, {4-11, 16-19, 28-31} and the same + 32; bank = (byte / 4)
+// mod 64): the 16 rows of a group are four rows of each residue mod 4 -- which picks the 64-byte quarter of the 256-byte
+// bank row -- and their (row >> 2) & 3 are {0, 3, 1, 2} / {1, 2, 0, 3}, four different chunks of that quarter: every group
+// covers the 64 banks exactly once, for every q.  (row & 3, dag_seg's rule for 128-byte rows scaled down, would be 4-way.)
+// No cache line holds parts of two tiles.
 // Tried and not kept: the images BEHIND the publish of rowfin, announced by a progress word of their own that the shadow
 // segments poll instead, with the chain's images converted from its LDS image under the rank-128 update's MFMAs.  The chain's
 // panel step went back from 15.3 to 12.8 us, but its rank-128 update rose from 7.8 to 10.3 us and its diagonal block from 22.9
 // to 24.8 us: the headline step was the same to 0.1 ms, for a fourth progress array and a second writer.
 constexpr int64_t kShTile = 65536;                              // bytes of a shadow tile
-constexpr int kShPlane = 32768, kShHalf = 16384;                // ... of a plane, of a 64-column half of a plane
-// lane's DMA source inside the shadow tile at `tile` (row wid*32 + rl, logical chunk lc of the image row): far | middle (SPLIT)
+constexpr int kShPlane = 32768, kShGroup = 4096;                // ... of a plane, of a 16-column group of a plane
+constexpr int kShUnit = 16384;                                  // bytes of a unit in LDS; the workgroup's image holds four
+// The segment's RING: kShRing stages of 4 / kShRing units each, kShAhead stages' DMAs in flight while one is consumed.
+// 2 | 1: one 32 KiB stage ahead, every wait a vmcnt(0) -- the default.  4 | 3: three half-size stages ahead, counted waits;
+// 4 | 2: the shallower pipeline of the same stages.  All three were measured from these two constants (4 | 2: kShAhead = 2; profiles/EXPERIMENTS.md,
+// "A ring of four stages"): at lead 0.2 4 | 3 is 0.36 ms of the headline step ahead of 2 | 1 and missed the bar set for it; at the
+// lead that ships the two measure the same.
+constexpr int kShRing = 2;
+constexpr int kShAhead = kShRing - 1;
+constexpr int kShStageUnits = 4 / kShRing;
+constexpr int kShStagePieces = 4 * kShStageUnits;               // LDS-DMA instructions per wave and stage: 2 per operand and unit
+static_assert((kShRing == 2 || kShRing == 4) && kShAhead >= 1 && kShAhead < kShRing, "a stage is refilled one barrier behind its last read");
+static_assert(kShStagePieces * kShAhead <= 63, "vmcnt is six bits");
+// lane's DMA source inside the shadow tile at `tile`: row wid*32 + (lane >> 2) of the tile's first unit, far | middle (SPLIT)
 template <bool SPLIT>
 __device__ __forceinline__ const char* dag_sh_src(const char* tile, const DagLane& L) {
-    return tile + (L.wid * 32 + L.rl) * 128 + (SPLIT ? 16 * (L.lc & 3) + (L.lc >> 2) * kShPlane : 16 * L.lc);
+    const int q = (L.lane & 3) ^ ((L.lane >> 4) & 3);           // (the pieces start at multiples of 16 rows: (row >> 2) & 3 = (lane >> 4) & 3)
+    return tile + (q >> 1) * (SPLIT ? kShPlane : kShGroup) + (L.wid * 32 + (L.lane >> 2)) * 32 + (q & 1) * 16;
 }
-
-// One K-segment over the shadow: SPLIT = the middle stretch's split products (else the far stretch's single ones).  Ad / Bd:
-// dag_sh_src<SPLIT> of the segment's first tile of each operand row.  A far K-step is 64 columns (two per tile, four k-chunks),
-// a middle one 32 (four per tile, two k-chunks).  Barriers and look-ahead as in dag_seg_bf16, the twelve MFMAs of a split
-// k-chunk in dag_seg_bf16x2's order.
-template <bool SPLIT>
-__device__ __forceinline__ int64_t dag_sh_step(int kt) {        // byte offset of K-step kt from the segment's first
-    if (!SPLIT) return (int64_t)(kt >> 1) * kShTile + (kt & 1) * kShHalf;
-    return (int64_t)(kt >> 2) * kShTile + ((kt >> 1) & 1) * kShHalf + (kt & 1) * 64;
-}
-// the bf16 fragment(s) of k-chunk c of an operand row (`row`: the row's start in an operand image; logical chunk q holds 8 columns)
-template <bool SPLIT>
-__device__ __forceinline__ void dag_sh_frag(const float* row, const DagLane& L, int c, dag_bf16x8& hi, dag_bf16x8& lo) {
-    hi = *reinterpret_cast<const dag_bf16x8*>(row + 4 * ((2 * c + L.fh) ^ L.sw));
-    if (SPLIT) lo = *reinterpret_cast<const dag_bf16x8*>(row + 4 * ((4 + 2 * c + L.fh) ^ L.sw));
-}
-#define DAG_MFMA4_BF16(A0, A1, B0, B1)                                                          \
-    acc00 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A0, B0, acc00, 0, 0, 0);                    \
-    acc01 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A0, B1, acc01, 0, 0, 0);                    \
-    acc10 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A1, B0, acc10, 0, 0, 0);                    \
-    acc11 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A1, B1, acc11, 0, 0, 0);
-template <bool SPLIT>
-__device__ __forceinline__ void dag_seg_sh(float* __restrict__ lds, const DagLane& L, const char* Ad, const char* Bd, int nkt, f32x16& acc00,
-                                           f32x16& acc01, f32x16& acc10, f32x16& acc11) {
-    constexpr int64_t sa = 128, sb = 128;                       // bytes between the rows of a shadow plane
-    constexpr int IMG = NB * BK;
-    constexpr int NCHUNK = SPLIT ? 2 : 4;                // k-chunks of 16 columns per K-step
-    dag_dma(lds, 0, L, Ad, sa, Bd, sb);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    for (int kt = 0; kt < nkt; ++kt) {
-        const int cur = kt & 1;
-        if (kt + 1 < nkt) {                                     // the other buffer is free since the last barrier
-            const int64_t off = dag_sh_step<SPLIT>(kt + 1);
-            dag_dma(lds, cur ^ 1, L, Ad + off, sa, Bd + off, sb);
-        }
+// LDS-DMA of one unit into unit slot `us` of the image: wave `wid` brings rows wid*32 + 16 i .. + 15 (i = 0, 1) of each operand,
+// one KiB per instruction.  a / b: dag_sh_src of the unit.
+__device__ __forceinline__ void dag_sh_dma(float* __restrict__ lds, int us, const DagLane& L, const char* a, const char* b) {
+    typedef __attribute__((address_space(1))) const void* gptr_t;
+    typedef __attribute__((address_space(3))) void* lptr_t;
 #pragma unroll
-        for (int c = 0; c < NCHUNK; ++c) {
-            const float* A = lds + (cur * 2 + 0) * IMG;
-            const float* B = lds + (cur * 2 + 1) * IMG;
-            dag_bf16x8 a0, a0l, a1, a1l, b0, b0l, b1, b1l;
-            dag_sh_frag<SPLIT>(A + L.arow, L, c, a0, a0l);
-            dag_sh_frag<SPLIT>(A + L.arow + 32 * BK, L, c, a1, a1l);
-            dag_sh_frag<SPLIT>(B + L.brow, L, c, b0, b0l);
-            dag_sh_frag<SPLIT>(B + L.brow + 32 * BK, L, c, b1, b1l);
-            if (SPLIT) {
-                DAG_MFMA4_BF16(a0l, a1l, b0, b1)
-                DAG_MFMA4_BF16(a0, a1, b0l, b1l)
-            }
+    for (int i = 0; i < 2; ++i) {
+        __builtin_amdgcn_global_load_lds((gptr_t)(a + 512 * i), (lptr_t)(lds + us * (kShUnit / 4) + (L.wid * 32 + 16 * i) * 16), 16, 0, 0);
+        __builtin_amdgcn_global_load_lds((gptr_t)(b + 512 * i), (lptr_t)(lds + us * (kShUnit / 4) + kShUnit / 8 + (L.wid * 32 + 16 * i) * 16), 16, 0, 0);
+    }
+}
+// The fragment reads are written out as instructions.  Left to the compiler, every ds_read behind an LDS-DMA that it cannot
+// prove disjoint gets an s_waitcnt vmcnt(0) in front of it -- the whole ring would drain at the first read of every stage
+// (it did so in the two-buffer loop this replaced: its look-ahead never overlapped anything).  The compiler then no longer
+// counts these reads either: dag_lds_wait retires them, and takes the fragments as operands so that nothing that uses
+// them moves in front of it.  What nothing enforces: to the compiler a fragment is complete at the read's asm statement, so a
+// register copy or a spill of it placed between the read and its wait would move stale data.  The generated gfx950 code has
+// reads, lgkmcnt, MFMAs and no move in between (0 spilled VGPRs); at a compiler upgrade the bit-equality tests
+// (tests/test_gpu_seg_pipeline.py, test_gpu_factor_shadow.py) are the guard, and the .s is worth a look.
+template <int OFF>
+__device__ __forceinline__ dag_u32x4 dag_lds_rd(unsigned addr) {
+    dag_u32x4 v;
+    asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(v) : "v"(addr), "n"(OFF) : "memory");
+    return v;
+}
+template <int N>
+__device__ __forceinline__ void dag_lds_wait(dag_u32x4& a, dag_u32x4& b, dag_u32x4& c, dag_u32x4& d) {
+    asm volatile("s_waitcnt lgkmcnt(%4)" : "+v"(a), "+v"(b), "+v"(c), "+v"(d) : "n"(N) : "memory");
+}
+__device__ __forceinline__ void dag_lds_wait_all(dag_u32x4& a, dag_u32x4& b, dag_u32x4& c, dag_u32x4& d, dag_u32x4& e, dag_u32x4& f, dag_u32x4& g,
+                                                 dag_u32x4& h) {
+    asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(a), "+v"(b), "+v"(c), "+v"(d), "+v"(e), "+v"(f), "+v"(g), "+v"(h) : : "memory");
+}
+template <int N>
+__device__ __forceinline__ void dag_vm_wait() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
+// the workgroup barrier of the ring: LDS traffic only -- __syncthreads() would drain the DMAs in flight
+__device__ __forceinline__ void dag_ring_barrier() {
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_s_barrier();
+}
+template <int N> struct DagInt { static constexpr int value = N; };
+
+// One K-segment over the shadow, nkb K-blocks (tiles) long: SPLIT = the middle stretch's split products (else the far
+// stretch's single ones).  Ad / Bd: dag_sh_src<SPLIT> of the segment's first tile of each operand row.  The same operand bits
+// into the same MFMAs in the same order as dag_seg_bf16 / dag_seg_bf16x2: k-chunk by k-chunk, the twelve MFMAs of a split
+// k-chunk in dag_seg_bf16x2's order.
+// INVARIANT: a tile is 4 far or 8 middle units, so a segment is a whole number of turns of the ring -- it starts and ends on
+// ring slot 0, the kShAhead stages of the prologue always exist, and the loop body is half a turn -- 32 KiB of the image, whose
+// slots differ from a constant by the turn's half (the code holds every MFMA as often as the loop it replaced).
+// Phase s (stage s is in LDS and every wave is past the barrier behind the wait that retired it): issue stage s + kShAhead
+// into the slot whose last reads were retired in front of the previous barrier; read and consume stage s; wait until at most
+// kShAhead - 1 stages are in flight, i.e. this wave's pieces of stage s + 1 have landed; barrier.  The last stages drain
+// with smaller counts, the last wait is vmcnt(0): on return everything has landed, every read is back and every wave is
+// past a barrier, as after dag_seg.  On entry no wave reads or fills the image and this wave has no load in flight whose
+// result the compiler still waits for (callers: a join or a segment's last barrier is behind every wave).
+#define DAG_MFMA4_BF16(A0, A1, B0, B1)                                                          \
+    acc00 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(DAG_BF(A0), DAG_BF(B0), acc00, 0, 0, 0);    \
+    acc01 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(DAG_BF(A0), DAG_BF(B1), acc01, 0, 0, 0);    \
+    acc10 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(DAG_BF(A1), DAG_BF(B0), acc10, 0, 0, 0);    \
+    acc11 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(DAG_BF(A1), DAG_BF(B1), acc11, 0, 0, 0);
+#define DAG_BF(X) __builtin_bit_cast(dag_bf16x8, X)
+template <bool SPLIT>
+__device__ __forceinline__ void dag_seg_sh(float* __restrict__ lds, const DagLane& L, const char* Ad, const char* Bd, int nkb, f32x16& acc00,
+                                           f32x16& acc01, f32x16& acc10, f32x16& acc11) {
+    constexpr int UPT = SPLIT ? 8 : 4;                          // units per tile
+    constexpr int64_t USTEP = SPLIT ? kShGroup : 2 * kShGroup;  // bytes between a tile's units in the source
+    constexpr int U = kShStageUnits, P = kShStagePieces;
+    const int nst = __builtin_amdgcn_readfirstlane(nkb) * (UPT / U);    // stages; a multiple of kShRing (wave-uniform: the waits below are scalar branches)
+    // fragment addresses: logical chunks fh and 2 + fh of the lane's row of each operand, in unit slot 0
+    typedef __attribute__((address_space(3))) const void* lcptr_t;
+    const unsigned sw = 16 * (L.fh ^ ((L.frow >> 2) & 3));
+    const unsigned a_row = (unsigned)(uintptr_t)(lcptr_t)lds + (L.wr * 64 + L.frow) * 64;
+    const unsigned b_row = (unsigned)(uintptr_t)(lcptr_t)lds + kShUnit / 2 + (L.wc * 64 + L.frow) * 64;
+    const unsigned a_q0 = a_row + sw, a_q1 = a_row + (sw ^ 32u), b_q0 = b_row + sw, b_q1 = b_row + (sw ^ 32u);
+    auto issue = [&](int s) {                                   // stage s into its ring slot
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const int n = s * U + u;                            // unit n of the segment
+            const int64_t off = (int64_t)(n / UPT) * kShTile + (n % UPT) * USTEP;
+            dag_sh_dma(lds, (s % kShRing) * U + u, L, Ad + off, Bd + off);
+        }
+    };
+    auto unit = [&](auto us, unsigned turn) {                   // the k-chunk(s) of the unit in unit slot `us` (+ turn bytes)
+        constexpr int O = decltype(us)::value * kShUnit;
+        const unsigned pa0 = a_q0 + turn, pa1 = a_q1 + turn, pb0 = b_q0 + turn, pb1 = b_q1 + turn;
+        dag_u32x4 a0 = dag_lds_rd<O>(pa0), a1 = dag_lds_rd<O + 32 * 64>(pa0);
+        dag_u32x4 b0 = dag_lds_rd<O>(pb0), b1 = dag_lds_rd<O + 32 * 64>(pb0);
+        dag_u32x4 c0 = dag_lds_rd<O>(pa1), c1 = dag_lds_rd<O + 32 * 64>(pa1);
+        dag_u32x4 d0 = dag_lds_rd<O>(pb1), d1 = dag_lds_rd<O + 32 * 64>(pb1);
+        if (!SPLIT) {                                           // two k-chunks: (a, b), then (c, d)
+            dag_lds_wait<4>(a0, a1, b0, b1);                    // (LDS reads return in order)
+            DAG_MFMA4_BF16(a0, a1, b0, b1)
+            dag_lds_wait<0>(c0, c1, d0, d1);
+            DAG_MFMA4_BF16(c0, c1, d0, d1)
+        } else {                                                // one k-chunk: a, b = hi, c, d = lo
+            dag_lds_wait_all(a0, a1, b0, b1, c0, c1, d0, d1);
+            DAG_MFMA4_BF16(c0, c1, b0, b1)
+            DAG_MFMA4_BF16(a0, a1, d0, d1)
             DAG_MFMA4_BF16(a0, a1, b0, b1)
         }
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");        // this wave's DMA pieces of K-step kt+1 have landed ...
-        __syncthreads();                                        // ... everyone else's too; every read of K-step kt is back
+    };
+    auto phase = [&](auto r, int s, unsigned turn) {            // stage s, in ring slot r + (turn ? kShRing / 2 : 0)
+        constexpr int R = decltype(r)::value;
+        if (s + kShAhead < nst) issue(s + kShAhead);
+        unit(DagInt<R * U>{}, turn);
+        if constexpr (U == 2) unit(DagInt<R * U + U - 1>{}, turn);
+        const int left = nst - 2 - s;                           // stages behind s + 1 that exist
+        if (left >= kShAhead - 1) dag_vm_wait<P * (kShAhead - 1)>();
+        else if (kShAhead >= 3 && left == 1) dag_vm_wait<P>();
+        else dag_vm_wait<0>();
+        dag_ring_barrier();
+    };
+#pragma unroll
+    for (int s = 0; s < kShAhead; ++s) issue(s);
+    dag_vm_wait<P * (kShAhead - 1)>();
+    dag_ring_barrier();
+    for (int s = 0; s < nst; s += kShRing / 2) {                // half a turn, 32 KiB of the image, per iteration
+        const unsigned turn = ((s / (kShRing / 2)) & 1) * 2 * kShUnit;
+        phase(DagInt<0>{}, s, turn);
+        if constexpr (kShRing == 4) phase(DagInt<1>{}, s + 1, turn);
     }
 }
 #undef DAG_MFMA4_BF16
+#undef DAG_BF
 __device__ __forceinline__ void dag_seg_bf16(float* __restrict__ lds, const DagLane& L, const float* Ad, int64_t lda, const float* Bd, int64_t ldb,
                                              int nkt, f32x16& acc00, f32x16& acc01, f32x16& acc10, f32x16& acc11) {
     typedef __attribute__((address_space(1))) const void* gptr_t;
@@ -340,8 +426,14 @@ __device__ __forceinline__ void dag_seg_bf16x2(float* __restrict__ lds, const Da
 }
 
 // The writer: the final tile held in the accumulators -> its two planes at `tile` (a shadow tile).  Through LDS, so that the
-// stores are coalesced 16-byte ones: a wave's 64 x 64 quadrant is 64 whole 128-byte rows of half wc of each plane, 8 KiB
-// contiguous in memory, and it stages them in the two 8 KiB pieces of the image that dag_acc_to_image gives the same wave
+// stores are coalesced 16-byte ones: a wave's 64 x 64 quadrant is rows 64 wr .. + 63 of the groups 4 wc .. + 3 of each plane,
+// four runs of 2 KiB contiguous in memory, and it stages them -- [group][row][16 columns], the memory order -- in the two 8 KiB
+// pieces of the image that dag_acc_to_image gives the same wave.  Banks of the 2-byte staging writes (32 banks of 4 bytes, by
+// enumeration of a write's 64 lanes): 16 consecutive lanes share 8 banks pairwise in one dword; lanes frow and frow + 16 are
+// 2 KiB apart and fh = 0, 1 are 128 bytes apart, both multiples of the 128-byte bank row -- 4 dwords per bank where the
+// [row][64 columns] staging this replaced had 2.  Not swizzled away: the staging order is the memory order so that the
+// reads below stay linear; the cost shows in the chain's panel phase and the tile tasks' tail, both reported with the ring
+// (profiles/EXPERIMENTS.md, "A ring of four stages")
 // (disjoint between waves: no barrier, the wave's own LDS accesses complete in order).  Every element is rounded as the
 // in-loop variants round it: hi by v_cvt_pk_bf16_f32 (nearest even), lo = the same rounding of a - float(hi).  Stores are
 // write-through (`sc1`) like the epilogue's and are drained by the vmcnt(0) of the caller's dag_publish.  On entry no wave
@@ -353,7 +445,7 @@ __device__ __forceinline__ void dag_shadow_store(float* __restrict__ lds, const 
     unsigned short* lo = reinterpret_cast<unsigned short*>(lds + (L.wc * 2 + 1) * IMG + L.wr * (IMG / 2));
 #define DAG_SH_PUT(ACC, i, j)                                                                           \
     _Pragma("unroll") for (int e = 0; e < 16; ++e) {                                                    \
-        const int at = ((i) * 32 + (e & 3) + 8 * (e >> 2) + 4 * L.fh) * 64 + (j) * 32 + L.frow;         \
+        const int at = ((j) * 2 + (L.frow >> 4)) * 1024 + ((i) * 32 + (e & 3) + 8 * (e >> 2) + 4 * L.fh) * 16 + (L.frow & 15); \
         const float a = ACC[e];                                                                         \
         const unsigned h = dag_pk_bf16(a, a);                                                           \
         const float rest = a - __builtin_bit_cast(float, h << 16);                                      \
@@ -367,13 +459,13 @@ __device__ __forceinline__ void dag_shadow_store(float* __restrict__ lds, const 
 #undef DAG_SH_PUT
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");          // (also keeps the compiler from moving the reads below over the 2-byte writes)
     const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void*)tile, (short)0, (int)kShTile, 0x00020000);
-    const int voff = L.wc * kShHalf + L.wr * (kShHalf / 2) + L.lane * 16;
+    const int voff = L.wc * 4 * kShGroup + L.wr * (kShGroup / 2) + L.lane * 16;
 #pragma unroll
     for (int n = 0; n < 8; ++n) {
         const dag_u32x4 vh = *reinterpret_cast<const dag_u32x4*>(reinterpret_cast<const char*>(hi) + n * 1024 + L.lane * 16);
         const dag_u32x4 vl = *reinterpret_cast<const dag_u32x4*>(reinterpret_cast<const char*>(lo) + n * 1024 + L.lane * 16);
-        __builtin_amdgcn_raw_buffer_store_b128(vh, rs, voff, n * 1024, 16);
-        __builtin_amdgcn_raw_buffer_store_b128(vl, rs, voff, kShPlane + n * 1024, 16);
+        __builtin_amdgcn_raw_buffer_store_b128(vh, rs, voff, (n >> 1) * kShGroup + (n & 1) * 1024, 16);
+        __builtin_amdgcn_raw_buffer_store_b128(vl, rs, voff, kShPlane + (n >> 1) * kShGroup + (n & 1) * 1024, 16);
     }
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");          // the staging reads are back: the pieces may be rewritten
 }
@@ -495,7 +587,7 @@ __device__ __forceinline__ bool dag_tile_task(const DagSys& sy, int kind, int k0
         if (FAR && k < kfar) {                                  // a segment ends where the far stretch does
             kav = kav < kfar ? kav : kfar;
             if (shA && (sy.shuse & 1))
-                dag_seg_sh<false>(lds, L, dag_sh_src<false>(shA + k * kShTile, L), dag_sh_src<false>(shB + k * kShTile, L), (kav - k) * 2,
+                dag_seg_sh<false>(lds, L, dag_sh_src<false>(shA + k * kShTile, L), dag_sh_src<false>(shB + k * kShTile, L), kav - k,
                                         acc00, acc01, acc10, acc11);
             else
                 dag_seg_bf16(lds, L, dag_src(Arow + (int64_t)k * NB, sy.ld, L), sy.ld, dag_src(Brow + (int64_t)k * NB, sy.ld, L), sy.ld,
@@ -503,7 +595,7 @@ __device__ __forceinline__ bool dag_tile_task(const DagSys& sy, int kind, int k0
         } else if (FAR && k < kmid) {                           // ... and where the middle stretch does
             kav = kav < kmid ? kav : kmid;
             if (shA && (sy.shuse & 2))
-                dag_seg_sh<true>(lds, L, dag_sh_src<true>(shA + k * kShTile, L), dag_sh_src<true>(shB + k * kShTile, L), (kav - k) * 4,
+                dag_seg_sh<true>(lds, L, dag_sh_src<true>(shA + k * kShTile, L), dag_sh_src<true>(shB + k * kShTile, L), kav - k,
                                        acc00, acc01, acc10, acc11);
             else
                 dag_seg_bf16x2(lds, L, dag_src(Arow + (int64_t)k * NB, sy.ld, L), sy.ld, dag_src(Brow + (int64_t)k * NB, sy.ld, L), sy.ld,
@@ -624,6 +716,10 @@ __device__ __forceinline__ bool dag_chain_task(const DagSys& sy, DagCtl* ctl, in
     __builtin_amdgcn_s_setprio(3);                              // where this workgroup shares its CU: the arbiter serves the chain first
     for (int j = 0; j < sy.nb; ++j) {
         if (ctr && t == 0) ctr[8 * j + 0] = wall_clock64();
+#ifdef OISAT_TEST_HOOKS
+        if (L.flags & 512)                                      // (profiling aid: every chain step ~5 us longer -- 4 x 47 x 64 clocks at 2.4 GHz)
+            for (int n = 0; n < 4; ++n) __builtin_amdgcn_s_sleep(47);
+#endif
         dag_chain_diag(sy, j, info, lds, L, sv, ctl);
         if (ctr && t == 0) ctr[8 * j + 1] = wall_clock64();
         if (j + 1 == sy.nb) break;
@@ -1282,7 +1378,10 @@ struct DagOrder {
 };
 constexpr int kDagWave = 8;                                     // systems per wave of small systems (12, 16, 24 and 48 measure the same to 0.2 ms of a month's 48.7)
 constexpr double kDagEnvLead = 0.15;                            // enveloped systems: columns a task is drawn early per block of its K-loop (below)
-constexpr double kDagEnvLeadFar = 0.2;                          // ... where part of the K-loops is a far stretch on the bf16 pipe (below)
+constexpr double kDagEnvLeadFar = 0.3;                          // ... where part of the K-loops is a far stretch on the bf16 pipe (below).
+// (0.3: the minimum of a sweep 0.15 .. 0.5 that ran on the 4 | 3 ring, whose far / middle K-blocks are cheaper than those of the 2 | 1 ring
+// that ships; on 2 | 1 only 0.2 against 0.3 is measured: 67.5 - 67.7 -> 66.2 - 66.4 ms.  profiles/EXPERIMENTS.md, "A ring of four stages":
+// the sweep is still to be repeated on 2 | 1.)
 constexpr int kDagWave0Max = 64;                                // wave 0 holds at most this many chains
 // Envelope (first != nullptr: ONE system whose rows are in an order that makes it a band, first[i] = first block column of
 // block row i that can be non-zero, non-decreasing, first[i] <= max(i - 1, 0)).  A Cholesky factor has no fill left of its
@@ -1302,7 +1401,9 @@ constexpr int kDagWave0Max = 64;                                // wave 0 holds 
 // list by dag_plan_install) and a task clamps kmid = mid[i] into [kfar, kend] with one scalar load.  The ticket ORDER does not
 // depend on it.
 constexpr int kDagEnvMaxBlocks = 1024;
-void dag_task_order(const std::vector<int>& nb_of, int wave_arg, DagOrder& out, const int* first = nullptr, const int* far = nullptr) {
+// lead_far: kDagEnvLeadFar for every launch; the query oisat_dag_task_order_env alone may be given another (its comment).
+void dag_task_order(const std::vector<int>& nb_of, int wave_arg, DagOrder& out, const int* first = nullptr, const int* far = nullptr,
+                    double lead_far = kDagEnvLeadFar) {
     const int nsys = (int)nb_of.size();
     // Ticket order.  Systems are taken in WAVES.  The BIG systems -- those with at least half the block rows of the largest
     // (a month's polar caps; at most 64) -- go two at a time, the others (table order, largest first) eight at a time.  A
@@ -1349,7 +1450,7 @@ void dag_task_order(const std::vector<int>& nb_of, int wave_arg, DagOrder& out, 
     tasks.clear();
     bool any_far = false;
     for (int i = 0; first && far && i < nb_of[0]; ++i) any_far = any_far || far[i] > first[i];
-    const double env_lead = any_far ? kDagEnvLeadFar : kDagEnvLead;
+    const double env_lead = any_far ? lead_far : kDagEnvLead;
     int chain_rows = 0;                                         // (.z of a chain task: first row of its stamps in the trace)
     int max_wave_chains = 0, second = 0;
     struct Item { double key; int4 task; };
@@ -1386,6 +1487,9 @@ void dag_task_order(const std::vector<int>& nb_of, int wave_arg, DagOrder& out, 
                 // With the middle stretch behind it (kFactorMidBits = 8: another 35 % of the K-blocks at ~0.6 of their fp32 time) the sweep
                 // was repeated: lead 0.15 / 0.2 / 0.25 / 0.3 / 0.4 = 75.4, 75.5 / 74.4 / 74.2 / 74.4 / 74.8 ms per step.  0.2 .. 0.3 are level
                 // within 0.2 ms: 0.2 stays, no third constant, and the order does not read the middle table.
+                // With the shadow and its segments' reads no longer draining their DMA (far 2.83, middle 5.01 us per K-block on the 4 | 3
+                // ring): lead 0.15 / 0.2 / 0.25 / 0.3 / 0.4 / 0.5 = 70.2 / 67.8, 67.7 / 67.1 / 66.5 / 66.9 / 67.7 ms per step; no flat stretch,
+                // 0.3 is kept (the note at kDagEnvLeadFar: swept on 4 | 3; on the 2 | 1 ring that ships 0.2 -> 0.3 is 67.6 -> 66.3 ms).
                 auto ekey = [&](int i, int jj) { return ((double)jj - env_lead * (double)(jj - first[i])) / (double)nb; };
                 // PRE(j) reads row j up to column j - 2 only (the chain adds column j - 1 itself), so it is drawn ONE COLUMN EARLY,
                 // in front of column j - 1's tasks: drawn with column j it was what a small system's chain waited for at every

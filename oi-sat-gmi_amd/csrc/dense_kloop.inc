@@ -7,7 +7,8 @@ struct DagLane {                 // a thread's fixed coordinates in the 128x128 
     int lane, wid, wr, wc, rl, lc, frow, fh, sw, arow, brow;
     int flags;                   // 0 in the product.  Only the -DOISAT_TEST_HOOKS build of the library (liboisat_hip_testhooks.so, loaded
                                  // by tests/test_gpu_dag.py alone) reads OISAT_DAG_FLAGS: 128 = fault injection -- no chain announces a
-                                 // diagonal block from block 3 on (the waiters time out); 256 = polls give up after 4096 spins
+                                 // diagonal block from block 3 on (the waiters time out); 256 = polls give up after 4096 spins;
+                                 // 512 = every chain step sleeps ~5 us (tools/chain_sensitivity.py)
     unsigned spin;               // polls before a wait gives up (kDagSpinMax)
 };
 
