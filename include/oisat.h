@@ -456,6 +456,19 @@ int oisat_factor_mid(const double* lat_sorted, int64_t m, double g, const int32_
 int oisat_set_correlation(oisat_ctx* h, int kind);
 int oisat_corr_eval(int kind, double g, const double* d2, int64_t n, double* out);
 int oisat_corr_cut_chord(int kind, double g, double bits, double* chord_out);
+/* The far tier of the float64 sums (Gaussian only; csrc/dense_solve_dev.inc: kSolveFarBits): the increment
+ * and the compact-block residual evaluate an observation whose correlation with every point of a workgroup's block is below
+ * 2^-bits in fp32 and add the block's fp32 partial sum to the float64 one.  By default the increment does so at 2^-28 and the residual
+ * does not.  OISAT_SOLVE_FAR_BITS=<b> in the environment (read at every call): 0 = no tier (every pair in float64, the fields
+ * of the code before the tier, byte for byte), 0 < b <= 52 = the tier at 2^-b in both (at 52 the far radius is the cull's: the list stays empty); anything else is OISAT_EINVAL
+ * of the call.
+ * oisat_solve_tier_counts (host only): for ONE block of points pts_xyz = x[npts] | y[npts] | z[npts] (unit vectors) and the
+ * observations obs_xyz = x[m] | y[m] | z[m], the number of observations the block evaluates in float64 (near_out) and in fp32
+ * (far_out); the rest is culled.  olat = the observations' latitudes, ascending, with [lat_lo, lat_hi] the latitude span of the
+ * block's points (the kernels' window), or NULL: no window, no cull, nothing far.  bits as in the variable; < 0 = the library's
+ * current setting.  Either out pointer may be NULL. */
+int oisat_solve_tier_counts(int kind, double g, double bits, const double* pts_xyz, int64_t npts, const double* obs_xyz, int64_t m,
+                            const double* olat, double lat_lo, double lat_hi, int64_t* near_out, int64_t* far_out);
 int oisat_envelope_corr(int kind, const double* lat_sorted, int64_t m, double g, int32_t* env_out);
 int oisat_factor_envelope_corr(int kind, const double* lat_sorted, int64_t m, double g, int32_t* env_out);
 int oisat_factor_far_corr(int kind, const double* lat_sorted, int64_t m, double g, const int32_t* first, int32_t* far_out);

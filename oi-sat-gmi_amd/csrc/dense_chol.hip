@@ -3185,12 +3185,18 @@ extern "C" int oisat_batch_analyse(oisat_ctx* h, int batch_id, int dtype, double
     sv.g2 = g2;
     sv.win_deg = lat_window_deg(OISAT_CORR_GAUSSIAN, g);
     sv.cut_chord = cut_chord_of(OISAT_CORR_GAUSSIAN, g);
+    double far_chord;
+    ARG_CHECK(far_chord_of(OISAT_CORR_GAUSSIAN, g, &far_chord));
+    sv.far_chord = (float)far_chord;
+    double far_chord_resid;                                 // the residual's: the same chord, or none (far_chord_of)
+    ARG_CHECK(far_chord_of(OISAT_CORR_GAUSSIAN, g, &far_chord_resid, -1.0, false));
     sv.tol2 = h->refine_tol * h->refine_tol;
     sv.refine = refine;
     sv.dtype = dtype;
     sv.cells = increment_cells(h->cu_count, bt.max_n, nmem);
     sv.blocks = residual_blocks_pay(OISAT_CORR_GAUSSIAN, g) ? 1 : 0;
     for (const SolveMember& sm : bt.solve_host) sv.blocks = sv.blocks && sm.perm != nullptr;
+    if (sv.blocks && far_chord_resid < 1e9) sv.blocks |= 2;
     sv.trsv_timeouts = (unsigned*)base;
     sv.nsys = nmem;
     if (!bt.dag_solve || bt.dag_solve_refine != refine || bt.dag_solve_cells != sv.cells) {

@@ -152,7 +152,7 @@ __global__ __launch_bounds__(256) void cov_residual_blocks_kernel(const double* 
                                                                    const double* __restrict__ d, const double* __restrict__ z,
                                                                    double* __restrict__ r, const double* __restrict__ olat, double win_deg,
                                                                    const int* __restrict__ converged, const SolveMember* __restrict__ mem,
-                                                                   const int* __restrict__ perm, double cut_chord) {
+                                                                   const int* __restrict__ perm, double cut_chord, double far_chord) {
     if (BATCH) {                                                // batched: blockIdx.y = member, r = its padded right-hand side
         const SolveMember* mb = mem + blockIdx.y;
         m = mb->m;
@@ -169,7 +169,7 @@ __global__ __launch_bounds__(256) void cov_residual_blocks_kernel(const double* 
     }
     SOLVE_LDS(W);
     if (converged != nullptr && *converged != 0) return;       // the refinement has met its tolerance: nothing left to evaluate
-    resid_compact_block<KIND, false>(oxyz, osig, ovar, m, g, d, z, r, olat, win_deg, perm, cut_chord, (int64_t)blockIdx.x, W);
+    resid_compact_block<KIND, false>(oxyz, osig, ovar, m, g, d, z, r, olat, win_deg, perm, cut_chord, far_chord, (int64_t)blockIdx.x, W);
 }
 
 // ---- inc_i = sig_i * sum_a C(i,a) w_a ; xa = xb + inc (dense_solve_dev.inc: increment_patch); blockIdx.x = patch / run ----
@@ -181,7 +181,7 @@ __global__ __launch_bounds__(256) void apply_increment_kernel(const double* __re
                                                                const T* __restrict__ xb, T* __restrict__ xa, T* __restrict__ inc,
                                                                const double* __restrict__ glat, const double* __restrict__ olat,
                                                                double win_deg, const SolveMember* __restrict__ mem, int nx,
-                                                               double cut_chord) {
+                                                               double cut_chord, double far_chord) {
     if (BATCH) {                                                // batched: blockIdx.y = member
         const SolveMember* mb = mem + blockIdx.y;
         n = mb->n;
@@ -198,7 +198,7 @@ __global__ __launch_bounds__(256) void apply_increment_kernel(const double* __re
         if (glat != nullptr) { glat = mb->glat; olat = mb->olat; }      // (non-null = "use the latitude window")
     }
     SOLVE_LDS(W);
-    increment_patch<KIND, T, CELLS>(gxyz, gsig, n, oxyz, osig, z, m, g2, xb, xa, inc, glat, olat, win_deg, nx, cut_chord, (int64_t)blockIdx.x, W);
+    increment_patch<KIND, T, CELLS>(gxyz, gsig, n, oxyz, osig, z, m, g2, xb, xa, inc, glat, olat, win_deg, nx, cut_chord, far_chord, (int64_t)blockIdx.x, W);
 }
 
 // launch KERNEL<KIND, ...> for the handle's correlation model (h->corr, oisat_set_correlation): one instantiation per model,
@@ -234,6 +234,53 @@ extern "C" int oisat_corr_eval(int kind, double g, const double* d2, int64_t n, 
 extern "C" int oisat_corr_cut_chord(int kind, double g, double bits, double* chord_out) {
     ARG_CHECK((kind == OISAT_CORR_GAUSSIAN || kind == OISAT_CORR_GASPARI_COHN) && g > 0.0 && bits >= 1.0 && chord_out);
     *chord_out = cut_chord(kind, g, bits);
+    return OISAT_OK;
+}
+
+// Host restatement of block_sphere + stage_near<true> for ONE block of points (an increment patch's cells, a compact residual
+// block's rows): how many observations the block stages into its near and into its far list.  pts_xyz = x[npts] | y[npts] |
+// z[npts], obs_xyz likewise with m; olat (ascending, or NULL: no window, hence no cull and no far tier) and the block's latitude
+// span [lat_lo, lat_hi] give the candidate range as in the kernels.  bits: the far tier's (0 = off, < 0 = the library's
+// setting).  The centre is summed point by point here and by a tree on the device: a count can differ by an observation that
+// sits on a radius to the last bit.
+extern "C" int oisat_solve_tier_counts(int kind, double g, double bits, const double* pts_xyz, int64_t npts, const double* obs_xyz, int64_t m,
+                                       const double* olat, double lat_lo, double lat_hi, int64_t* near_out, int64_t* far_out) {
+    ARG_CHECK((kind == OISAT_CORR_GAUSSIAN || kind == OISAT_CORR_GASPARI_COHN) && g > 0.0 && pts_xyz && npts > 0 && obs_xyz && m > 0);
+    ARG_CHECK(bits <= kCutBits && lat_lo <= lat_hi);
+    double far_chord;
+    ARG_CHECK(far_chord_of(kind, g, &far_chord, bits));
+    const double win = lat_window_deg(kind, g);
+    const bool windowed = olat != nullptr && win < 180.0;
+    int64_t j0 = 0, j1 = m;
+    if (windowed) {
+        j0 = std::lower_bound(olat, olat + m, lat_lo - win) - olat;
+        j1 = std::lower_bound(olat, olat + m, lat_hi + win + 1e-9) - olat;
+    }
+    double sx = 0.0, sy = 0.0, sz = 0.0;
+    for (int64_t i = 0; i < npts; ++i) { sx += pts_xyz[i]; sy += pts_xyz[npts + i]; sz += pts_xyz[2 * npts + i]; }
+    const double nrm = sqrt(sx * sx + sy * sy + sz * sz);
+    double r2cull = 1e30, r2far = (double)INFINITY, cx = 0.0, cy = 0.0, cz = 0.0;
+    if (nrm > 1e-9 && windowed) {
+        cx = sx / nrm; cy = sy / nrm; cz = sz / nrm;
+        double r2 = 0.0;
+        for (int64_t i = 0; i < npts; ++i) {
+            const double dx = pts_xyz[i] - cx, dy = pts_xyz[npts + i] - cy, dz = pts_xyz[2 * npts + i] - cz;
+            r2 = std::max(r2, dx * dx + dy * dy + dz * dz);
+        }
+        const double rho = sqrt(r2) * (1.0 + 1e-12) + 1e-12;
+        const double rr = cut_chord_of(kind, g) + rho, rf = far_chord + rho;
+        r2cull = rr * rr;
+        if (far_chord < 1e9) r2far = rf * rf;
+    }
+    int64_t nnear = 0, nfar = 0;
+    for (int64_t c = j0; c < j1; ++c) {
+        const double dx = obs_xyz[c] - cx, dy = obs_xyz[m + c] - cy, dz = obs_xyz[2 * m + c] - cz;
+        const double q2 = dx * dx + dy * dy + dz * dz;
+        if (!(q2 <= r2cull)) continue;
+        if (q2 >= r2far) ++nfar; else ++nnear;
+    }
+    if (near_out) *near_out = nnear;
+    if (far_out) *far_out = nfar;
     return OISAT_OK;
 }
 
@@ -341,8 +388,10 @@ int oisat_cov_residual_if(oisat_ctx* h, const double* oxyz, const double* osig, 
     const double win = lat_window_deg(kind, g);
     const double gk = corr_scale(kind, g);                  // what the kernels take: g | kz2
     if (perm && olat_sorted && residual_blocks_pay(kind, g)) {
+        double far_chord;
+        ARG_CHECK(far_chord_of(kind, g, &far_chord, -1.0, false));
         OISAT_LAUNCH_CORR(h, "cov_residual", cov_residual_blocks_kernel, false, dim3((unsigned)cdiv(m, 64)), dim3(256), 0, oxyz, osig, ovar, m,
-                          gk, d, z, r_out, olat_sorted, win, converged_dev, (const SolveMember*)nullptr, perm, cut_chord_of(kind, g));
+                          gk, d, z, r_out, olat_sorted, win, converged_dev, (const SolveMember*)nullptr, perm, cut_chord_of(kind, g), far_chord);
         return OISAT_OK;
     }
     // fewer than two blocks of 64 rows per CU (m < 32,768 on 256 CUs): the column range is cut into slices, a workgroup per
@@ -384,8 +433,11 @@ template <typename T, int CELLS, bool BATCH>
 static int increment_launch(oisat_ctx* h, unsigned gx, unsigned gy, const double* gxyz, const double* gsig, int64_t n, int nx, const double* oxyz,
                             const double* osig, const double* z, int64_t m, double g, const void* xb, void* xa, void* inc,
                             const double* glat, const double* olat, double win, const SolveMember* mem) {
+    double far_chord;
+    ARG_CHECK(far_chord_of(h->corr, g, &far_chord));
     OISAT_LAUNCH_CORR(h, "apply_increment", apply_increment_kernel, OISAT_TARGS(T, CELLS, BATCH), dim3(gx, gy), dim3(256), 0, gxyz, gsig, n, oxyz,
-                      osig, z, m, corr_scale2(h->corr, g), (const T*)xb, (T*)xa, (T*)inc, glat, olat, win, mem, nx, cut_chord_of(h->corr, g));
+                      osig, z, m, corr_scale2(h->corr, g), (const T*)xb, (T*)xa, (T*)inc, glat, olat, win, mem, nx, cut_chord_of(h->corr, g),
+                      far_chord);
     return OISAT_OK;
 }
 
@@ -432,10 +484,12 @@ int oisat_cov_residual_batched(oisat_ctx* h, const SolveMember* mem_dev, const s
     bool blocks = residual_blocks_pay(kind, g);
     for (const SolveMember& sm : mem_host) blocks = blocks && sm.perm != nullptr;
     if (blocks) {
+        double far_chord;
+        ARG_CHECK(far_chord_of(kind, g, &far_chord, -1.0, false));
         OISAT_LAUNCH_CORR(h, "cov_residual", cov_residual_blocks_kernel, true, dim3((unsigned)cdiv(max_m, 64), (unsigned)nmem), dim3(256), 0,
                           (const double*)nullptr, (const double*)nullptr, (const double*)nullptr, (int64_t)0, gk, (const double*)nullptr,
                           (const double*)nullptr, (double*)nullptr, (const double*)nullptr, win, (const int*)nullptr, mem_dev, (const int*)nullptr,
-                          cut_chord_of(kind, g));
+                          cut_chord_of(kind, g), far_chord);
         return OISAT_OK;
     }
     static const double dummy = 0.0;                        // non-null marker: "use each member's latitude window"

@@ -770,8 +770,11 @@ struct DagSolve {
     const SolveMember* mem;      // table order (the order of DagSys)
     unsigned long long* queue;   // [qcap][2]: (kind | system << 32), (index | round << 32); zero = not written yet
     double g, g2, win_deg, cut_chord, tol2;
-    int refine, dtype, cells, blocks;       // blocks: residual on compact blocks of rows (every member has its permutation)
+    int refine, dtype, cells, blocks;       // blocks: residual on compact blocks of rows (every member has its permutation);
+                                            // | 2: with the far tier at far_chord (off unless OISAT_SOLVE_FAR_BITS asks for it)
     int nsys, qcap, qcap0;                  // entries [0, qcap0) belong to queue 0 (sweep rows), [qcap0, qcap) to queue 1
+    float far_chord;                        // far_chord_of() beside cut_chord: a float by construction, in what was padding (the
+                                            // launches without solve tasks keep their argument block byte for byte)
     unsigned* trsv_timeouts;                // status slot 7
     // the launch that factors ONE system and runs its first forward sweep (DAG_SOLVE_FWD, oisat_potrf_env_fwd): the padded
     // right-hand side, the forward vector ("not yet published") and the factor's envelope first[nb] | last[nb] (or nullptr)
@@ -1008,7 +1011,8 @@ __device__ __forceinline__ bool dag_res_task(const DagSys& sy, const SolveMember
     __builtin_amdgcn_s_setprio(1);                              // VALU work beside a tile task's MFMA wave: first at the issue port (the MFMA wave
     const SolveLds W = solve_lds_carve(lds);                    // issues one instruction per 64 cycles of its pipe and loses nothing)
     if (sv.blocks)
-        resid_compact_block<OISAT_CORR_GAUSSIAN, true>(mb.oxyz, mb.osig, mb.ovar, mb.m, sv.g, mb.d, mb.z, mb.rhs, mb.olat, sv.win_deg, mb.perm, sv.cut_chord, (int64_t)c, W);
+        resid_compact_block<OISAT_CORR_GAUSSIAN, true>(mb.oxyz, mb.osig, mb.ovar, mb.m, sv.g, mb.d, mb.z, mb.rhs, mb.olat, sv.win_deg, mb.perm, sv.cut_chord,
+                                                       (sv.blocks & 2) ? (double)sv.far_chord : (double)INFINITY, (int64_t)c, W);
     else
         resid_rows_block<OISAT_CORR_GAUSSIAN, true>(mb.oxyz, mb.osig, mb.ovar, mb.m, sv.g, mb.d, mb.z, mb.rhs, sv.win_deg < 180.0 ? mb.olat : (const double*)nullptr,
                                sv.win_deg, (double*)nullptr, 1, 0, (int64_t)c, W);
@@ -1091,10 +1095,10 @@ __device__ __forceinline__ bool dag_inc_task(const DagSys& sy, const SolveMember
     const double* olat = windowed ? mb.olat : (const double*)nullptr;
     if (sv.cells == 1)
         increment_patch<OISAT_CORR_GAUSSIAN, T, 1>(mb.gxyz, mb.gsig, mb.n, mb.oxyz, mb.osig, mb.z, mb.m, sv.g2, (const T*)mb.xb, (T*)mb.xa, (T*)mb.inc, glat, olat,
-                              sv.win_deg, mb.nx, sv.cut_chord, (int64_t)blk, W);
+                              sv.win_deg, mb.nx, sv.cut_chord, (double)sv.far_chord, (int64_t)blk, W);
     else
         increment_patch<OISAT_CORR_GAUSSIAN, T, 2>(mb.gxyz, mb.gsig, mb.n, mb.oxyz, mb.osig, mb.z, mb.m, sv.g2, (const T*)mb.xb, (T*)mb.xa, (T*)mb.inc, glat, olat,
-                              sv.win_deg, mb.nx, sv.cut_chord, (int64_t)blk, W);
+                              sv.win_deg, mb.nx, sv.cut_chord, (double)sv.far_chord, (int64_t)blk, W);
     __builtin_amdgcn_s_setprio(0);
     __syncthreads();
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");            // (a later generation may overwrite these fields: this one's stores are out first)

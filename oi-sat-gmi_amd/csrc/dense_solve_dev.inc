@@ -9,6 +9,20 @@ constexpr float kLog2e = 1.4426950408889634f;
 // last bit of a term of correlation 1, and a sum's terms cancel to ~1/500 of their absolute sum at swath densities, so what
 // is dropped stays below 1e-12 of the result (rounds 1-3 used 2^-64: 19 % more pairs for nothing measurable).
 constexpr double kCutBits = 52.0;
+// The far tier of the Gaussian's float64 sums (increment, compact-block residual): an observation whose correlation with EVERY
+// point of a workgroup's block is below 2^-kSolveFarBits is evaluated in fp32 -- coordinates, |p - q|^2, v_exp_f32, product --
+// into an fp32 partial sum per flush of the staging buffer, which is then added to the double accumulator.  Such a term is at
+// most 2^-bits of a near one, so its fp32 relative error (~2e-5: the coordinates' rounding through the argument, v_exp_f32's
+// ulp) is 2^-bits 2e-5 of a near term.  Gaspari-Cohn has no far tier.  On by default in the increment; the residual has it
+// behind the variable only (far_chord_of).  OISAT_SOLVE_FAR_BITS=<b> (read at every call): 0 = off, every pair in float64, the
+// bits of the code before the tier; up to 52 = the tier at 2^-b in both kernels (at 52 the far radius is the cull's own or just
+// beyond it: the tier's code runs and its list stays empty).  The value is a measurement, by the protocol of kFactorFarBits
+// (profiles/EXPERIMENTS.md, "The solve phase's far tier"): on four months 16 bits is the smallest value that leaves the refinement's residuals (three digits) and the fp32
+// fields (one ulp of the largest entry, fewer elements than the factor's two schedules move) where they were; but the FLOAT64
+// fields of oisat_apply_increment are held to 1e-13 of their largest entry against the sum over every pair
+// (tests/test_gpu_parity.py: test_latitude_window_equals_the_full_sum), which 20 bits miss by a factor 3 and 24 bits meet:
+// 24 is the smallest admissible value, kept with 4 bits of headroom.
+constexpr double kSolveFarBits = 28.0;
 
 // ---- the correlation model ------------------------------------------------------------------------------------------
 // KIND = OISAT_CORR_GAUSSIAN (0): C = exp(-g d^2), d = |p - q| the chord.  KIND = OISAT_CORR_GASPARI_COHN (1): the compactly
@@ -116,12 +130,20 @@ __device__ __forceinline__ int64_t lower_bound_lat(const double* __restrict__ a,
 // line in it.  The survivors are compacted in candidate order (wave ballots), so the sums keep a fixed order.
 // (The residual kernel's blocks are 64 consecutive observations in LATITUDE order -- all around the globe in longitude -- so a
 // sphere around them culls nothing; it keeps the plain window.)
-struct BlockSphere { double cx, cy, cz, r2cull; };
+// a block-uniform double, moved to scalar registers (the far tier's radius beside the four words every thread already holds)
+__device__ __forceinline__ double uniform_f64(double v) {
+    return __hiloint2double(__builtin_amdgcn_readfirstlane(__double2hiint(v)), __builtin_amdgcn_readfirstlane(__double2loint(v)));
+}
+// r2far: the far tier's squared radius, (chord(kSolveFarBits) + rho)^2 with the cull's safety margins: an observation at least
+// that far from c is at least chord(bits) from every point of the block.  +inf (nothing is far) where there is no cull (no
+// centre, no window), where the tier is off (far_chord = +inf: far_chord_of) and for every model but the Gaussian.
+struct BlockSphere { double cx, cy, cz, r2cull, r2far; };
 
 // centre and cull radius of the block's live points (px, py, pz per thread and slot; every thread calls this)
 template <int SLOTS>
 __device__ __forceinline__ BlockSphere block_sphere(const double (&px)[SLOTS], const double (&py)[SLOTS], const double (&pz)[SLOTS],
-                                                    const bool (&live)[SLOTS], double cut_chord, double* __restrict__ red /*[16] shared*/) {
+                                                    const bool (&live)[SLOTS], double cut_chord, double far_chord,
+                                                    double* __restrict__ red /*[16] shared*/) {
     const int t = threadIdx.x, lane = t & 63, w = t >> 6;
     double sx = 0.0, sy = 0.0, sz = 0.0;
 #pragma unroll
@@ -144,6 +166,7 @@ __device__ __forceinline__ BlockSphere block_sphere(const double (&px)[SLOTS], c
     if (!(nrm > 1e-9)) {                                        // points all around the sphere (or none): keep everything
         b.cx = b.cy = b.cz = 0.0;
         b.r2cull = 1e30;
+        b.r2far = __builtin_inf();
         return b;
     }
     b.cx = sx / nrm; b.cy = sy / nrm; b.cz = sz / nrm;
@@ -162,37 +185,96 @@ __device__ __forceinline__ BlockSphere block_sphere(const double (&px)[SLOTS], c
     r2 = fmax(fmax(red[12], red[13]), fmax(red[14], red[15]));
     const double rr = cut_chord + sqrt(r2) * (1.0 + 1e-12) + 1e-12;
     b.r2cull = cut_chord < 1e9 ? rr * rr : 1e30;
+    const double rf = far_chord + sqrt(r2) * (1.0 + 1e-12) + 1e-12;
+    b.r2far = uniform_f64(cut_chord < 1e9 && far_chord < 1e9 ? rf * rf : __builtin_inf());
     return b;
 }
 
 constexpr int kStage = 768;                                     // staged observations: processed once 512 have gathered
 
-// one pass of 256 candidates [c0, c0 + 256) /\ [.., j1): the near ones go to buf[fill ..) in candidate order; returns the new fill
+// one pass of 256 candidates [c0, c0 + 256) /\ [.., j1): the near ones go to buf[fill ..) in candidate order; returns the new fill.
+// FAR (the Gaussian's far tier): the survivors at least sqrt(bs.r2far) from the centre go to a second list instead, float4
+// {x, y, z, sig * z_solve}, in candidate order too and by the same ballots and prefix sums (a wave's two counts share one word
+// of wcnt: near in the low half, far in the high half; neither passes 64, no sum of them 256).  The far list grows from the BACK
+// of the same buffer, in the slots the near list has not reached: entry k is the 16 bytes of bzw[kStage - 1 - k / 2] (k even) or
+// bxy[kStage - 1 - k / 2] (k odd) -- far_entry().  A near entry takes one slot of either array, two far entries take one of
+// either, so the lists fit while 2 near + far <= 2 kStage = 1536; a pass adds at most 256 survivors, i.e. at most 512 to that
+// weight, hence the callers' flush rule: process both lists once 2 near + far >= 1024 (with an empty far list: near >= 512,
+// the rule before the tier), or behind the last pass.  A rule of the counts alone: the sums' order does not depend on timing.
+template <bool FAR>
 __device__ __forceinline__ int stage_near(const double* __restrict__ oxyz, const double* __restrict__ osig, const double* __restrict__ z,
                                           int64_t m, int64_t c0, int64_t j1, const BlockSphere& bs, double2* __restrict__ bxy,
-                                          double2* __restrict__ bzw, int fill, int* __restrict__ wcnt /*[4] shared*/) {
+                                          double2* __restrict__ bzw, int fill, int& ffill, int* __restrict__ wcnt /*[4] shared*/) {
     const int t = threadIdx.x, lane = t & 63, w = t >> 6;
     const int64_t c = c0 + t;
     double x = 0.0, y = 0.0, zz = 0.0;
-    bool near = false;
+    bool near = false, far = false;
     if (c < j1) {
         x = oxyz[c]; y = oxyz[m + c]; zz = oxyz[2 * m + c];
         const double dx = x - bs.cx, dy = y - bs.cy, dz = zz - bs.cz;
-        near = dx * dx + dy * dy + dz * dz <= bs.r2cull;
+        const double q2 = dx * dx + dy * dy + dz * dz;
+        near = q2 <= bs.r2cull;
+        if (FAR) {
+            far = near && q2 >= bs.r2far;
+            near = near && !far;
+        }
     }
     const unsigned long long mask = __ballot(near);
-    if (lane == 0) wcnt[w] = __popcll(mask);
+    const unsigned long long fmask = FAR ? __ballot(far) : 0ull;
+    if (lane == 0) wcnt[w] = FAR ? (__popcll(mask) | (__popcll(fmask) << 16)) : __popcll(mask);
     __syncthreads();
     const int c0w = wcnt[0], c1w = wcnt[1], c2w = wcnt[2], c3w = wcnt[3];
-    const int base = fill + (w > 0 ? c0w : 0) + (w > 1 ? c1w : 0) + (w > 2 ? c2w : 0);
+    const int before = (w > 0 ? c0w : 0) + (w > 1 ? c1w : 0) + (w > 2 ? c2w : 0);
+    const int base = fill + (FAR ? (before & 0xffff) : before);
     if (near) {
         const int pos = base + __popcll(mask & ((1ull << lane) - 1ull));
         bxy[pos] = make_double2(x, y);
         bzw[pos] = make_double2(zz, osig[c] * z[c]);
     }
+    if (FAR && far) {
+        const int k = ffill + (before >> 16) + __popcll(fmask & ((1ull << lane) - 1ull));
+        reinterpret_cast<float4*>((k & 1) ? bxy : bzw)[kStage - 1 - (k >> 1)] = make_float4((float)x, (float)y, (float)zz, (float)(osig[c] * z[c]));
+    }
     __syncthreads();
-    return fill + c0w + c1w + c2w + c3w;
+    const int all = c0w + c1w + c2w + c3w;
+    if (FAR) {
+        ffill += all >> 16;
+        return fill + (all & 0xffff);
+    }
+    return fill + all;
 }
+// the two lists are due: see stage_near
+template <bool FAR>
+__device__ __forceinline__ bool stage_full(int fill, int ffill) { return FAR ? 2 * fill + ffill >= 1024 : fill >= 512; }
+// far entry k of the staging buffer (stage_near)
+__device__ __forceinline__ float4 far_entry(const double2* __restrict__ bxy, const double2* __restrict__ bzw, int k) {
+    return reinterpret_cast<const float4*>((k & 1) ? bxy : bzw)[kStage - 1 - (k >> 1)];
+}
+
+// Two far pairs in packed fp32 (v_pk_add / v_pk_mul / v_pk_fma_f32, two v_exp_f32): sum + 2^(-g2 |p - q|^2) w per lane.  The lanes
+// are the thread's two cells against one observation (increment, CELLS = 2) or one point against two observations.
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ f32x2 far_pairs(f32x2 dx, f32x2 dy, f32x2 dz, float g2, f32x2 w, f32x2 sum) {
+    const f32x2 x = (dx * dx + dy * dy + dz * dz) * -g2;
+    f32x2 e;
+    e.x = __builtin_amdgcn_exp2f(x.x);
+    e.y = __builtin_amdgcn_exp2f(x.y);
+    return e * w + sum;
+}
+// one point (ax, ay, az) against far entries o0 and o1
+__device__ __forceinline__ f32x2 far_pairs_of(float ax, float ay, float az, const float4& o0, const float4& o1, float g2, f32x2 sum) {
+    const f32x2 dx = {ax - o0.x, ax - o1.x}, dy = {ay - o0.y, ay - o1.y}, dz = {az - o0.z, az - o1.z}, w = {o0.w, o1.w};
+    return far_pairs(dx, dy, dz, g2, w, sum);
+}
+// v, opaque to the optimiser: what a far loop derives from it (fp32 copies of the coordinates, LDS addresses) is formed where the
+// loop runs, once per flush, and does not sit in registers across the float64 loop, whose occupancy the far tier must not cost.
+// Nothing but the compiler's register allocation depends on these: a compiler that hoists across them anyway costs waves, not
+// bits.  If `make asm` shows the Gaussian apply_increment_kernel above 96 VGPRs (two cells) / 80 (one) or
+// cov_residual_blocks_kernel above 80 -- occupancy 5 / 6 / 6, recorded in profiles/EXPERIMENTS.md -- look here and at
+// uniform_f64 first: the values to keep out of the float64 loops' live ranges are fx, fy, fz, g2 and the far list's addresses.
+__device__ __forceinline__ double far_local(double v) { asm volatile("" : "+v"(v)); return v; }
+__device__ __forceinline__ int far_local(int v) { asm volatile("" : "+v"(v)); return v; }
+__device__ __forceinline__ int far_local_uniform(int v) { asm volatile("" : "+s"(v)); return v; }
 
 // 2^x for x <= 0 in double to 2e-10 relative: x = n + f, |f| <= 1/2, 2^f = e^(f ln 2) by a degree-8 polynomial, 2^n by ldexp
 __device__ __forceinline__ double exp2_neg(double x) {
@@ -216,6 +298,31 @@ __device__ __forceinline__ double exp2_neg(double x) {
 // tasks of the task-graph launch, so that the two paths do the same arithmetic) ------------------------------------------------
 // chord beyond which the correlation is below 2^-kCutBits (the same cut-off as the latitude window's)
 static inline double cut_chord_of(int kind, double g) { return cut_chord(kind, g, kCutBits); }
+// chord from which a pair belongs to the far tier (kSolveFarBits), passed beside cut_chord_of by every launch of the increment
+// and of the compact-block residual; +inf = no far tier: another model than the Gaussian, or bits = 0.  bits < 0: the library's setting, kSolveFarBits or OISAT_SOLVE_FAR_BITS.  false: the variable
+// holds something else than a number in [0, 52].  default_on = false (the compact-block residual, whose tier did not earn its
+// place at kSolveFarBits -- profiles/EXPERIMENTS.md): a tier only where the variable asks for one.  The chord is rounded UP to
+// a float (the correlation there is no larger than 2^-bits): the task-graph launch carries it as one, in the padding of its argument block (DagSolve), and every path takes the
+// same value.
+static inline bool far_chord_of(int kind, double g, double* chord_out, double bits = -1.0, bool default_on = true) {
+    if (bits < 0.0) {
+        bits = default_on ? kSolveFarBits : 0.0;
+        const char* e = getenv("OISAT_SOLVE_FAR_BITS");
+        if (e && *e) {
+            char* end = nullptr;
+            bits = strtod(e, &end);
+            if (end == e || *end != '\0' || !(bits >= 0.0 && bits <= kCutBits)) return false;
+        }
+    }
+    const bool on = kind == OISAT_CORR_GAUSSIAN && bits > 0.0 && bits <= kCutBits;
+    *chord_out = (double)INFINITY;
+    if (on) {
+        const double chord = cut_chord(kind, g, bits);
+        const float f = (float)chord;
+        *chord_out = (double)f >= chord ? (double)f : (double)nextafterf(f, INFINITY);
+    }
+    return true;
+}
 // The compact-block residual pays where the covariance's reach is small against the domain: measured at 720x1440 / 1e5
 // observations, L = 300 km (reach 2 800 km): 6.6 -> 4.6 ms; a month's 50 tiles: 1.69 -> 1.59 ms; at 360x720 / 1e4 observations,
 // L = 500 km (reach 4 700 km) the staging costs more than the cull saves: 0.21 -> 0.26 ms.
@@ -339,12 +446,17 @@ __device__ __forceinline__ void resid_rows_block(const double* __restrict__ oxyz
 // sphere and keeps, while staging the candidates into LDS, only the observations within the covariance's reach of it -- the
 // increment's cull (block_sphere / stage_near).  Per row: the same terms in the same (latitude) order, four column phases
 // combined in a fixed order; terms below 2^-kCutBits of a term left out.
+// Gaussian: the staged observations that are far from the whole block (stage_near<true>) are evaluated in packed fp32, every
+// fourth entry of the far list per column phase like the near list, two entries per step in the two lanes of a partial sum
+// that joins the phase's double sum behind each flush (lane 0, then lane 1).  far_chord = +inf: no such entry, the same bits
+// as without the tier.
 template <int KIND, bool AGENT>
 __device__ __forceinline__ void resid_compact_block(const double* __restrict__ oxyz, const double* __restrict__ osig,
                                                     const double* __restrict__ ovar, int64_t m, double g, const double* __restrict__ d,
                                                     const double* __restrict__ z, double* __restrict__ r, const double* __restrict__ olat,
-                                                    double win_deg, const int* __restrict__ perm, double cut_chord, int64_t blk,
-                                                    const SolveLds& W) {
+                                                    double win_deg, const int* __restrict__ perm, double cut_chord, double far_chord,
+                                                    int64_t blk, const SolveLds& W) {
+    constexpr bool FAR = KIND == OISAT_CORR_GAUSSIAN;
     double (*part)[64] = (double (*)[64])W.part;
     const int t = threadIdx.x;
     const int lr = t & 63, ph = t >> 6;
@@ -363,19 +475,33 @@ __device__ __forceinline__ void resid_compact_block(const double* __restrict__ o
     const int64_t j1 = lower_bound_lat(olat, m, W.s_hi[0] + win_deg + 1e-9);
     const double sx1[1] = {ax}, sy1[1] = {ay}, sz1[1] = {az};
     const bool lv1[1] = {live && ph == 0};
-    const BlockSphere bs = block_sphere<1>(sx1, sy1, sz1, lv1, cut_chord, W.red);
+    const BlockSphere bs = block_sphere<1>(sx1, sy1, sz1, lv1, cut_chord, FAR ? far_chord : (double)INFINITY, W.red);
     double acc = 0.0;
-    int fill = 0;
-    for (int64_t c0 = j0; c0 < j1 || fill > 0; c0 += 256) {
-        if (c0 < j1) fill = stage_near(oxyz, osig, z, m, c0, j1, bs, W.bxy, W.bzw, fill, W.wcnt);
-        if (fill >= 512 || c0 + 256 >= j1) {                    // block-uniform
+    int fill = 0, ffill = 0;
+    for (int64_t c0 = j0; c0 < j1 || fill > 0 || ffill > 0; c0 += 256) {
+        if (c0 < j1) fill = stage_near<FAR>(oxyz, osig, z, m, c0, j1, bs, W.bxy, W.bzw, fill, ffill, W.wcnt);
+        if (stage_full<FAR>(fill, ffill) || c0 + 256 >= j1) {  // block-uniform
             for (int j = ph; j < fill; j += 4) {                // column phase ph takes every fourth staged observation
                 const double2 oxy = W.bxy[j];
                 const double2 ozw = W.bzw[j];
                 const double dx = ax - oxy.x, dy = ay - oxy.y, dz = az - ozw.x;
                 acc += corr_f64<KIND>(g, dx * dx + dy * dy + dz * dz) * ozw.y;
             }
+            if (FAR && ffill > 0) {                             // block-uniform; g is the Gaussian's: the far terms are 2^(-g2 d^2) w
+                const float fx = (float)far_local(ax), fy = (float)far_local(ay), fz = (float)far_local(az);
+                const float g2 = (float)(far_local(g) * (double)kLog2e);
+                f32x2 fs = {0.0f, 0.0f};
+                int k = far_local(ph);
+                for (; k + 4 < ffill; k += 8) fs = far_pairs_of(fx, fy, fz, far_entry(W.bxy, W.bzw, k), far_entry(W.bxy, W.bzw, k + 4), g2, fs);
+                if (k < ffill) {                                // an odd entry: its twin with weight 0
+                    const float4 o = far_entry(W.bxy, W.bzw, k);
+                    fs = far_pairs_of(fx, fy, fz, o, make_float4(o.x, o.y, o.z, 0.0f), g2, fs);
+                }
+                acc += (double)fs.x;
+                acc += (double)fs.y;
+            }
             fill = 0;
+            ffill = 0;
             __syncthreads();
         }
     }
@@ -403,8 +529,9 @@ __device__ __forceinline__ void increment_patch(const double* __restrict__ gxyz,
                                                 const double* __restrict__ oxyz, const double* __restrict__ osig,
                                                 const double* __restrict__ z, int64_t m, double g2, const T* __restrict__ xb,
                                                 T* __restrict__ xa, T* __restrict__ inc, const double* __restrict__ glat,
-                                                const double* __restrict__ olat, double win_deg, int nx, double cut_chord, int64_t blk,
-                                                const SolveLds& W) {
+                                                const double* __restrict__ olat, double win_deg, int nx, double cut_chord, double far_chord,
+                                                int64_t blk, const SolveLds& W) {
+    constexpr bool FAR = KIND == OISAT_CORR_GAUSSIAN;
     constexpr int PW = 32, PH = CELLS * 8;
     const int t = threadIdx.x;
     int64_t cell[CELLS];
@@ -458,11 +585,15 @@ __device__ __forceinline__ void increment_patch(const double* __restrict__ gxyz,
         j0 = W.s_j[0];
         j1 = W.s_j[1];
     }
-    const BlockSphere bs = block_sphere<CELLS>(px, py, pz, live, windowed ? cut_chord : 1e30, W.red);
-    int fill = 0;
-    for (int64_t c0 = j0; c0 < j1 || fill > 0; c0 += 256) {
-        if (c0 < j1) fill = stage_near(oxyz, osig, z, m, c0, j1, bs, W.bxy, W.bzw, fill, W.wcnt);
-        if (fill >= 512 || c0 + 256 >= j1) {                    // block-uniform
+    BlockSphere bs = block_sphere<CELLS>(px, py, pz, live, windowed ? cut_chord : 1e30, FAR ? far_chord : (double)INFINITY, W.red);
+    if (FAR) {                                                  // (the same values: registers for the far loop, at the old occupancy)
+        bs.cx = uniform_f64(bs.cx); bs.cy = uniform_f64(bs.cy); bs.cz = uniform_f64(bs.cz);
+        bs.r2cull = uniform_f64(bs.r2cull);
+    }
+    int fill = 0, ffill = 0;
+    for (int64_t c0 = j0; c0 < j1 || fill > 0 || ffill > 0; c0 += 256) {
+        if (c0 < j1) fill = stage_near<FAR>(oxyz, osig, z, m, c0, j1, bs, W.bxy, W.bzw, fill, ffill, W.wcnt);
+        if (stage_full<FAR>(fill, ffill) || c0 + 256 >= j1) {  // block-uniform
 #pragma unroll 4
             for (int j = 0; j < fill; ++j) {
                 const double2 oxy = W.bxy[j];
@@ -479,7 +610,41 @@ __device__ __forceinline__ void increment_patch(const double* __restrict__ gxyz,
                     acc[q] += corr_f64_exp2<KIND>(g2, dx * dx + dy * dy + dz * dz) * ozw.y;
                 }
             }
+            // The far list (stage_near<true>; Gaussian only): every correlation between such an observation and a cell of this
+            // patch is below 2^-kSolveFarBits, so the term's fp32 error (coordinates, argument, v_exp_f32: ~1e-5 of it) is that
+            // much below the near terms' own.  Packed fp32, an fp32 partial sum per cell and flush, in list order; two cells =
+            // the two lanes, one cell = two consecutive entries per step (lane 0 the even ones), joined lane 0 first.
+            if (FAR && ffill > 0) {                             // block-uniform
+                const float fg2 = (float)far_local(g2);
+                if (CELLS == 2) {
+                    const f32x2 fx = {(float)far_local(px[0]), (float)far_local(px[CELLS - 1])},
+                                fy = {(float)far_local(py[0]), (float)far_local(py[CELLS - 1])},
+                                fz = {(float)far_local(pz[0]), (float)far_local(pz[CELLS - 1])};
+                    f32x2 fs = {0.0f, 0.0f};
+#pragma unroll 4
+                    for (int k = far_local_uniform(0); k < ffill; ++k) {
+                        const float4 o = far_entry(W.bxy, W.bzw, k);
+                        const f32x2 w = {o.w, o.w};
+                        fs = far_pairs(fx - o.x, fy - o.y, fz - o.z, fg2, w, fs);
+                    }
+                    acc[0] += (double)fs.x;
+                    acc[CELLS - 1] += (double)fs.y;
+                } else {
+                    const float fx = (float)far_local(px[0]), fy = (float)far_local(py[0]), fz = (float)far_local(pz[0]);
+                    f32x2 fs = {0.0f, 0.0f};
+                    int k = far_local_uniform(0);
+#pragma unroll 2
+                    for (; k + 1 < ffill; k += 2) fs = far_pairs_of(fx, fy, fz, far_entry(W.bxy, W.bzw, k), far_entry(W.bxy, W.bzw, k + 1), fg2, fs);
+                    if (k < ffill) {                            // an odd entry: its twin with weight 0
+                        const float4 o = far_entry(W.bxy, W.bzw, k);
+                        fs = far_pairs_of(fx, fy, fz, o, make_float4(o.x, o.y, o.z, 0.0f), fg2, fs);
+                    }
+                    acc[0] += (double)fs.x;
+                    acc[0] += (double)fs.y;
+                }
+            }
             fill = 0;
+            ffill = 0;
             __syncthreads();
         }
     }

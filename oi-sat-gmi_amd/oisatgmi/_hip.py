@@ -108,6 +108,8 @@ SIGNATURES = {
     "oisat_set_correlation": (C.c_int, [_c_ctx, C.c_int]),
     "oisat_corr_eval": (C.c_int, [C.c_int, C.c_double, _ptr, _i64, _ptr]),
     "oisat_corr_cut_chord": (C.c_int, [C.c_int, C.c_double, C.c_double, C.POINTER(C.c_double)]),
+    "oisat_solve_tier_counts": (C.c_int, [C.c_int, C.c_double, C.c_double, _ptr, _i64, _ptr, _i64, _ptr, C.c_double, C.c_double,
+                                          C.POINTER(_i64), C.POINTER(_i64)]),
     "oisat_envelope_corr": (C.c_int, [C.c_int, _ptr, _i64, C.c_double, _ptr]),
     "oisat_factor_envelope_corr": (C.c_int, [C.c_int, _ptr, _i64, C.c_double, _ptr]),
     "oisat_factor_far_corr": (C.c_int, [C.c_int, _ptr, _i64, C.c_double, _ptr, _ptr]),
