@@ -208,7 +208,12 @@ int oisat_boxfilter_symm(oisat_ctx* h, int dtype, const void* Z, int64_t Ny, int
  * need, interpolator.py:145-150,:78-91,:28-33).  Points/targets: dev double lon/lat arrays.
  * idx_out: dev int32[T], -1 where no point lies within max_dist (those cells are NaN-masked by
  * the caller's gather).  Exact ties resolve to the lowest point index (see oisat_nn_query_ties).  Distances are Euclidean in
- * degree space in double, like the reference.  Synchronises internally (sizes a workspace). */
+ * degree space in double, like the reference: d2 = dx*dx + dy*dy without contraction, dist = sqrt(d2), and a target is kept
+ * iff NOT dist > max_dist (a point at exactly max_dist is kept).  The answer is the brute-force one for every target: the
+ * hash cell is the radius padded by 2^-26, which covers the rounding of the cell coordinates (csrc/regrid.hip).
+ * NaN coordinates: a point with a NaN longitude or latitude is never returned and never counts as a tie; a target with a
+ * NaN coordinate gets idx -1 and dist +inf; with no finite point at all every target does.  Coordinates must not be
+ * infinite.  dist_out: +inf where idx is -1.  Synchronises internally (sizes a workspace). */
 int oisat_nn_query(oisat_ctx* h, const double* plon, const double* plat, int64_t P,
                    const double* tlon, const double* tlat, int64_t T, double max_dist,
                    int32_t* idx_out, double* dist_out /* may be NULL */);
@@ -240,7 +245,14 @@ int oisat_gather_mask(oisat_ctx* h, int dtype, const void* values, int64_t P, in
  * degenerate simplex or does not converge it falls back, like scipy's _find_simplex_directed, to the brute-force scan
  * (_find_simplex_bruteforce: bounding box, every simplex, eps_broad towards NaN-transform simplices).
  * bounds_host: HOST double[4] = {min x, max x, min y, max y} of the triangulated points (Delaunay.min_bound /
- * max_bound) for that scan's bounding-box test; NULL = no box test. */
+ * max_bound) for that scan's bounding-box test; NULL = no box test.
+ * The walk takes the first hull facet it crosses (a coordinate below -eps whose neighbour is -1) as "outside", without a
+ * second look, as scipy's directed walk does.  Where the triangulation is not a partition to rounding -- qhull closes the
+ * straight edge of a regular swath grid with zero-area slivers, and a target ON that edge is inside or outside by 1e-13 --
+ * the answer therefore depends on the simplex the walk starts from: here always one at the target's nearest point
+ * (vertex_to_simplex[nn_idx]; simplex 0 if that entry is out of range), in scipy the simplex its previous target ended in,
+ * so for such hull-grazing targets scipy's own answer varies with the order of the targets and the two can differ.  They are
+ * not reported by oisat_linear_locate unless a second simplex accepts them. */
 int oisat_linear_interp(oisat_ctx* h, int dtype, const double* tlon, const double* tlat, int64_t T,
                         const int32_t* nn_idx, const int32_t* vertex_to_simplex, const int32_t* simplices,
                         const int32_t* neighbors, const double* transform, int64_t nsimplex,

@@ -4,8 +4,10 @@
 //
 // The reference builds a fresh k-d tree over ~1e6 nodes for every field it regrids.  Here the
 // neighbour search is done once per (points, targets) pair on the device with a uniform-cell hash
-// whose cell edge equals the mask radius: only neighbours within `max_dist` can survive the mask,
-// so the 3x3 cell block around a target contains every candidate and the search is exact.  The
+// whose cell edge is the mask radius padded by 2^-26: only neighbours within `max_dist` can survive the mask,
+// and the pad covers the rounding of the cell coordinates (an unpadded cell misses a point just inside the
+// radius of a target a few ulp from a cell border: nn_query_impl has the argument), so the 3x3 cell block
+// around a target contains every candidate and the search is exact.  The
 // resulting index vector is reused by every field (one gather kernel for a whole stack of fields).
 // Distances are Euclidean in degree space, in double, exactly like the reference.  Exactly equidistant
 // points DO occur on the reference's own settings (grid_size 1.0 against a 1.25 / 2.5 deg model longitude
@@ -46,7 +48,7 @@ __global__ __launch_bounds__(256) void boxfilter_kernel(const T* __restrict__ Z,
 }
 
 // G lanes cooperate on one picked node: lanes stride the ky*kx window, then a fixed xor-tree adds
-// the G partials (deterministic).  G in {1,4,16,64}.
+// the G partials (deterministic).  G in {1,64}: windows the row-wise form below does not take (one or two nodes; kx > 64).
 template <typename T, int G>
 __global__ __launch_bounds__(256) void boxfilter_pick_kernel(const T* __restrict__ Z, int64_t Ny, int64_t Nx, int nfields,
                                                               int ky, int kx, T w, const int32_t* __restrict__ idx, int64_t Tn,
@@ -293,6 +295,10 @@ __global__ __launch_bounds__(256) void nn_query_kernel(const double* __restrict_
         if (x == x && y == y) {
             int cx, cy;
             cell_of(g, x, y, cx, cy);
+            // a point whose coordinate rounds into cell nb is held in cell nb - 1 (nn_count_kernel clamps it): a target in
+            // cell nb + 1 is one cell from where that point was hashed, so it looks from cell nb (see nn_query_impl)
+            if (cx == g.nbx + 1) cx = g.nbx;
+            if (cy == g.nby + 1) cy = g.nby;
             for (int yy = cy - 1; yy <= cy + 1; ++yy) {
                 if (yy < 0 || yy >= g.nby) continue;
                 for (int xx = cx - 1; xx <= cx + 1; ++xx) {
@@ -901,19 +907,11 @@ static int pick_impl(oisat_ctx* h, const void* Z, int64_t Ny, int64_t Nx, int nf
                      nfields, ky, kx, (T)w, idx, Tn, (T*)out, tpw, wpf);
         return OISAT_OK;
     }
-    if (win >= 48) {
+    if (kx > 64) {                                           // win >= 65: a wave per node
         const int grid = stream_grid(groups * 64, 256);
         OISAT_LAUNCH(h, "boxfilter_pick", (boxfilter_pick_kernel<T, 64>), dim3(grid), dim3(256), 0, (const T*)Z, Ny, Nx, nfields,
                      ky, kx, (T)w, idx, Tn, (T*)out);
-    } else if (win >= 12) {
-        const int grid = stream_grid(groups * 16, 256);
-        OISAT_LAUNCH(h, "boxfilter_pick", (boxfilter_pick_kernel<T, 16>), dim3(grid), dim3(256), 0, (const T*)Z, Ny, Nx, nfields,
-                     ky, kx, (T)w, idx, Tn, (T*)out);
-    } else if (win >= 3) {
-        const int grid = stream_grid(groups * 4, 256);
-        OISAT_LAUNCH(h, "boxfilter_pick", (boxfilter_pick_kernel<T, 4>), dim3(grid), dim3(256), 0, (const T*)Z, Ny, Nx, nfields,
-                     ky, kx, (T)w, idx, Tn, (T*)out);
-    } else {
+    } else {                                                 // win < 3: a lane per node
         const int grid = stream_grid(groups, 256);
         OISAT_LAUNCH(h, "boxfilter_pick", (boxfilter_pick_kernel<T, 1>), dim3(grid), dim3(256), 0, (const T*)Z, Ny, Nx, nfields,
                      ky, kx, (T)w, idx, Tn, (T*)out);
@@ -1079,13 +1077,25 @@ static int nn_query_impl(oisat_ctx* h, const double* plon, const double* plat, i
                          int64_t Tn, double max_dist, int32_t* idx_out, double* dist_out, int32_t* tie_list, int64_t* n_ties) {
     ARG_CHECK(h && plon && plat && tlon && tlat && idx_out);
     ARG_CHECK(P > 0 && P < (int64_t)INT32_MAX && Tn > 0 && Tn < (int64_t)INT32_MAX && max_dist > 0.0 && std::isfinite(max_dist));
-    // cell edge = mask radius: the 3x3 block around a target holds every candidate that can survive the mask
+    // Cell edge = mask radius * (1 + 2^-26), so that the 3x3 block around a target holds every candidate that can survive
+    // the mask.  With the edge equal to the radius it does not: the cell coordinate of x is computed,
+    //     q(x) = fl(fl(x - x0) * fl(1 / h)) = r(x) (1 + e),  r(x) = (x - x0) / h,  |e| <= 3.01 u,  u = 2^-53,
+    // and a target a few ulp below a cell border with a point 0.9999.. h further on land two cells apart.  With the pad: a
+    // point p that survives the mask of target t has |p.x - t.x| <= max_dist (1 + 3 u) (the rounding of dx, of d2 and of its
+    // root), and h >= max_dist (1 + pad)(1 - u) (coarsening only doubles it), so |r(p) - r(t)| <= (1 + 4 u) / (1 + pad) and
+    //     |q(p) - q(t)| <= (1 + 4 u) / (1 + pad) + 3.01 u (|r(p)| + |r(t)|) <= 1 - pad / (1 + pad) + 4 u + 3.01 u (2 C + 3),
+    // C = the largest cell coordinate.  build_hash allows 4 Mi cells and a collinear set puts them all on one axis, so C < 2^22
+    // and the rounding term is below 6.1 * 2^22 * 2^-53 = 2.9e-9 (a pad of 1e-9 would not cover it); pad = 2^-26 = 1.5e-8
+    // leaves |q(p) - q(t)| < 1, and two numbers less than 1 apart have floors at most 1 apart.  The same holds in y.
+    // The box's far edge: q(xmax) < nbx (1 + 4 u) < nbx + 1, so a point's cell is at most nbx, where nn_count_kernel clamps it
+    // to nbx - 1; its targets sit in cells nbx - 1 .. nbx + 1 and nn_query_kernel searches the last of these from cell nbx.
+    // Every other target still visits exactly its own 3x3 block.
     HashGrid g;
     const unsigned* start;
     const int32_t* sorted;
     const double2* sxy;
     const unsigned* scan_error;
-    const int rc = build_hash(h, plon, plat, P, max_dist, &g, &start, &sorted, &sxy, &scan_error);
+    const int rc = build_hash(h, plon, plat, P, max_dist * (1.0 + 0x1p-26), &g, &start, &sorted, &sxy, &scan_error);
     if (rc != OISAT_OK) return rc;
     unsigned* count = nullptr;
     unsigned* count_host = (unsigned*)oisat_pinned(h, 64);
