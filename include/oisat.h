@@ -453,18 +453,27 @@ int oisat_factor_mid(const double* lat_sorted, int64_t m, double g, const int32_
  *   z >= 2:       C = 0 exactly
  * It takes no parameter besides g.  Its latitude windows, envelopes and culls end at the support chord 2 / sqrt(0.6 g) and
  * leave out exact zeros only.
+ * OISAT_CORR_SOAR: the second-order autoregressive function of classical optimal interpolation, the Matern function of
+ * nu = 3/2 matched to the same g,
+ *   C = (1 + s) exp(-s),  s = chord sqrt(2 g) = distance / L      (C ~ 1 - g chord^2 at small separation, C(0) = 1 exactly)
+ * Once mean-square differentiable, exponential tails: it reaches 2^-52 at s = 39.75 (the Gaussian: 8.49 L), so from L ~ 321 km
+ * on nothing is windowed.  Positive definite in R^3, hence on the sphere with chord distance.  No parameter besides g, no
+ * far tier (oisat_solve_tier_counts: far_out = 0).  Its code is 3 = 2 nu; 2 is no model and stays OISAT_EINVAL.
  * oisat_set_correlation: the model of every later oisat_cov_build*, oisat_cov_residual, oisat_gain_solve,
  * oisat_apply_increment*, oisat_posterior_error and oisat_batch_solve on this handle (set it per run where handles are
  * shared, like oisat_set_refine_tol).  oisat_batch_analyse is Gaussian only: OISAT_EINVAL under any other model.
  * oisat_corr_eval (host only): out[i] = C at squared chord d2[i], float64, by the function the float64 kernels use.
  * oisat_corr_cut_chord (host only): the chord at which C has fallen to 2^-bits (bits >= 1) -- Gaussian sqrt(bits / (g log2 e));
- * Gaspari-Cohn by bisection, never beyond the support chord, and the support chord itself from 52 bits on.
+ * Gaspari-Cohn by bisection, never beyond the support chord, and the support chord itself from 52 bits on; SOAR by bisection
+ * on s (15.265708 at 18 bits, 22.568011 at 28, 39.751137 at 52), not clamped to the sphere's diameter 2.
  * oisat_envelope_corr / oisat_factor_envelope_corr / oisat_factor_far_corr: the three tables above for a model; kind =
- * OISAT_CORR_GAUSSIAN gives the tables of the functions above word for word.  Under Gaspari-Cohn the factor's envelope is the
- * support envelope (= oisat_envelope_corr) and far_out == first unless OISAT_FACTOR_CUT_BITS / OISAT_FACTOR_FAR_BITS force a
- * cut-off: the Gaussian's defaults were measured for the Gaussian.  An unknown kind is OISAT_EINVAL. */
+ * OISAT_CORR_GAUSSIAN gives the tables of the functions above word for word.  Under any other model the factor's envelope is
+ * the 2^-52 envelope (= oisat_envelope_corr; Gaspari-Cohn: the support envelope) and far_out == first unless
+ * OISAT_FACTOR_CUT_BITS / OISAT_FACTOR_FAR_BITS force a cut-off: the Gaussian's defaults were measured for the Gaussian.  An
+ * unknown kind is OISAT_EINVAL. */
 #define OISAT_CORR_GAUSSIAN 0
 #define OISAT_CORR_GASPARI_COHN 1
+#define OISAT_CORR_SOAR 3                  /* = 2 nu of the Matern family; 2 is unassigned and stays OISAT_EINVAL */
 int oisat_set_correlation(oisat_ctx* h, int kind);
 int oisat_corr_eval(int kind, double g, const double* d2, int64_t n, double* out);
 int oisat_corr_cut_chord(int kind, double g, double bits, double* chord_out);
@@ -486,7 +495,7 @@ int oisat_factor_envelope_corr(int kind, const double* lat_sorted, int64_t m, do
 int oisat_factor_far_corr(int kind, const double* lat_sorted, int64_t m, double g, const int32_t* first, int32_t* far_out);
 int oisat_set_factor_far(oisat_ctx* h, const int32_t* far, int64_t nb);
 int oisat_factor_mid_corr(int kind, const double* lat_sorted, int64_t m, double g, const int32_t* first, const int32_t* far,
-                          int32_t* mid_out);       /* oisat_factor_mid for a model; Gaspari-Cohn: mid_out == far unless forced */
+                          int32_t* mid_out);       /* oisat_factor_mid for a model; not Gaussian: mid_out == far unless forced */
 int oisat_set_factor_mid(oisat_ctx* h, const int32_t* mid, int64_t nb);
 /* The factor's shadow (csrc/dense_dag.inc "Shadow"): where an enveloped factorization has a far or a
  * middle block, the task that makes a strictly-lower tile (r, k), first[r] <= k < r, final also stores its two bf16 images,

@@ -2490,8 +2490,6 @@ static int64_t envelope_ksteps(const int32_t* first, int64_t nb) {
     return k;
 }
 
-static bool corr_kind_ok(int kind) { return kind == OISAT_CORR_GAUSSIAN || kind == OISAT_CORR_GASPARI_COHN; }
-
 static bool lat_sorted_ok(const double* lat_sorted, int64_t m) {
     for (int64_t i = 1; i < m; ++i)
         if (!(lat_sorted[i] >= lat_sorted[i - 1])) return false;
@@ -2529,14 +2527,16 @@ extern "C" int oisat_envelope(const double* lat_sorted, int64_t m, double g, int
 // kFactorCutBits, kFactorMinKstepsPerRow and kFactorFarBits below were measured for the Gaussian only.  Gaspari-Cohn reaches
 // 2^-28 and 2^-18 at 99.5 % and 97 % of its support radius, so there is no narrower table worth having: its factor's envelope
 // IS the support envelope (oisat_envelope_corr's, which drops exact zeros only), with no chain-bound fallback to decide, and
-// its far table is empty (far = first).  The two environment variables still force their rules, through cut_chord.
+// its far table is empty (far = first).  SOAR, and any model that is not the Gaussian, takes the same rule -- the 2^-52 table,
+// far = first, mid = far -- because nothing has been measured for it.  The environment variables still force their rules,
+// through cut_chord.
 extern "C" int oisat_factor_envelope_corr(int kind, const double* lat_sorted, int64_t m, double g, int32_t* env_out) {
     ARG_CHECK(corr_kind_ok(kind) && lat_sorted && env_out && m > 0 && g >= 0.0);
     ARG_CHECK(lat_sorted_ok(lat_sorted, m));
     double bits = kFactorCutBits;
     bool forced = false;
     if (int rc = env_bits("OISAT_FACTOR_CUT_BITS", 1.0, &bits, &forced)) return rc;
-    if (kind == OISAT_CORR_GASPARI_COHN && !forced) bits = kCutBits;
+    if (kind != OISAT_CORR_GAUSSIAN && !forced) bits = kCutBits;
     envelope_table(kind, lat_sorted, m, g, bits, env_out);
     if (kind == OISAT_CORR_GAUSSIAN && !forced && !narrow_table_pays(env_out, cdiv(m, NB)))
         envelope_table(kind, lat_sorted, m, g, kCutBits, env_out);     // chain-bound: nothing to win, keep the float64 sums' table
@@ -2838,12 +2838,17 @@ extern "C" int oisat_posterior_error(oisat_ctx* h, const float* L, int64_t m, in
     float* X = (float*)oisat_ws(h, 6, sizeof(float) * chunk_rows * mp + sizeof(double) * chunk_rows);
     if (!X) return OISAT_ENOMEM;
     double* ss = (double*)(X + chunk_rows * mp);
-    const float g2 = h->corr == OISAT_CORR_GASPARI_COHN ? (float)(kGcZ2PerG * g) : (float)(g * 1.4426950408889634);      // g2 | kz2
+    const float g2 = h->corr == OISAT_CORR_SOAR           ? (float)corr_scale2(OISAT_CORR_SOAR, g)
+                     : h->corr == OISAT_CORR_GASPARI_COHN ? (float)(kGcZ2PerG * g)
+                                                          : (float)(g * 1.4426950408889634);      // g2 | kz2 | 2 g (log2 e)^2
     for (int64_t c0 = i0; c0 < i1; c0 += chunk_rows) {
         const int64_t live = (i1 - c0 < chunk_rows) ? i1 - c0 : chunk_rows;
         const int64_t nrows = cdiv(live, NB) * NB;                 // rows live..nrows are zero rows
         if (h->corr == OISAT_CORR_GASPARI_COHN) {
             OISAT_LAUNCH(h, "cross_cov_rows", cross_cov_rows_kernel<OISAT_CORR_GASPARI_COHN>, dim3((unsigned)(mp / 64), (unsigned)(nrows / 64)),
+                         dim3(256), 0, gxyz, gsig, n, c0, live, oxyz, osig, m, mp, g2, X, mp);
+        } else if (h->corr == OISAT_CORR_SOAR) {
+            OISAT_LAUNCH(h, "cross_cov_rows", cross_cov_rows_kernel<OISAT_CORR_SOAR>, dim3((unsigned)(mp / 64), (unsigned)(nrows / 64)),
                          dim3(256), 0, gxyz, gsig, n, c0, live, oxyz, osig, m, mp, g2, X, mp);
         } else {
             OISAT_LAUNCH(h, "cross_cov_rows", cross_cov_rows_kernel<OISAT_CORR_GAUSSIAN>, dim3((unsigned)(mp / 64), (unsigned)(nrows / 64)),

@@ -1,7 +1,8 @@
 // Dense background-error covariance pieces of the north-star analysis
 //     x_a = x_b + B H^T (H B H^T + R)^-1 (y - H x_b),   B = D^1/2 C D^1/2,
 //     C(p,q) = exp(-g |p-q|^2),  g = R_earth^2 / (2 L^2),  p,q unit vectors on the sphere (the default model), or the
-//     compactly supported Gaspari-Cohn function of the same g (oisat_set_correlation; dense_solve_dev.inc: corr_f32 / corr_f64).
+//     compactly supported Gaspari-Cohn function or the SOAR (Matern 3/2) function of the same g (oisat_set_correlation;
+//     dense_solve_dev.inc: corr_f32 / corr_f64).
 // The reference has no counterpart (its OI is the L->0, H=I limit: optimal_interpolation.py:27,
 // :49-50).  Chord distance keeps C positive definite on the sphere; |p-q|^2 is formed from
 // coordinate DIFFERENCES (not 2-2p.q) so that fp32 keeps ~1e-7 relative accuracy at small range.
@@ -207,6 +208,8 @@ __global__ __launch_bounds__(256) void apply_increment_kernel(const double* __re
     do {                                                                                                           \
         if ((h)->corr == OISAT_CORR_GASPARI_COHN) {                                                                \
             OISAT_LAUNCH(h, NAME, (KERNEL<OISAT_CORR_GASPARI_COHN, TARGS>), grid, block, shmem, __VA_ARGS__);      \
+        } else if ((h)->corr == OISAT_CORR_SOAR) {                                                                 \
+            OISAT_LAUNCH(h, NAME, (KERNEL<OISAT_CORR_SOAR, TARGS>), grid, block, shmem, __VA_ARGS__);              \
         } else {                                                                                                   \
             OISAT_LAUNCH(h, NAME, (KERNEL<OISAT_CORR_GAUSSIAN, TARGS>), grid, block, shmem, __VA_ARGS__);          \
         }                                                                                                          \
@@ -216,23 +219,25 @@ __global__ __launch_bounds__(256) void apply_increment_kernel(const double* __re
 }  // namespace
 
 extern "C" int oisat_set_correlation(oisat_ctx* h, int kind) {
-    ARG_CHECK(h != nullptr && (kind == OISAT_CORR_GAUSSIAN || kind == OISAT_CORR_GASPARI_COHN));
+    ARG_CHECK(h != nullptr && corr_kind_ok(kind));
     h->corr = kind;
     return OISAT_OK;
 }
 
 extern "C" int oisat_corr_eval(int kind, double g, const double* d2, int64_t n, double* out) {
-    ARG_CHECK((kind == OISAT_CORR_GAUSSIAN || kind == OISAT_CORR_GASPARI_COHN) && g >= 0.0 && n >= 0 && ((d2 && out) || n == 0));
+    ARG_CHECK(corr_kind_ok(kind) && g >= 0.0 && n >= 0 && ((d2 && out) || n == 0));
     const double a = corr_scale(kind, g);
     if (kind == OISAT_CORR_GASPARI_COHN)
         for (int64_t i = 0; i < n; ++i) out[i] = corr_f64<OISAT_CORR_GASPARI_COHN>(a, d2[i]);
+    else if (kind == OISAT_CORR_SOAR)
+        for (int64_t i = 0; i < n; ++i) out[i] = corr_f64<OISAT_CORR_SOAR>(a, d2[i]);
     else
         for (int64_t i = 0; i < n; ++i) out[i] = corr_f64<OISAT_CORR_GAUSSIAN>(a, d2[i]);
     return OISAT_OK;
 }
 
 extern "C" int oisat_corr_cut_chord(int kind, double g, double bits, double* chord_out) {
-    ARG_CHECK((kind == OISAT_CORR_GAUSSIAN || kind == OISAT_CORR_GASPARI_COHN) && g > 0.0 && bits >= 1.0 && chord_out);
+    ARG_CHECK(corr_kind_ok(kind) && g > 0.0 && bits >= 1.0 && chord_out);
     *chord_out = cut_chord(kind, g, bits);
     return OISAT_OK;
 }
@@ -245,7 +250,7 @@ extern "C" int oisat_corr_cut_chord(int kind, double g, double bits, double* cho
 // sits on a radius to the last bit.
 extern "C" int oisat_solve_tier_counts(int kind, double g, double bits, const double* pts_xyz, int64_t npts, const double* obs_xyz, int64_t m,
                                        const double* olat, double lat_lo, double lat_hi, int64_t* near_out, int64_t* far_out) {
-    ARG_CHECK((kind == OISAT_CORR_GAUSSIAN || kind == OISAT_CORR_GASPARI_COHN) && g > 0.0 && pts_xyz && npts > 0 && obs_xyz && m > 0);
+    ARG_CHECK(corr_kind_ok(kind) && g > 0.0 && pts_xyz && npts > 0 && obs_xyz && m > 0);
     ARG_CHECK(bits <= kCutBits && lat_lo <= lat_hi);
     double far_chord;
     ARG_CHECK(far_chord_of(kind, g, &far_chord, bits));

@@ -31,9 +31,22 @@ constexpr double kSolveFarBits = 28.0;
 // sphere with chord distance (dense_cov.hip, head).  Every kernel that evaluates a correlation is a template on KIND and takes
 // ONE scale next to d^2: what its Gaussian form has always taken (g, or g2 = g log2 e where it uses exp2) or kz2 = 0.6 g.
 constexpr double kGcZ2PerG = 0.6;
+// KIND = OISAT_CORR_SOAR (3): the second-order autoregressive function, the Matern function of nu = 3/2, C = (1 + s) exp(-s) with
+// s = d sqrt(2 g) = distance / L (the Gaussian's curvature at d = 0: C ~ 1 - g d^2).  Positive definite in R^3, hence on the sphere
+// with chord distance; once mean-square differentiable, exponential tails: 2^-52 at s = 39.75 where the Gaussian is there at
+// 8.49 L.  Its scale is s^2 / d^2 = 2 g, or 2 g (log2 e)^2 where the kernel uses exp2: then s' = sqrt(a d^2) = s log2 e and
+// C = fma(s', ln 2, 1) 2^-s'.  No far tier, no parameter besides g.
+constexpr double kLog2eD = 1.4426950408889634;
+constexpr double kLn2D = 0.6931471805599453;
 // what a kernel of model `kind` takes in the place of the Gaussian's g2 = g log2 e / of the Gaussian's g
-static inline double corr_scale2(int kind, double g) { return kind == OISAT_CORR_GASPARI_COHN ? kGcZ2PerG * g : g * (double)kLog2e; }
-static inline double corr_scale(int kind, double g) { return kind == OISAT_CORR_GASPARI_COHN ? kGcZ2PerG * g : g; }
+static inline double corr_scale2(int kind, double g) {
+    if (kind == OISAT_CORR_SOAR) return 2.0 * g * (kLog2eD * kLog2eD);
+    return kind == OISAT_CORR_GASPARI_COHN ? kGcZ2PerG * g : g * (double)kLog2e;
+}
+static inline double corr_scale(int kind, double g) {
+    if (kind == OISAT_CORR_SOAR) return 2.0 * g;
+    return kind == OISAT_CORR_GASPARI_COHN ? kGcZ2PerG * g : g;
+}
 
 // Both branches in Horner form and a select: a wave's 64 pairs straddle all three ranges.  (z = 0: the far branch is -inf /
 // NaN and not selected.)  Rounding noise below 0 next to z = 2 is clamped.
@@ -62,31 +75,61 @@ __host__ __device__ inline double gc_f64(double kz2, double d2) {
     return z < 2.0 ? (c > 0.0 ? c : 0.0) : 0.0;
 }
 
+// the models the library knows (include/oisat.h: 2 is unassigned)
+static inline bool corr_kind_ok(int kind) { return kind == OISAT_CORR_GAUSSIAN || kind == OISAT_CORR_GASPARI_COHN || kind == OISAT_CORR_SOAR; }
+
+// SOAR in fp32: one v_sqrt_f32, one v_exp_f32, one fma, one multiply; no division, no branch (d2 = 0: sqrt 0, 2^-0, exactly 1)
+__device__ __forceinline__ float soar_f32(float a, float d2) {
+    const float sp = __builtin_amdgcn_sqrtf(a * d2);                         // s log2 e
+    return __builtin_fmaf(sp, (float)kLn2D, 1.0f) * __builtin_amdgcn_exp2f(-sp);
+}
+
 __device__ __forceinline__ double exp2_neg(double x);
-// fp32 (the build of S, the rows of H B): a = g2 | kz2
+// fp32 (the build of S, the rows of H B): a = g2 | kz2 | 2 g (log2 e)^2
 template <int KIND>
 __device__ __forceinline__ float corr_f32(float a, float d2) {
     if (KIND == OISAT_CORR_GASPARI_COHN) return gc_f32(a, d2);
+    if (KIND == OISAT_CORR_SOAR) return soar_f32(a, d2);
     return __builtin_amdgcn_exp2f(-a * d2);
 }
-// float64 (the residual): a = g | kz2
+// float64 (the residual): a = g | kz2 | 2 g
 template <int KIND>
 __host__ __device__ inline double corr_f64(double a, double d2) {
     if (KIND == OISAT_CORR_GASPARI_COHN) return gc_f64(a, d2);
+    if (KIND == OISAT_CORR_SOAR) {
+        const double s = sqrt(a * d2);
+        return (1.0 + s) * exp(-s);
+    }
     return exp(-a * d2);
 }
-// float64 (the increment): a = g2 | kz2
+// float64 (the increment): a = g2 | kz2 | 2 g (log2 e)^2
 template <int KIND>
 __device__ __forceinline__ double corr_f64_exp2(double a, double d2) {
     if (KIND == OISAT_CORR_GASPARI_COHN) return gc_f64(a, d2);
+    if (KIND == OISAT_CORR_SOAR) {
+        const double sp = sqrt(a * d2);
+        return __builtin_fma(sp, kLn2D, 1.0) * exp2_neg(-sp);
+    }
     return exp2_neg(-a * d2);
 }
 
 // ---- host: the chord at which the correlation has fallen to 2^-bits -------------------------------------------------------
 // Gaussian: sqrt(bits / g2).  Gaspari-Cohn: by bisection on z in [0, 2] (C falls monotonically there), the upper end of the
 // last bracket, never beyond the support chord 2 / sqrt(0.6 g); from kCutBits on it IS the support chord: the float64 sums
-// then leave out nothing.  Every window, envelope and cull of the library derives its chord here.
+// then leave out nothing.  SOAR: by bisection on s for (1 + s) exp(-s) = 2^-bits (C falls monotonically; the root lies below
+// bits ln 2 + ln(1 + s) < 2 bits + 2), the upper end of the last bracket too; NOT clamped to the sphere's diameter: from
+// L ~ 321 km on the 2^-52 chord is 2 or more and lat_window_deg windows nothing.  Every window, envelope and cull of the library
+// derives its chord here.
 static inline double cut_chord(int kind, double g, double bits) {
+    if (kind == OISAT_CORR_SOAR) {
+        const double lt = -bits * kLn2D;                                    // ln of the target: log1p(s) - s <= lt beyond the root
+        double lo = 0.0, hi = 2.0 * bits + 2.0;
+        for (int it = 0; it < 100; ++it) {
+            const double mid = 0.5 * (lo + hi);
+            if (log1p(mid) - mid > lt) lo = mid; else hi = mid;
+        }
+        return hi / sqrt(2.0 * g);
+    }
     if (kind != OISAT_CORR_GASPARI_COHN) return sqrt(bits / (g * (double)kLog2e));
     double hi = 2.0;
     if (bits < kCutBits) {
@@ -327,9 +370,9 @@ static inline bool far_chord_of(int kind, double g, double* chord_out, double bi
 // observations, L = 300 km (reach 2 800 km): 6.6 -> 4.6 ms; a month's 50 tiles: 1.69 -> 1.59 ms; at 360x720 / 1e4 observations,
 // L = 500 km (reach 4 700 km) the staging costs more than the cull saves: 0.21 -> 0.26 ms.
 // (The rule is about the reach: the Gaussian's 2^-64 chord, as measured.  Gaspari-Cohn: the same 0.5 applied to its support
-// chord -- reasoned from the Gaussian's figures, not measured.)
+// chord; SOAR: to its 2^-52 chord (L <= 80 km) -- both reasoned from the Gaussian's figures, not measured.)
 static inline bool residual_blocks_pay(int kind, double g) {
-    if (kind == OISAT_CORR_GASPARI_COHN) return cut_chord(kind, g, kCutBits) <= 0.5;
+    if (kind != OISAT_CORR_GAUSSIAN) return cut_chord(kind, g, kCutBits) <= 0.5;
     return sqrt(64.0 / (g * (double)kLog2e)) <= 0.5;           // chord on the unit sphere: 3 200 km (L <= 340 km)
 }
 // two cells per thread share every observation fetched from LDS; with too few cells to fill the GPU that way (a polar cap:

@@ -5,7 +5,9 @@
     H = selection of the grid cell that contains each observation
 
 ``corr="gaspari_cohn"`` replaces the Gaussian C by the compactly supported function of Gaspari and Cohn (1999, eq. 4.10) of the
-same L (half-support c = L sqrt(10/3), exactly zero beyond 2 c = 3.65 L); ``corr="gaussian"`` is the default everywhere.
+same L (half-support c = L sqrt(10/3), exactly zero beyond 2 c = 3.65 L); ``corr="soar"`` by the second-order autoregressive
+function of classical optimal interpolation, the Matern function of nu = 3/2, C = (1 + r/L) exp(-r/L) with r the chord in km
+(once differentiable, exponential tails: 2^-52 only at 39.75 L); ``corr="gaussian"`` is the default everywhere.
 
 The reference's ``OI`` (optimal_interpolation.py:6-52) is the L -> 0 limit of this with one
 observation per cell: there C = I and K_ii = s Sa_i / (s Sa_i + So_i) (:27).  There is NO
@@ -62,12 +64,28 @@ def morton_order(lat_deg, lon_deg) -> np.ndarray:
 
 
 # correlation models (include/oisat.h: OISAT_CORR_*)
-CORRELATIONS = {"gaussian": 0, "gaspari_cohn": 1}
+CORRELATIONS = {"gaussian": 0, "gaspari_cohn": 1, "soar": 3}     # (3 = 2 nu of the Matern family; 2 is no model)
 GC_SUPPORT_PER_L = 2.0 * (10.0 / 3.0) ** 0.5        # Gaspari-Cohn: C = 0 beyond 2 c = 3.6515 L
 
 
+def _soar_halo_per_l() -> float:
+    """s = r / L at which SOAR, (1 + s) exp(-s), has fallen to the Gaussian's value at its 3 L halo, exp(-4.5): the root of
+    log1p(s) - s + 4.5 by bisection (the function falls monotonically from 4.5 at s = 0)."""
+    lo, hi = 0.0, 16.0
+    for _ in range(80):
+        mid = 0.5 * (lo + hi)
+        if np.log1p(mid) - mid + 4.5 > 0.0:
+            lo = mid
+        else:
+            hi = mid
+    return hi
+
+
+SOAR_HALO_PER_L = _soar_halo_per_l()                # 6.5172: the ``OI_tiled`` halo under ``corr="soar"``, in units of L
+
+
 def corr_kind(corr) -> int:
-    """``"gaussian"`` | ``"gaspari_cohn"`` -> the library's code; anything else is a ``ValueError`` (no device call made)."""
+    """``"gaussian"`` | ``"gaspari_cohn"`` | ``"soar"`` -> the library's code; anything else is a ``ValueError`` (no device call made)."""
     try:
         return CORRELATIONS[corr]
     except (KeyError, TypeError):
@@ -251,7 +269,7 @@ class DenseAnalysis:
     def run(self, L_km: float, refine: int = 2, check_pd: bool = False, want_resid: bool = False, tol=None, corr="gaussian"):
         """``refine``: the most refinement rounds the gain solve may take; it stops earlier once the float64 residual is
         below ``tol`` |d| (default: the handle's, 1e-6 -- ``oisat_set_refine_tol``; 0 runs every round).  ``corr``: the
-        correlation model, ``"gaussian"`` or ``"gaspari_cohn"`` (same L; module docstring)."""
+        correlation model, ``"gaussian"``, ``"gaspari_cohn"`` or ``"soar"`` (same L; module docstring)."""
         kind = self._kind = corr_kind(corr)
         c, lib, h = self.ctx, self.ctx.lib, self.ctx.h
         c.check(lib.oisat_set_refine_tol(h, REFINE_TOL if tol is None else float(tol)))      # per run: handles are shared
@@ -967,7 +985,7 @@ def OI_dense(Xa, Y, Sa, So, lat, lon, L_km, scale=1.0, refine=2, obs=None, dtype
     ``Xa, Sa``: (ny, nx) background and its variance; ``Y, So``: (ny, nx) observations and their
     variance, NaN where unobserved (as ``oisatgmi.oi`` passes them, driver.py:110-111);
     ``lat, lon``: (ny, nx) cell centres; ``L_km``: correlation length.  ``obs`` (optional) replaces
-    ``Y, So`` by scattered observations: dict(lat, lon, y, var).  ``corr``: ``"gaussian"`` (default) or ``"gaspari_cohn"``.
+    ``Y, So`` by scattered observations: dict(lat, lon, y, var).  ``corr``: ``"gaussian"`` (default), ``"gaspari_cohn"`` or ``"soar"``.
     Returns ``(Xb, increment, info)``; unlike the element-wise ``OI`` every cell is analysed
     (unobserved cells get the spread increment instead of NaN).
     """
@@ -1022,7 +1040,8 @@ def OI_tiled(Xa, Y, Sa, So, lat, lon, L_km, tile_deg=30.0, halo_km=None, scale=1
              streams=12, corr="gaussian"):
     """Localised block-B analysis with the reference's gridded argument convention (see ``OI_dense``): the grid is cut
     into ``tile_deg`` tiles, each analysed with the observations inside it or within ``halo_km`` (default: 3 L for the
-    Gaussian; the support 2 c = 3.6515 L for ``corr="gaspari_cohn"``, where the halo is then a true boundary).
+    Gaussian; the support 2 c = 3.6515 L for ``corr="gaspari_cohn"``, where the halo is then a true boundary; 6.5172 L for
+    ``corr="soar"``: ``SOAR_HALO_PER_L``, where SOAR has the Gaussian's value at 3 L).
     Returns ``(Xb, increment, info)``; ``info`` carries ``ak`` / ``err`` when ``want_error``."""
     kind = corr_kind(corr)                                    # (ValueError before anything is touched)
     Xa = np.asarray(Xa)
@@ -1035,7 +1054,7 @@ def OI_tiled(Xa, Y, Sa, So, lat, lon, L_km, tile_deg=30.0, halo_km=None, scale=1
     xa_f = np.where(np.isfinite(Xa), Xa, 0.0)
     sa_f = np.where(np.isfinite(Sa), Sa, 0.0)
     if halo_km is None:
-        halo_km = (GC_SUPPORT_PER_L if kind == CORRELATIONS["gaspari_cohn"] else 3.0) * float(L_km)
+        halo_km = {CORRELATIONS["gaspari_cohn"]: GC_SUPPORT_PER_L, CORRELATIONS["soar"]: SOAR_HALO_PER_L}.get(kind, 3.0) * float(L_km)
     ta = TiledAnalysis(lat, lon, tile_deg=tile_deg, halo_km=halo_km, dtype=dt, streams=streams)
     try:
         ta.load(xa_f, sa_f, np.ravel(lat)[cell], np.ravel(lon)[cell], np.ravel(Y)[cell], np.ravel(So)[cell], scale=scale)

@@ -85,9 +85,9 @@ class oisatgmi(object):
     # ---- analysis mode (extension; the signature of oi() is the reference's) -----------------------------
     #   mode        attribute `oi_mode`        | env OISAT_OI_MODE        diag (default) | dense | tiled
     #   L           attribute `corr_length_km` | env OISAT_CORR_LENGTH_KM km, default 300           (dense, tiled)
-    #   model       attribute `oi_correlation` | env OISAT_CORRELATION    gaussian (default) | gaspari_cohn  (dense, tiled)
+    #   model       attribute `oi_correlation` | env OISAT_CORRELATION    gaussian (default) | gaspari_cohn | soar  (dense, tiled)
     #   tile size   attribute `tile_deg`       | env OISAT_TILE_DEG       degrees, default 30       (tiled; halo = 3 L,
-    #               gaspari_cohn: its support 3.65 L)
+    #               gaspari_cohn: its support 3.65 L, soar: 6.52 L)
     #   unobserved  attribute `oi_unobserved`  | env OISAT_UNOBSERVED     nan (default) | xa        (dense, tiled)
     #   grid        attributes `grid_lat`, `grid_lon` (ny, nx), else the first granule's latitude_center/longitude_center
     #   knee        attribute `oi_reg_index`: force the index into the 99-scaling sweep (all modes)
@@ -129,8 +129,8 @@ class oisatgmi(object):
             raise ValueError(f"OISAT_OI_MODE / oi_mode must be diag, dense or tiled, not {mode!r}")
         L = self._oi_setting("corr_length_km", "OISAT_CORR_LENGTH_KM", 300.0, float)
         corr = self._oi_setting("oi_correlation", "OISAT_CORRELATION", "gaussian").lower()
-        if corr not in ("gaussian", "gaspari_cohn"):
-            raise ValueError(f"OISAT_CORRELATION / oi_correlation must be gaussian or gaspari_cohn, not {corr!r}")
+        if corr not in ("gaussian", "gaspari_cohn", "soar"):
+            raise ValueError(f"OISAT_CORRELATION / oi_correlation must be gaussian, gaspari_cohn or soar, not {corr!r}")
         unobserved = self._oi_setting("oi_unobserved", "OISAT_UNOBSERVED", "nan").lower()
         if unobserved not in ("nan", "xa"):
             raise ValueError(f"OISAT_UNOBSERVED / oi_unobserved must be nan or xa, not {unobserved!r}")
