@@ -768,6 +768,35 @@ int oisat_solve_status(oisat_ctx* h, int* first_notpd_col, int* n_notpd_blocks, 
  * oisat_potrf / oisat_gain_solve / ... call on this handle allocates or frees device memory. */
 int oisat_dense_reserve(oisat_ctx* h, int64_t max_obs, int64_t diag_chunk_rows);
 
+/* ---- the innovations' covariogram (Hollingsworth-Loennberg): what the data say about the correlation length ----------
+ * oisat_covariogram: oxyz dev double[3][m] unit vectors, d dev double[m] innovations, w dev double[m] or NULL; u_a = d_a w_a
+ * (NULL: u = d; the caller passes 1 / (sig_b sqrt(scale))).  An observation whose u is NaN or +-inf takes part in nothing;
+ * *nobs_used_out (host, may be NULL) counts the others.  For every pair a < b of used observations
+ *   dx = xa - xb (dy, dz likewise), d2 = dx dx + dy dy + dz dz left to right (no FMA), chord = sqrt(d2),
+ *   k = (int64)(chord * (nbins / max_chord))        (the factor computed once on the host in double)
+ * and, unless k >= nbins:  count[k] += 1, sum_prod[k] += u_a u_b, sum_chord[k] += chord.
+ * count_out / sum_prod_out / sum_chord_out: HOST arrays of nbins.  Synchronises, like oisat_oi_curve.
+ * olat_sorted (dev double[m], degrees, or NULL) as for oisat_cov_residual: valid only if the observations are stored in
+ * ASCENDING latitude; a block of 256 rows then visits only the columns up to the latitude of its last row plus
+ * 2 asin(min(max_chord, 2) / 2).  What is skipped lies beyond max_chord: the outputs are the same bits with and without it.
+ * 0 <= m <= 1 << 20 (m = 0 or 1: zeros), 1 <= nbins <= 1024, max_chord > 0 and finite; anything else is OISAT_EINVAL and
+ * leaves the outputs untouched.
+ * The sums are exact integers, hence independent of the order of the atomics, of the launch shape, of the window and of the
+ * order of the observations, bit for bit: with P = m (m - 1) / 2, umax = the largest finite |u| (a device reduction) and e
+ * the frexp exponent of umax * umax * (double)P, q_prod = 2^(e - 62) (1 if that product is 0); q_chord = 2^(e_c - 62), e_c the
+ * frexp exponent of 2.0 * (double)max(P, 1); either exponent is kept at -1022 or above.  Each term is rounded once, to
+ * llrint(term / q) (an exact division, nearest even), the terms are added as int64 (below 2^63 by the choice of q) and a
+ * bin's output is (double)sum * q.  So |sum_prod[k] - exact| <= count[k] q_prod / 2 plus the last bit of the result, and
+ * likewise sum_chord with q_chord and the chord's own rounding.  umax^2 P must be finite.
+ * Workspace: 24.6 KB + 8 m bytes on the handle, grow-only, allocated at the first call that needs it (oisat_dense_reserve
+ * does not cover it).
+ * oisat_covariogram_quantum (host only): the two quanta by this rule, for tests and callers that bound the error without
+ * asking the kernel; m outside 0 .. 1 << 20, umax negative or NaN, or umax^2 P not finite is OISAT_EINVAL. */
+int oisat_covariogram(oisat_ctx* h, const double* oxyz, const double* d, const double* w, int64_t m, double max_chord,
+                      int nbins, const double* olat_sorted, int64_t* count_out, double* sum_prod_out, double* sum_chord_out,
+                      int64_t* nobs_used_out);
+int oisat_covariogram_quantum(double umax, int64_t m, double* q_prod_out, double* q_chord_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -92,6 +92,11 @@ def corr_kind(corr) -> int:
         raise ValueError(f"corr must be one of {sorted(CORRELATIONS)}, not {corr!r}") from None
 
 
+def latitude_order(lat_deg) -> np.ndarray:
+    """The permutation into ascending latitude (stable) that every latitude window of the library assumes."""
+    return np.argsort(np.ravel(np.asarray(lat_deg, dtype=np.float64)), kind="stable")
+
+
 def decay_constant(L_km: float) -> float:
     """g in C = exp(-g * chord^2) for a correlation length L (km)."""
     return 0.5 * (EARTH_RADIUS_KM / float(L_km)) ** 2
@@ -213,7 +218,7 @@ class DenseAnalysis:
         latitude windows of ``oisat_apply_increment`` / ``oisat_cov_residual`` skip by.  Per-observation results
         (``download_z``, ``gain_diag``) are handed back in the caller's order."""
         lat = np.ravel(np.asarray(obs_lat, dtype=np.float64))
-        self._order = np.argsort(lat, kind="stable")
+        self._order = latitude_order(lat)
         self._lat_sorted = np.ascontiguousarray(lat[self._order])
         self._env_host = None                                  # (belongs to these observations, one L and one model: made by run())
         self.ctx.upload_into(self.olat.ptr, self._lat_sorted, dtype=np.float64)
@@ -1073,3 +1078,159 @@ def OI_tiled(Xa, Y, Sa, So, lat, lon, L_km, tile_deg=30.0, halo_km=None, scale=1
         xb = xb.copy()
         xb[bad] = np.nan
     return xb, inc, {"nobs": int(cell.size), "cells": cell, "tiles": len(ta.tiles), **extra}
+
+
+# ---- the correlation length from the data: the innovations' covariogram (Hollingsworth-Loennberg) ----
+COVARIOGRAM_MAX_OBS = 1 << 20                        # include/oisat.h: oisat_covariogram
+
+
+def covariogram_quantum(umax: float, m: int):
+    """``(q_prod, q_chord)``: the fixed-point quanta of ``oisat_covariogram`` for ``m`` observations whose largest finite
+    ``|u|`` is ``umax`` (host only; ``OisatError`` outside the library's range)."""
+    lib = _hip.load_library()
+    qp, qc = C.c_double(0.0), C.c_double(0.0)
+    rc = lib.oisat_covariogram_quantum(float(umax), int(m), C.byref(qp), C.byref(qc))
+    if rc != 0:
+        raise _hip.OisatError(f"liboisat_hip error {rc}: {lib.oisat_last_error().decode()}")
+    return qp.value, qc.value
+
+
+def innovation_covariogram(obs_lat, obs_lon, innovation, sigma=None, max_km=2000.0, nbins=64, ctx=None):
+    """Binned products of normalised innovations ``u = innovation / sigma`` (``sigma=None``: ``u = innovation``) over all pairs of
+    observations up to ``max_km`` apart, ``nbins`` equal bins of the CHORD ``r / R_earth`` (the distance the library's ``g`` is
+    defined on), on the device (``oisat_covariogram``: exact integer sums, bitwise repeatable).  An observation whose ``u`` is
+    not finite takes part in nothing.  -> dict: ``chord`` (per-bin mean chord, NaN where ``count == 0``), ``r_km`` (``R_earth``
+    times it), ``cov`` (mean of ``u_a u_b``), ``count``, ``nobs`` (observations used), ``var0`` (mean of ``u^2`` over them),
+    ``q_prod`` / ``q_chord`` (the quanta: ``|sum - exact| <= count q / 2``), ``max_km``, ``nbins``."""
+    c = ctx or _hip.context()
+    lat = np.ravel(np.asarray(obs_lat, dtype=np.float64))
+    lon = np.ravel(np.asarray(obs_lon, dtype=np.float64))
+    d = np.ravel(np.asarray(innovation, dtype=np.float64))
+    m, nbins = int(d.size), int(nbins)
+    if lat.size != m or lon.size != m:
+        raise ValueError("obs_lat, obs_lon and innovation must have the same size")
+    with np.errstate(divide="ignore"):                        # (sigma = 0: w = inf, u not finite, the observation is dropped)
+        w = None if sigma is None else 1.0 / np.broadcast_to(np.asarray(sigma, dtype=np.float64), np.shape(innovation)).ravel()
+    o = latitude_order(lat)
+    count = np.zeros(max(nbins, 0), dtype=np.int64)
+    sp, sc = np.zeros(max(nbins, 0)), np.zeros(max(nbins, 0))
+    used = C.c_int64(0)
+    bufs = []
+    if m:
+        bufs = [c.upload(unit_vectors(lat[o], lon[o])), c.upload(d[o]), c.upload(lat[o])] + ([c.upload(w[o])] if w is not None else [])
+    ptr = [b.ptr for b in bufs] + [None] * 4
+    try:
+        c.check(c.lib.oisat_covariogram(c.h, ptr[0], ptr[1], ptr[3], m, float(max_km) / EARTH_RADIUS_KM, nbins, ptr[2],
+                                        count.ctypes.data, sp.ctypes.data, sc.ctypes.data, C.byref(used)))
+    finally:
+        for b in bufs:
+            b.free()
+    with np.errstate(invalid="ignore", divide="ignore", over="ignore"):
+        u = d if w is None else d * w
+        fin = np.isfinite(u)
+        umax = float(np.abs(u[fin]).max()) if fin.any() else 0.0
+        var0 = float(np.mean(u[fin] ** 2)) if fin.any() else float("nan")
+        chord = np.where(count > 0, sc / np.maximum(count, 1), np.nan)
+        cov = np.where(count > 0, sp / np.maximum(count, 1), np.nan)
+    q_prod, q_chord = covariogram_quantum(umax, m)
+    return {"chord": chord, "r_km": EARTH_RADIUS_KM * chord, "cov": cov, "count": count, "nobs": int(used.value), "var0": var0,
+            "q_prod": q_prod, "q_chord": q_chord, "max_km": float(max_km), "nbins": nbins}
+
+
+def _corr_at(kind: int, L_km: float, chord2: np.ndarray) -> np.ndarray:
+    """C(chord; g(L)) by the library's float64 function (``oisat_corr_eval``, host only)."""
+    lib = _hip.load_library()
+    out = np.empty_like(chord2)
+    rc = lib.oisat_corr_eval(kind, decay_constant(L_km), chord2.ctypes.data, chord2.size, out.ctypes.data)
+    if rc != 0:
+        raise _hip.OisatError(f"liboisat_hip error {rc}: {lib.oisat_last_error().decode()}")
+    return out
+
+
+def fit_correlation(cg, corr="gaussian", L_bounds=None, min_count=30):
+    """Least-squares fit of ``s C(r; L)`` to a covariogram ``cg`` (``innovation_covariogram``), host only.  Over the bins with
+    ``count >= min_count``: J(L) = sum n_k (cov_k - s(L) C(chord_k; g(L)))^2 with s(L) = sum n C cov / sum n C^2 in closed form,
+    clamped at 0; 64 log-spaced L in ``L_bounds`` (default: one bin width .. ``max_km``), then a golden-section search on log L
+    between the best point's neighbours until the bracket is below 1e-9.  -> dict ``L_km``, ``scale`` (s: the share of the
+    innovations' normalised variance that is spatially correlated, i.e. the background's if the observation errors are not),
+    ``rms`` (sqrt(J / sum n)), ``corr``, ``found`` (False: fewer than three usable bins, or s = 0 at the minimum), ``at_bound``
+    (the minimum sits on an end of ``L_bounds``), ``nbins_used``.  ``corr`` may be a list of models: the dict of the one with the
+    smallest ``rms`` among those found is returned, all of them under ``"all"``."""
+    if not isinstance(corr, str):
+        fits = {name: fit_correlation(cg, name, L_bounds, min_count) for name in corr}
+        if not fits:
+            raise ValueError("corr is an empty list")
+        best = min(fits, key=lambda name: (not fits[name]["found"], fits[name]["rms"] if fits[name]["found"] else 0.0))
+        return {**fits[best], "all": fits}
+    kind = corr_kind(corr)
+    count = np.asarray(cg["count"], dtype=np.float64)
+    chord_all, cov_all = np.asarray(cg["chord"], dtype=np.float64), np.asarray(cg["cov"], dtype=np.float64)
+    use = (count >= min_count) & np.isfinite(chord_all) & np.isfinite(cov_all)
+    n, cov = count[use], cov_all[use]
+    chord2 = np.ascontiguousarray(chord_all[use] ** 2)
+    if L_bounds is None:
+        max_km = float(cg["max_km"]) if "max_km" in cg else float(np.nanmax(cg["r_km"]))
+        L_bounds = (max_km / max(int(np.size(count)), 1), max_km)
+    lo, hi = float(L_bounds[0]), float(L_bounds[1])
+    if not (0.0 < lo < hi and np.isfinite(hi)):
+        raise ValueError(f"L_bounds must be 0 < low < high, not {L_bounds!r}")
+    out = {"L_km": float("nan"), "scale": 0.0, "rms": float("nan"), "corr": corr, "found": False, "at_bound": False,
+           "nbins_used": int(n.size)}
+    if n.size < 3:
+        return out
+
+    def s_and_J(logL):
+        Cm = _corr_at(kind, float(np.exp(logL)), chord2)
+        den = float(np.sum(n * Cm * Cm))
+        s = max(float(np.sum(n * Cm * cov)) / den, 0.0) if den > 0.0 else 0.0
+        r = cov - s * Cm
+        return s, float(np.sum(n * r * r))
+
+    grid = np.linspace(np.log(lo), np.log(hi), 64)
+    Jg = [s_and_J(x)[1] for x in grid]
+    i = int(np.argmin(Jg))
+    a, b = grid[max(i - 1, 0)], grid[min(i + 1, 63)]
+    inv_phi = 0.5 * (5.0 ** 0.5 - 1.0)
+    x1, x2 = b - inv_phi * (b - a), a + inv_phi * (b - a)
+    J1, J2 = s_and_J(x1)[1], s_and_J(x2)[1]
+    while b - a > 1e-9:                                       # (on log L: 1e-9 relative in L)
+        if J1 <= J2:
+            b, x2, J2 = x2, x1, J1
+            x1 = b - inv_phi * (b - a)
+            J1 = s_and_J(x1)[1]
+        else:
+            a, x1, J1 = x1, x2, J2
+            x2 = a + inv_phi * (b - a)
+            J2 = s_and_J(x2)[1]
+    x = 0.5 * (a + b)
+    s, J = s_and_J(x)
+    for xe in (grid[0], grid[-1]):                            # an end of the bounds that is no worse: the minimum is there
+        se, Je = s_and_J(xe)
+        if Je <= J:
+            x, s, J = xe, se, Je
+    L = float(np.exp(x))
+    out.update(L_km=L, scale=s, rms=float(np.sqrt(J / np.sum(n))), found=bool(s > 0.0),
+               at_bound=bool(abs(x - grid[0]) <= 1e-6 or abs(x - grid[-1]) <= 1e-6))
+    return out
+
+
+def estimate_corr_length(Xa, Y, Sa, So, lat, lon, scale=1.0, corr="gaussian", **kw):
+    """The correlation length the month's own innovations support, with the gridded convention of ``OI_dense`` (same ``ok``
+    mask, same clamp of ``Y`` -- on a copy: the caller's arrays are not altered): u = (Y - Xa) / sqrt(Sa scale) at the observed
+    cells (cells with ``Sa scale == 0`` dropped) -> ``innovation_covariogram`` (``max_km``, ``nbins``, ``ctx`` from ``kw``) ->
+    ``fit_correlation`` (``L_bounds``, ``min_count`` from ``kw``).  -> the fit dict with the covariogram under ``"covariogram"``."""
+    cg_kw = {k: kw.pop(k) for k in ("max_km", "nbins", "ctx") if k in kw}
+    fit_kw = {k: kw.pop(k) for k in ("L_bounds", "min_count") if k in kw}
+    if kw:
+        raise TypeError(f"estimate_corr_length: unexpected arguments {sorted(kw)}")
+    for name in ([corr] if isinstance(corr, str) else corr):
+        corr_kind(name)                                       # (ValueError before anything is touched)
+    Xa, Sa, So = np.asarray(Xa, dtype=np.float64), np.asarray(Sa, dtype=np.float64), np.asarray(So, dtype=np.float64)
+    Y = np.array(Y, dtype=np.float64)
+    Y[Y < 0] = 0.0
+    var = np.ravel(Sa) * float(scale)
+    ok = np.isfinite(np.ravel(Y)) & np.isfinite(np.ravel(So)) & np.isfinite(np.ravel(Xa)) & np.isfinite(np.ravel(Sa)) & (var != 0)
+    cell = np.flatnonzero(ok)
+    cg = innovation_covariogram(np.ravel(lat)[cell], np.ravel(lon)[cell], (np.ravel(Y) - np.ravel(Xa))[cell],
+                                sigma=np.sqrt(var[cell]), **cg_kw)
+    return {**fit_correlation(cg, corr, **fit_kw), "covariogram": cg}

@@ -84,7 +84,8 @@ class oisatgmi(object):
 
     # ---- analysis mode (extension; the signature of oi() is the reference's) -----------------------------
     #   mode        attribute `oi_mode`        | env OISAT_OI_MODE        diag (default) | dense | tiled
-    #   L           attribute `corr_length_km` | env OISAT_CORR_LENGTH_KM km, default 300           (dense, tiled)
+    #   L           attribute `corr_length_km` | env OISAT_CORR_LENGTH_KM km, default 300, or `auto`: fitted to the covariogram of
+    #               the month's own innovations (dense.estimate_corr_length; oi_info["corr_fit"]; 300 if no fit is found)  (dense, tiled)
     #   model       attribute `oi_correlation` | env OISAT_CORRELATION    gaussian (default) | gaspari_cohn | soar  (dense, tiled)
     #   tile size   attribute `tile_deg`       | env OISAT_TILE_DEG       degrees, default 30       (tiled; halo = 3 L,
     #               gaspari_cohn: its support 3.65 L, soar: 6.52 L)
@@ -98,6 +99,13 @@ class oisatgmi(object):
         if v is None:
             v = os.environ.get(env)
         return cast(default if v in (None, "") else v)
+
+    @staticmethod
+    def _corr_length(v):
+        """A length in km, or ``"auto"`` (any case): estimate it from the innovations.  Anything else is a ``ValueError``."""
+        if isinstance(v, str) and v.strip().lower() == "auto":
+            return "auto"
+        return float(v)
 
     def _oi_grid(self):
         lat, lon = getattr(self, "grid_lat", None), getattr(self, "grid_lon", None)
@@ -127,7 +135,7 @@ class oisatgmi(object):
             return
         if mode not in ("dense", "tiled"):
             raise ValueError(f"OISAT_OI_MODE / oi_mode must be diag, dense or tiled, not {mode!r}")
-        L = self._oi_setting("corr_length_km", "OISAT_CORR_LENGTH_KM", 300.0, float)
+        L = self._oi_setting("corr_length_km", "OISAT_CORR_LENGTH_KM", 300.0, self._corr_length)
         corr = self._oi_setting("oi_correlation", "OISAT_CORRELATION", "gaussian").lower()
         if corr not in ("gaussian", "gaspari_cohn", "soar"):
             raise ValueError(f"OISAT_CORRELATION / oi_correlation must be gaussian, gaspari_cohn or soar, not {corr!r}")
@@ -165,6 +173,15 @@ class oisatgmi(object):
         from . import optimal_interpolation as oi_mod
         index, scale, curve, found = oi_mod.regularization_pick(Sa, So, reg_index)
         print("The regularization factor is " + str(scale))
+        corr_fit = None
+        if isinstance(L, str):                                   # "auto": the length the month's own innovations support
+            corr_fit = dense.estimate_corr_length(xa, y, Sa, So, lat, lon, scale=scale, corr=corr)
+            corr_fit.pop("covariogram", None)
+            if corr_fit["found"]:
+                L = float(corr_fit["L_km"])
+            else:                                                # (the knee_found convention: say so once, use the default)
+                L = 300.0
+                print("No correlation length could be fitted to the innovations; using 300 km")
         if mode == "dense":
             xb, inc, info = dense.OI_dense(xa, y, Sa, So, lat, lon, L, scale=scale, want_error=want_error, corr=corr)
         else:
@@ -189,8 +206,11 @@ class oisatgmi(object):
                 ak[~observed & np.isfinite(xa)] = 0.0
             for a in (inc, err, ak):
                 a[~np.isfinite(xa)] = np.nan
-        return (xb, ak, inc, err), {"mode": mode, "corr_length_km": L, "correlation": corr, "scale": scale, "reg_index": index, "knee_found": found,
-                                    "nobs": info["nobs"], "unobserved": unobserved, "want_error": want_error}
+        out_info = {"mode": mode, "corr_length_km": L, "correlation": corr, "scale": scale, "reg_index": index, "knee_found": found,
+                    "nobs": info["nobs"], "unobserved": unobserved, "want_error": want_error}
+        if corr_fit is not None:
+            out_info["corr_fit"] = corr_fit
+        return (xb, ak, inc, err), out_info
 
     def scaling_factor(self):
         """posterior / prior model column with NaN, inf and 0 mapped to 1.0 -- the field the downstream
