@@ -88,9 +88,14 @@ int oisat_prof_collect(oisat_ctx* h, int cap, char (*names)[64], double* total_m
 /* ---- element-wise OI: optimal_interpolation.py:6-52 ------------------------------------------ */
 /* Regularisation sweep, optimal_interpolation.py:26-33: for each scale s,
  *   t = Sa*s; K = t*(t+So)^-1; Sb = (1-K)*t; AK = 1 - Sb/t; mean_s = nanmean(AK).
- * Sa, So: dev, n elements.  scales: HOST doubles (nscales <= OISAT_MAX_SCALES).
- * mean_out / count_out: HOST arrays of nscales (sum of non-NaN AK / count; count of non-NaN).
- * Synchronises (returns host values).  Deterministic: fixed launch shape, fixed reduction order. */
+ * Sa, So: dev, n elements.  scales: HOST doubles (1 <= nscales <= OISAT_MAX_SCALES, else OISAT_EINVAL).
+ * mean_out / count_out: HOST arrays of nscales (sum of non-NaN AK / count; count of non-NaN; count_out may be NULL).
+ * Synchronises (returns host values).  Deterministic: fixed launch shape, fixed reduction order.
+ * The means are taken over AK = K (Sb/t = 1 - K in real arithmetic; NaN where t == 0, as 0/0 is), one division per cell and
+ * scaling: each is within 1.5 * 2^-52 ABSOLUTE of the mean of the reference's 1 - Sb/t wherever 0 <= K <= 1.  That is nothing
+ * on curves of 0.1 .. 1, and it is the reference form's own rounding noise: where Sa/So is near 1e-10 the means are
+ * 1e-11 .. 1e-9, the reference's curve is this one plus that noise, and Kneedle finds a knee in the noise that the smooth
+ * curve does not have (oisat_oi_fused then answers index 0 where the reference picks some index of its noise). */
 int oisat_oi_curve(oisat_ctx* h, int dtype, const void* Sa, const void* So, int64_t n,
                    const double* scales, int nscales, double* mean_out, int64_t* count_out);
 
@@ -102,7 +107,11 @@ int oisat_oi_apply(oisat_ctx* h, int dtype, const void* Xa, void* Y_inout, const
 
 /* Fully device-side OI: sweep + knee pick (Kneedle, the algorithm of kneed.KneeLocator used at
  * optimal_interpolation.py:37-41, restated) + analysis, no host round trip; graph-capturable.
- * index_dev: dev int32[1] receives the chosen index; curve_dev: dev double[nscales] (may be NULL). */
+ * index_dev: dev int32[1] receives the chosen index; curve_dev: dev double[nscales] (may be NULL).
+ * forced_index >= 0 (< nscales) bypasses the pick; with fewer than three scales the index is 0.  When the library is to pick
+ * (forced_index < 0, nscales >= 3) the LAST entry of scales must be finite and no smaller than any other entry, else
+ * OISAT_EINVAL and nothing is written: the walk ends at the table's maximum, and past a maximum that is not the last point it
+ * would look one element beyond the difference curve (kneed itself raises IndexError on such a table). */
 int oisat_oi_fused(oisat_ctx* h, int dtype, const void* Xa, void* Y_inout, const void* Sa,
                    const void* So, int64_t n, const double* scales, int nscales, int forced_index,
                    void* Xb, void* AK, void* inc, void* err, int32_t* index_dev, double* curve_dev);

@@ -25,7 +25,9 @@ constexpr int kCurveWaves = kCurveBlocks * kCurveThreads / kWave;
 // (dropped by nanmean) where t = 0 -- within one rounding of the reference's value (1.1e-16 absolute in float64, nine orders
 // inside the curve's 1e-12 parity bar and four inside the smallest knee margin seen, 1.9e-6), for one division per (cell,
 // scaling) instead of two: the sweep is bound by exactly those divisions.  The analysis kernel (oi_apply_kernel) keeps the
-// reference's order: its AK FIELD is a returned quantity.
+// reference's order: its AK FIELD is a returned quantity.  The bound is ABSOLUTE (1.5 * 2^-52 with all three roundings): where
+// Sa / So ~ 1e-10 it is the reference form's own noise on means of 1e-10, and the reference's knee pick sits in that noise while
+// this curve has no knee (include/oisat.h at oisat_oi_curve; tests/test_gpu_elementwise_abi.py pins it).
 template <typename T>
 __device__ __forceinline__ T ak_of(T sa, T so, T s) {
     T t = sa * s;
@@ -417,6 +419,13 @@ extern "C" int oisat_oi_fused(oisat_ctx* h, int dtype, const void* Xa, void* Y, 
     ARG_CHECK(h && Xa && Y && Sa && So && scales && n > 0);
     ARG_CHECK(nscales > 0 && nscales <= OISAT_MAX_SCALES && forced_index < nscales);
     ARG_CHECK(dtype == OISAT_F32 || dtype == OISAT_F64);
+    if (forced_index < 0 && nscales >= 3) {
+        // The knee walk (kneedle_index_block) ends where xn == 1, and reads df[i + 1] until then: that stays inside df only if
+        // the LAST point is the table's maximum.  (kneed and the host twin index past their arrays on such a table.)
+        bool last_is_finite_max = std::isfinite(scales[nscales - 1]);
+        for (int i = 0; i + 1 < nscales; ++i) last_is_finite_max = last_is_finite_max && !(scales[nscales - 1] < scales[i]);
+        ARG_CHECK(last_is_finite_max);
+    }
     if (dtype == OISAT_F32)
         return fused_impl<float>(h, (const float*)Xa, (float*)Y, (const float*)Sa, (const float*)So, n, scales, nscales,
                                  forced_index, (float*)Xb, (float*)AK, (float*)inc, (float*)err, index_dev, curve_dev);
