@@ -404,7 +404,7 @@ int oisat_potrf(oisat_ctx* h, float* S, int64_t m, int64_t ld, int* info_host);
  * the zeros stay.  Systems the task graph does not take (under three block rows, OISAT_DAG=0) are factored densely.
  * The handle remembers the envelope with the factor: oisat_gain_solve and oisat_potrs sweep inside it (same bits: the
  * skipped blocks are zeros).  Who reads an enveloped factor, per function:
- *   oisat_gain_solve, oisat_potrs                          walk the envelope only
+ *   oisat_gain_solve, oisat_potrs, oisat_trsm_rows_bwd     walk the envelope only
  *   oisat_trsm_rows, oisat_posterior_error, oisat_gain_diag, a download of S
  *                                                          read densely and find the zeros of the build
  *   oisat_potrf, oisat_factor_adopt                        forget the envelope (dense sweeps from then on)
@@ -638,6 +638,48 @@ int oisat_posterior_error(oisat_ctx* h, const float* L, int64_t m, int64_t ld, c
  * (the dense counterpart of AK = 1 - Sb/(Sa*reg), optimal_interpolation.py:31).  ak_out: dev double[m]. */
 int oisat_gain_diag(oisat_ctx* h, const float* L, int64_t m, int64_t ld, const double* ovar, int64_t chunk_rows,
                     double* ak_out);
+
+/* ---- randomized analysis error and averaging kernel ----------------------------------------
+ * With S = L L^T, w a vector of independent +-1 entries and u = L^-T w, E[u u^T] = S^-1.  Hence, from K probes u_k,
+ *   q_i = g_i^T S^-1 g_i = E[(g_i^T u)^2]   (g_i = row i of B H^T; the analysis error variance is sig_i^2 - q_i)
+ *   (S^-1)_aa = E[u_a^2]                     (oisat_gain_diag's ak_a = 1 - R_aa (S^-1)_aa)
+ * as sample means whose standard errors come from the fourth moments: the four calls below produce the probes and the
+ * sums of squares and of fourth powers; the caller (oisatgmi/dense.py: posterior_error_mc) forms means and errors.
+ * All device calls are asynchronous on the handle's stream and use no workspace.
+ *
+ * oisat_probe_sign (host only): *sign_out = +1.0f or -1.0f, a counter-based hash of (seed, probe, column) -- splitmix64's
+ * finaliser applied three times, mix(mix(mix(seed) ^ probe) ^ column), top bit -- the same function on host and device.
+ * oisat_probe_fill: X dev float[nrows][ldx], ldx >= roundup(m,128): X[r][a] = oisat_probe_sign(seed, first_probe + r, a) for
+ * a < m, exact zeros in the columns m..ldx.  first_probe >= 0, nrows > 0.
+ *
+ * oisat_trsm_rows_bwd: X <- X L^-1 for nrows (multiple of 128) rows, i.e. row r becomes (L^-T x_r)^T: the backward
+ * counterpart of oisat_trsm_rows, same arguments and checks; must follow a factorization of this L on this handle
+ * (oisat_potrf, oisat_potrf_env / _fwd, oisat_factor_adopt).  Block columns j = nb-1 .. 0, one launch each: the workgroup
+ * of block column k < j applies X_k -= X_j L_jk (128 x 128 x 128 on v_mfma_f32_32x32x2_f32, L_jk read as it lies), the one of
+ * k = j-1 then multiplies by the inverted diagonal block and so finishes the next column.  Stream order is the only
+ * dependency and one workgroup writes a tile per launch: the bits do not depend on timing.  On an enveloped factor only
+ * the blocks first[j] <= k < j are visited (the handle keeps a host copy of first[] with the factor; it is dropped where
+ * the envelope is forgotten) and nothing outside the envelope is read.  The padding rows of L are identity: columns
+ * m..mp of X pass through unchanged.
+ *
+ * oisat_probe_spread: t_ik = gsig_i sum_a C(i,a) osig_a U[k][a] under the handle's correlation model, U dev
+ * float[nprobe][ldu] (ldu >= m); sum2_out[i] (+)= sum_k t_ik^2, sum4_out[i] (+)= sum_k t_ik^4, dev double[n]; accumulate = 0
+ * overwrites.  nx > 0: the cells are an ny x nx grid taken in 32 x 8 patches (oisat_apply_increment_grid); nx = 0: ny
+ * consecutive cells in runs of 256 (oisat_apply_increment).  glat / olat_sorted (both or the pair counts as NULL) enable the
+ * latitude window and the bounding-sphere cull at the library's 2^-52 chord; NULL: every pair is evaluated.  |p - q|^2 is
+ * formed in double, the correlation, the products and the per-probe sums in fp32, the squares and fourth powers are added
+ * in double.  nprobe a multiple of 32 with 32 <= nprobe <= 4096, anything else is OISAT_EINVAL.
+ *
+ * oisat_probe_diag: per observation a < m, sum2_out[a] (+)= sum_k U[k][a]^2, sum4_out[a] (+)= sum_k U[k][a]^4 (double sums
+ * in the order of k), dev double[m]; nprobe >= 1. */
+int oisat_probe_sign(uint64_t seed, int64_t probe, int64_t column, float* sign_out);
+int oisat_probe_fill(oisat_ctx* h, uint64_t seed, int64_t first_probe, float* X, int64_t nrows, int64_t ldx, int64_t m);
+int oisat_trsm_rows_bwd(oisat_ctx* h, const float* L, int64_t m, int64_t ld, float* X, int64_t nrows, int64_t ldx);
+int oisat_probe_spread(oisat_ctx* h, const double* gxyz, const double* gsig, int64_t ny, int64_t nx, const double* oxyz,
+                       const double* osig, const float* U, int64_t nprobe, int64_t ldu, int64_t m, double g,
+                       const double* glat, const double* olat_sorted, int accumulate, double* sum2_out, double* sum4_out);
+int oisat_probe_diag(oisat_ctx* h, const float* U, int64_t nprobe, int64_t ldu, int64_t m, int accumulate,
+                     double* sum2_out, double* sum4_out);
 
 /* The ticket list of a task-graph launch over nsys systems of block_rows[s] block rows (largest first), as the library would
  * build it -- host only, no device: int32 quadruples (kind, system, i, j) with kind 0 = chain of `system` (i = first row of its

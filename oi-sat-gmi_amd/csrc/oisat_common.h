@@ -35,6 +35,7 @@ struct ChFactor {                // what the triangular solves need besides L: t
     const int* env = nullptr;    // device, first[mp/128] | last[mp/128]: the factor's block envelope (oisat_potrf_env), or nullptr = dense
     int band = 0;                // enveloped: max over b of (b - first[b]) + 1 block rows, from the host table; 0 = dense / adopted
                                  // (the sweeps' launch rule, oisat_trsv_plan)
+    std::vector<int32_t> first;  // enveloped: host copy of first[mp/128] (oisat_trsm_rows_bwd sizes its launches with it); empty = dense
     // oisat_potrf_env_fwd: the right-hand side whose forward vector the factorization launch left in workspace 5 (with the
     // right-hand side re-armed and the solve state reset), or nullptr.  oisat_gain_solve of the same d takes it, once.
     const double* fwd_d = nullptr;

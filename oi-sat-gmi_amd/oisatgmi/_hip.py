@@ -129,6 +129,12 @@ SIGNATURES = {
     "oisat_trsm_rows": (C.c_int, [_c_ctx, _ptr, _i64, _i64, _ptr, _i64, _i64]),
     "oisat_posterior_error": (C.c_int, [_c_ctx, _ptr, _i64, _i64, _ptr, _ptr, _i64, _i64, _i64, _ptr, _ptr, C.c_double, _i64, _ptr]),
     "oisat_gain_diag": (C.c_int, [_c_ctx, _ptr, _i64, _i64, _ptr, _i64, _ptr]),
+    "oisat_probe_sign": (C.c_int, [C.c_uint64, _i64, _i64, C.POINTER(C.c_float)]),
+    "oisat_probe_fill": (C.c_int, [_c_ctx, C.c_uint64, _i64, _ptr, _i64, _i64, _i64]),
+    "oisat_trsm_rows_bwd": (C.c_int, [_c_ctx, _ptr, _i64, _i64, _ptr, _i64, _i64]),
+    "oisat_probe_spread": (C.c_int, [_c_ctx, _ptr, _ptr, _i64, _i64, _ptr, _ptr, _ptr, _i64, _i64, _i64, C.c_double, _ptr, _ptr,
+                                     C.c_int, _ptr, _ptr]),
+    "oisat_probe_diag": (C.c_int, [_c_ctx, _ptr, _i64, _i64, _i64, C.c_int, _ptr, _ptr]),
     "oisat_apply_increment": (C.c_int, [_c_ctx, C.c_int, _ptr, _ptr, _i64, _ptr, _ptr, _ptr, _i64, C.c_double, _ptr,
                                         _ptr, _ptr, _ptr, _ptr]),
     "oisat_apply_increment_grid": (C.c_int, [_c_ctx, C.c_int, _ptr, _ptr, _i64, _i64, _ptr, _ptr, _ptr, _i64, C.c_double, _ptr,

@@ -38,6 +38,41 @@ SCHEDULE_ENV_DAG, SCHEDULE_ENV_DAG_FWD = 1, 2      # oisat_potrf_env_fwd's sched
 # relative float64 residual |d - S z| / |d| at which the gain solve stops refining (oisat_gain_solve): the increment is K r
 # away from the exact one and |K| <= 1, so the fields are then within 1e-6 |d| -- a tenth of the 1e-5 bar
 REFINE_TOL = float(os.environ.get("OISAT_REFINE_TOL", "1e-6"))
+PROBE_PANEL = 128             # probes per pass of the randomized error estimate (one row panel of oisat_trsm_rows_bwd)
+
+
+def _mean_and_var(sum2, sum4, K):
+    """Mean of K samples x_k^2 and the sample variance of that mean, from sum x_k^2 and sum x_k^4."""
+    mean = np.asarray(sum2, dtype=np.float64) / K
+    var = np.maximum(np.asarray(sum4, dtype=np.float64) / K - mean * mean, 0.0) / (K - 1)
+    return mean, var
+
+
+def combine_error_estimates(sig2, q, q_var, obs_cell, R, s, s_var):
+    """Analysis error variance per cell from the two randomized estimates, pure NumPy.
+
+    ``sig2`` (n,): background variance; ``q``, ``q_var`` (n,): estimate of g_i^T S^-1 g_i and the variance of that estimate;
+    ``obs_cell`` (m,) or None: the cell each observation sits on; ``R``, ``s``, ``s_var`` (m,): observation variance, estimate
+    of (S^-1)_aa and its variance.  Every cell gets A = sig2 - q with variance q_var.  A cell that carries EXACTLY ONE
+    observation a also has A = R_a (1 - R_a s_a), variance R_a^4 s_var_a, which is taken where that variance is the smaller
+    one.  A is clipped to [0, sig2], on the singly observed cells to [0, min(sig2, R_a)] (A <= R there: the analysis is no
+    worse than the observation).  Returns ``(A, A_var)``."""
+    sig2 = np.ravel(np.asarray(sig2, dtype=np.float64))
+    A = sig2 - np.ravel(np.asarray(q, dtype=np.float64))
+    A_var = np.array(np.ravel(q_var), dtype=np.float64)
+    hi = sig2.copy()
+    if obs_cell is not None and np.size(obs_cell):
+        cell = np.ravel(np.asarray(obs_cell, dtype=np.int64))
+        R = np.ravel(np.asarray(R, dtype=np.float64))
+        single = np.flatnonzero(np.bincount(cell, minlength=sig2.size)[cell] == 1)     # observations alone on their cell
+        ci = cell[single]
+        A2 = R[single] * (1.0 - R[single] * np.ravel(s)[single])
+        v2 = R[single] ** 4 * np.ravel(s_var)[single]
+        take = v2 < A_var[ci]
+        A[ci[take]] = A2[take]
+        A_var[ci[take]] = v2[take]
+        hi[ci] = np.minimum(hi[ci], R[single])
+    return np.clip(A, 0.0, hi), A_var
 
 
 def unit_vectors(lat_deg, lon_deg) -> np.ndarray:
@@ -264,6 +299,7 @@ class DenseAnalysis:
         self.mp = -(-m // NB) * NB
         o = self._sort_by_latitude(obs_lat, obs_lon)
         cell = np.ascontiguousarray(np.ravel(obs_cell)[o], dtype=np.int64)
+        self._cell_sorted = cell                               # (posterior_error_mc: which cells carry exactly one observation)
         c.upload_into(self.oxyz.ptr, unit_vectors(np.ravel(obs_lat)[o], np.ravel(obs_lon)[o]))
         c.upload_into(self.osig.ptr, self._gsig_host[cell], dtype=np.float64)
         c.upload_into(self.ovar.ptr, np.ravel(obs_var)[o], dtype=np.float64)
@@ -365,6 +401,51 @@ class DenseAnalysis:
             self._ak = c.alloc(self.max_obs * 8)
         c.check(c.lib.oisat_gain_diag(c.h, self.S.ptr, self.m, self.mp, self.ovar.ptr, int(chunk_rows), self._ak.ptr))
         return self._unsort(c.download(self._ak.ptr, (self.m,), np.float64))
+
+    def posterior_error_mc(self, nprobe: int = 256, seed: int = 0, gridded: bool = False):
+        """Randomized estimate of ``posterior_error()`` and ``gain_diag()`` from ``nprobe`` Rademacher probes pushed through
+        the factor that ``run()`` left in HBM: u = L^-T w has E[u u^T] = S^-1, so the error
+        variance is sig_i^2 - E[(g_i^T u)^2] and diag(K H) at observation a is 1 - R_aa E[u_a^2].  Panels of 128 probes:
+        fill, backward row sweep, then the per-observation and per-cell sums of squares and fourth powers (accumulating).
+        ``gridded``: every observation sits on its cell's centre (``OI_dense`` without ``obs``); a cell that carries exactly
+        one observation then has the second estimate R_aa ak_a (``combine_error_estimates``).
+        Returns ``err`` (grid shape, float32), ``err_se``, ``ak_obs`` (m, caller order), ``ak_obs_se``, ``nprobe`` and the
+        raw estimates ``q`` / ``q_se`` (cells) and ``s`` / ``s_se`` (observations, caller order).  Every standard error is the
+        sample's own, from its fourth moments; same seed, same bits."""
+        K = int(nprobe)
+        if K < PROBE_PANEL or K % PROBE_PANEL:
+            raise ValueError(f"nprobe must be a positive multiple of {PROBE_PANEL}, got {nprobe}")
+        c, lib, h = self.ctx, self.ctx.lib, self.ctx.h
+        m, mp, n = self.m, self.mp, self.n
+        if not hasattr(self, "_probe"):
+            self._probe = c.alloc(PROBE_PANEL * self.mp_max * 4)        # one panel of probes, allocated once
+            self._mc_sums = c.alloc(2 * (self.n + self.max_obs) * 8)    # sum2 | sum4 of the cells, then of the observations
+        cell2, cell4 = self._mc_sums.at(0), self._mc_sums.at(n * 8)
+        obs2, obs4 = self._mc_sums.at(2 * n * 8), self._mc_sums.at((2 * n + self.max_obs) * 8)
+        c.check(lib.oisat_set_correlation(h, self._kind))               # (the model of the run that left the factor)
+        ny, nx = self._ny, self._nx
+        for p in range(K // PROBE_PANEL):
+            acc = 1 if p else 0
+            c.check(lib.oisat_probe_fill(h, int(seed) & (2 ** 64 - 1), p * PROBE_PANEL, self._probe.ptr, PROBE_PANEL, mp, m))
+            c.check(lib.oisat_trsm_rows_bwd(h, self.S.ptr, m, mp, self._probe.ptr, PROBE_PANEL, mp))
+            c.check(lib.oisat_probe_diag(h, self._probe.ptr, PROBE_PANEL, mp, m, acc, obs2, obs4))
+            c.check(lib.oisat_probe_spread(h, self.gxyz.ptr, self.gsig.ptr, ny, nx, self.oxyz.ptr, self.osig.ptr, self._probe.ptr,
+                                           PROBE_PANEL, mp, m, self._g, self.glat.ptr, self.olat.ptr, acc, cell2, cell4))
+        self.check()
+        cs = c.download(cell2, (2, n), np.float64)
+        q, q_var = _mean_and_var(cs[0], cs[1], K)
+        s, s_var = _mean_and_var(c.download(obs2, (m,), np.float64), c.download(obs4, (m,), np.float64), K)
+        R = c.download(self.ovar.ptr, (m,), np.float64)
+        sig2 = np.asarray(self._gsig_host, dtype=np.float64) ** 2
+        obs_cell = getattr(self, "_cell_sorted", None) if gridded and not self._direct_innovation else None
+        A, A_var = combine_error_estimates(sig2, q, q_var, obs_cell, R, s, s_var)
+        err = np.sqrt(A)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            err_se = np.where(err > 0, np.sqrt(A_var) / (2.0 * err), 0.0)
+        return {"err": err.reshape(self.shape).astype(np.float32), "err_se": err_se.reshape(self.shape),
+                "ak_obs": self._unsort(1.0 - R * s), "ak_obs_se": self._unsort(R * np.sqrt(s_var)), "nprobe": K,
+                "q": q.reshape(self.shape), "q_se": np.sqrt(q_var).reshape(self.shape),
+                "s": self._unsort(s), "s_se": self._unsort(np.sqrt(s_var))}
 
     # ---- outputs
     def check(self):
@@ -984,7 +1065,7 @@ class MonthTileBatch:
 
 
 def OI_dense(Xa, Y, Sa, So, lat, lon, L_km, scale=1.0, refine=2, obs=None, dtype=None, want_error=False, tol=None,
-             corr="gaussian"):
+             corr="gaussian", nprobe=256, seed=0):
     """Dense-covariance analysis with the reference's gridded argument convention.
 
     ``Xa, Sa``: (ny, nx) background and its variance; ``Y, So``: (ny, nx) observations and their
@@ -993,8 +1074,14 @@ def OI_dense(Xa, Y, Sa, So, lat, lon, L_km, scale=1.0, refine=2, obs=None, dtype
     ``Y, So`` by scattered observations: dict(lat, lon, y, var).  ``corr``: ``"gaussian"`` (default), ``"gaspari_cohn"`` or ``"soar"``.
     Returns ``(Xb, increment, info)``; unlike the element-wise ``OI`` every cell is analysed
     (unobserved cells get the spread increment instead of NaN).
+    ``want_error``: True = the exact ``err`` / ``ak`` / ``ak_obs`` (n m^2 flop); ``"mc"`` = their randomized estimates from
+    ``nprobe`` probes (``DenseAnalysis.posterior_error_mc``) with ``err_se`` / ``ak_obs_se`` beside them and
+    ``info["error_method"] = "mc"``.
     """
     corr_kind(corr)                                           # (ValueError before anything is touched)
+    mc = isinstance(want_error, str)
+    if mc and want_error != "mc":
+        raise ValueError(f"want_error is False, True or 'mc', got {want_error!r}")
     Xa = np.asarray(Xa)
     if obs is None:
         Y[Y < 0] = 0.0                                        # same clamp as optimal_interpolation.py:14
@@ -1014,9 +1101,12 @@ def OI_dense(Xa, Y, Sa, So, lat, lon, L_km, scale=1.0, refine=2, obs=None, dtype
         if want_error:
             extra = {"ak": np.full(np.shape(Xa), np.nan), "err": np.sqrt(np.asarray(Sa, dtype=np.float64) * scale),
                      "ak_obs": np.empty(0)}
+            if mc:
+                extra.update(err=extra["err"].astype(np.float32), err_se=np.zeros(np.shape(Xa)), ak_obs_se=np.empty(0),
+                             error_method="mc", nprobe=int(nprobe))
         return (np.array(Xa, dtype=dt), np.zeros(np.shape(Xa), dtype=dt),
                 {"nobs": 0, "residuals": [], "cells": cell, "z": np.empty(0), **extra})
-    plan = DenseAnalysis(lat, lon, max_obs=int(cell.size), dtype=dt, diag_chunk_rows=4096 if want_error else 0)
+    plan = DenseAnalysis(lat, lon, max_obs=int(cell.size), dtype=dt, diag_chunk_rows=4096 if want_error and not mc else 0)
     xa_f = np.where(np.isfinite(Xa), Xa, 0.0)
     sa_f = np.where(np.isfinite(Sa), Sa, 0.0)
     plan.load_background(xa_f, sa_f, scale=scale)
@@ -1028,12 +1118,15 @@ def OI_dense(Xa, Y, Sa, So, lat, lon, L_km, scale=1.0, refine=2, obs=None, dtype
         # diag(K H) at a cell = sum over the observations INSIDE that cell of diag(H K) at the observation
         # ((B H^T S^-1)[cell(a), a] = (H B H^T S^-1)[a, a]); with one observation per cell -- the reference's
         # case -- this is AK of optimal_interpolation.py:31.  np.add.at: deterministic for repeated cells.
-        ak_obs = plan.gain_diag()
+        est = plan.posterior_error_mc(nprobe=nprobe, seed=seed, gridded=obs is None) if mc else None
+        ak_obs = est["ak_obs"] if mc else plan.gain_diag()
         ak_sum = np.zeros(Xa.size)
         np.add.at(ak_sum, cell, ak_obs)
         ak = np.full(Xa.size, np.nan)
         ak[cell] = ak_sum[cell]
-        extra = {"ak": ak.reshape(np.shape(Xa)), "err": plan.posterior_error(), "ak_obs": ak_obs}
+        extra = {"ak": ak.reshape(np.shape(Xa)), "err": est["err"] if mc else plan.posterior_error(), "ak_obs": ak_obs}
+        if mc:
+            extra.update(err_se=est["err_se"], ak_obs_se=est["ak_obs_se"], error_method="mc", nprobe=est["nprobe"])
     bad = ~np.isfinite(Xa)
     if bad.any():
         xb = xb.copy()

@@ -94,6 +94,10 @@ class oisatgmi(object):
     #   knee        attribute `oi_reg_index`: force the index into the 99-scaling sweep (all modes)
     #   error/AK    attribute `oi_want_error`  | env OISAT_OI_ERROR       1 (default) | 0: error_OI / ak_OI left NaN -- the
     #               posterior error costs n m^2 flop, 1e16 for a global 720x1440 / 1e5-observation analysis (dense, tiled)
+    #               mc | mc:<K> (dense only): the randomized estimate of both from K probes (default 256, a multiple of 128)
+    #               through the factor the analysis leaves behind, with its own standard errors in oi_info["err_se"] /
+    #               ["ak_obs_se"] (dense.DenseAnalysis.posterior_error_mc); tiled: ValueError -- the
+    #               tiles' exact error is affordable
     def _oi_setting(self, attr, env, default, cast=str):
         v = getattr(self, attr, None)
         if v is None:
@@ -106,6 +110,28 @@ class oisatgmi(object):
         if isinstance(v, str) and v.strip().lower() == "auto":
             return "auto"
         return float(v)
+
+    @staticmethod
+    def _error_setting(v):
+        """``OISAT_OI_ERROR`` / ``oi_want_error`` -> ``(want_error, nprobe)``: ``(False, 0)`` for 0 / false / no / off,
+        ``("mc", K)`` for ``mc`` / ``mc:<K>`` (K a positive multiple of 128; anything else behind ``mc`` is a ``ValueError``),
+        ``(True, 0)`` for every other value, as before."""
+        v = str(v).strip().lower()
+        if v in ("0", "false", "no", "off"):
+            return False, 0
+        if not v.startswith("mc"):
+            return True, 0
+        if v == "mc":
+            return "mc", 256
+        try:
+            if v[2] != ":":
+                raise ValueError
+            K = int(v[3:])
+        except ValueError:
+            raise ValueError(f"OISAT_OI_ERROR / oi_want_error: expected mc or mc:<probes>, not {v!r}") from None
+        if K < 128 or K % 128:
+            raise ValueError(f"OISAT_OI_ERROR / oi_want_error: the number of probes must be a positive multiple of 128, not {K}")
+        return "mc", K
 
     def _oi_grid(self):
         lat, lon = getattr(self, "grid_lat", None), getattr(self, "grid_lon", None)
@@ -142,7 +168,9 @@ class oisatgmi(object):
         unobserved = self._oi_setting("oi_unobserved", "OISAT_UNOBSERVED", "nan").lower()
         if unobserved not in ("nan", "xa"):
             raise ValueError(f"OISAT_UNOBSERVED / oi_unobserved must be nan or xa, not {unobserved!r}")
-        want_error = self._oi_setting("oi_want_error", "OISAT_OI_ERROR", "1").lower() not in ("0", "false", "no", "off")
+        want_error, nprobe = self._oi_setting("oi_want_error", "OISAT_OI_ERROR", "1", self._error_setting)
+        if want_error == "mc" and mode == "tiled":
+            raise ValueError("OISAT_OI_ERROR / oi_want_error = mc belongs to the dense mode; a tiled analysis has the exact error (1)")
         lat, lon = self._oi_grid()
         xa, y = np.asarray(xa), np.asarray(y)
         if lat.shape != xa.shape[:2] or lon.shape != xa.shape[:2]:
@@ -159,7 +187,7 @@ class oisatgmi(object):
         for tail in np.ndindex(*xa.shape[2:]):
             sl = (slice(None), slice(None)) + tail
             res, info = self._oi_spatial(mode, xa[sl], y[sl], np.asarray(Sa)[sl], np.asarray(So)[sl], lat, lon, L, tile,
-                                         unobserved, reg_index, want_error, corr=corr)
+                                         unobserved, reg_index, want_error, corr=corr, nprobe=nprobe)
             for o, r in zip(outs, res):
                 o[sl] = r
             infos.append(info)
@@ -167,7 +195,7 @@ class oisatgmi(object):
         self.oi_info = dict(infos[0]) if len(infos) == 1 else {**infos[0], "slices": infos}
 
     @staticmethod
-    def _oi_spatial(mode, xa, y, Sa, So, lat, lon, L, tile, unobserved, reg_index, want_error, corr="gaussian"):
+    def _oi_spatial(mode, xa, y, Sa, So, lat, lon, L, tile, unobserved, reg_index, want_error, corr="gaussian", nprobe=256):
         """One (ny, nx) Gaussian-B analysis -> ((Xb, AK, increment, error), info) in the reference's attribute order."""
         from . import dense
         from . import optimal_interpolation as oi_mod
@@ -183,7 +211,8 @@ class oisatgmi(object):
                 L = 300.0
                 print("No correlation length could be fitted to the innovations; using 300 km")
         if mode == "dense":
-            xb, inc, info = dense.OI_dense(xa, y, Sa, So, lat, lon, L, scale=scale, want_error=want_error, corr=corr)
+            xb, inc, info = dense.OI_dense(xa, y, Sa, So, lat, lon, L, scale=scale, want_error=want_error, corr=corr,
+                                           nprobe=nprobe or 256)
         else:
             xb, inc, info = dense.OI_tiled(xa, y, Sa, So, lat, lon, L, tile_deg=tile, scale=scale, want_error=want_error, corr=corr)
         xb, inc = np.array(xb, dtype=np.float64), np.array(inc, dtype=np.float64)
@@ -208,6 +237,8 @@ class oisatgmi(object):
                 a[~np.isfinite(xa)] = np.nan
         out_info = {"mode": mode, "corr_length_km": L, "correlation": corr, "scale": scale, "reg_index": index, "knee_found": found,
                     "nobs": info["nobs"], "unobserved": unobserved, "want_error": want_error}
+        if want_error == "mc":                                  # the estimate's own standard errors travel with it
+            out_info.update(error_method="mc", nprobe=info["nprobe"], err_se=info["err_se"], ak_obs_se=info["ak_obs_se"])
         if corr_fit is not None:
             out_info["corr_fit"] = corr_fit
         return (xb, ak, inc, err), out_info
