@@ -573,7 +573,13 @@ int oisat_potrf_env_fwd(oisat_ctx* h, float* S, int64_t m, int64_t ld, const int
  * anything else in either is OISAT_EINVAL.  Neither changes a bit of any result. */
 int oisat_trsv_plan(int64_t nb, int band, int cu_count, int32_t* two_tiles_out, int32_t* grid_out);
 
-/* z <- L^-T L^-1 z  (dev double[m], fp32 factor, double accumulation). */
+/* z <- L^-T L^-1 z  (dev double[m], fp32 factor, double accumulation).  The sweeps' diagonal solves are products with the inverted
+ * diagonal blocks, which are float32 (a few 2^-24 of their largest entry from the exact inverses), so ONE pass is as far from
+ * the solve on the factor as a float32 substitution.  oisat_potrs therefore corrects once against the factor itself:
+ * x1 = M^-1 z, r = z - L (L^T x1) in double, z <- x1 + M^-1 r -- the blocks' error enters squared.  (oisat_gain_solve's passes are
+ * single ones: it refines against the float64 S instead.)  Of an enveloped factor only the blocks inside the envelope are read.
+ * Cost: two solves (four sweeps) and two O(m^2) passes over the factor by plain kernels, one of them a serial walk down each
+ * column -- more than twice a single solve; a diagnostic entry point, not one for a hot path. */
 int oisat_potrs(oisat_ctx* h, const float* L, int64_t m, int64_t ld, double* z_inout);
 
 /* r = d - (C.*sig sig^T + diag(var)) z  evaluated in double on the fly (iterative refinement).

@@ -2954,17 +2954,73 @@ extern "C" int oisat_potrf_env_fwd(oisat_ctx* h, float* S, int64_t m, int64_t ld
     return potrf_env_entry(h, S, m, ld, first, env_dev, true, d, info_host, schedule_out);
 }
 
+// ---- oisat_potrs' correction against the factor itself ----------------------------------------------------------------------------
+// The sweeps multiply by the inverted diagonal blocks T_b, which are float32 products (a few 2^-24 from the exact inverses):
+// one solve is as far from L^-T L^-1 d as a float32 substitution.  oisat_potrs therefore corrects once against L L^T in
+// double: x1 = M^-1 d, r = d - L (L^T x1), x = x1 + M^-1 r, after which T_b's error enters squared.  Only the lower triangle
+// is read (the diagonal tiles' upper halves are not part of the factor), and of an enveloped factor only the blocks inside
+// the envelope: env = first[nb] | last[nb] as in the sweeps, clamped.  Plain kernels: oisat_potrs is no hot path.
+// t[c] = sum_{r >= c} L[r][c] x[r], one thread per column, rows in ascending order (coalesced across the columns)
+static __global__ __launch_bounds__(256) void potrs_lt_kernel(const float* __restrict__ L, int64_t ld, int64_t mp, const double* __restrict__ x,
+                                                               const int* __restrict__ env, double* __restrict__ t) {
+    const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= mp) return;
+    const int64_t nb = mp / NB, cb = c / NB;
+    int64_t lastb = nb - 1;
+    if (env != nullptr) {
+        lastb = env[nb + cb];
+        lastb = lastb < cb ? cb : (lastb > nb - 1 ? nb - 1 : lastb);
+    }
+    double s = 0.0;
+    for (int64_t r = c; r < (lastb + 1) * NB; ++r) s += (double)L[r * ld + c] * x[r];
+    t[c] = s;
+}
+
+// out[r] = d[r] - sum_{c <= r} L[r][c] t[c] for r < m, 0 in the padding; one wave per row, fixed shuffle tree
+static __global__ __launch_bounds__(256) void potrs_resid_kernel(const float* __restrict__ L, int64_t ld, int64_t m, int64_t mp,
+                                                                  const double* __restrict__ t, const double* __restrict__ d,
+                                                                  const int* __restrict__ env, double* __restrict__ out) {
+    const int lane = threadIdx.x & 63;
+    const int64_t r = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+    if (r >= mp) return;
+    if (r >= m) {
+        if (lane == 0) out[r] = 0.0;
+        return;
+    }
+    const int64_t rb = r / NB;
+    int64_t firstb = 0;
+    if (env != nullptr) {
+        firstb = env[rb];
+        firstb = firstb < 0 ? 0 : (firstb > rb ? rb : firstb);
+    }
+    const float* row = L + r * ld;
+    double s = 0.0;
+    for (int64_t c = firstb * NB + lane; c <= r; c += 64) s += (double)row[c] * t[c];
+#pragma unroll
+    for (int k = 32; k >= 1; k >>= 1) s += __shfl_xor(s, k, kWave);
+    if (lane == 0) out[r] = d[r] - s;
+}
+
 extern "C" int oisat_potrs(oisat_ctx* h, const float* L, int64_t m, int64_t ld, double* z_inout) {
     ARG_CHECK(h && L && z_inout && m > 0);
     ARG_CHECK(h->factor.S == L && h->factor.m == m && h->factor.ld == ld);     // must follow oisat_potrf of this matrix
     h->factor.fwd_d = nullptr;                                  // (the work vectors are about to be reused)
-    double* w = (double*)oisat_ws(h, 5, sizeof(double) * (2 + 8) * h->factor.mp);
+    const int64_t mp = h->factor.mp;                           // (mp / 4 workgroups at the most below: far from 2^31 for any factor that exists)
+    double* w = (double*)oisat_ws(h, 5, sizeof(double) * (2 + 8) * mp);
     if (!w) return OISAT_ENOMEM;
     double* rhs = w;
-    double* fwd = w + h->factor.mp;
-    OISAT_LAUNCH(h, "copy_pad", solve_prep_kernel, dim3(stream_grid(h->factor.mp, 256)), dim3(256), 0, (const double*)z_inout, m,
-                 h->factor.mp, rhs, fwd, (SolveState*)nullptr);
-    return trsv_solve(h, h->factor, rhs, fwd, nullptr, z_inout, 0);
+    double* fwd = w + mp;
+    double* lt = w + 2 * mp;                                    // L^T x1
+    double* d = w + 3 * mp;                                     // the right-hand side: z_inout is about to take x1
+    HIP_TRY(hipMemcpyAsync(d, z_inout, sizeof(double) * m, hipMemcpyDeviceToDevice, h->stream));
+    OISAT_LAUNCH(h, "copy_pad", solve_prep_kernel, dim3(stream_grid(mp, 256)), dim3(256), 0, (const double*)z_inout, m, mp, rhs, fwd,
+                 (SolveState*)nullptr);
+    if (int rc = trsv_solve(h, h->factor, rhs, fwd, nullptr, z_inout, 0)) return rc;          // rhs <- x1 (padded), fwd re-armed
+    OISAT_LAUNCH(h, "potrs_lt", potrs_lt_kernel, dim3((unsigned)cdiv(mp, 256)), dim3(256), 0, h->factor.S, ld, mp, (const double*)rhs,
+                 (const int*)h->factor.env, lt);
+    OISAT_LAUNCH(h, "potrs_resid", potrs_resid_kernel, dim3((unsigned)cdiv(mp * 64, 256)), dim3(256), 0, h->factor.S, ld, m, mp,
+                 (const double*)lt, (const double*)d, (const int*)h->factor.env, rhs);
+    return trsv_solve(h, h->factor, rhs, fwd, nullptr, z_inout, 1);                             // z_inout += M^-1 r
 }
 
 int oisat_cov_residual_if(oisat_ctx* h, const double* oxyz, const double* osig, const double* ovar, int64_t m, double g,

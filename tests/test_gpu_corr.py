@@ -1,6 +1,6 @@
 """The Gaspari-Cohn correlation on the device (``corr="gaspari_cohn"``, ``oisat_set_correlation``): S as built, the dense
 analysis against a float64 host solve of the Gaspari-Cohn system, the Gaussian's bits next to it, the batched / tiled paths
-and the diagnostics.  The references are float64 NumPy / SciPy written here (the oracle has the Gaussian only)."""
+and the diagnostics.  The references are float64 NumPy / SciPy written here and in tests/readers_cases.py (the oracle has the Gaussian only)."""
 import ctypes as C
 import functools
 
@@ -9,6 +9,7 @@ import pytest
 import scipy.linalg as sla
 
 from oisatgmi import _hip, dense, synthetic as syn
+from readers_cases import chord2, corr_ref as _corr_ref, gc_ref          # the float64 restatements of the formulas in oisat.h
 
 pytestmark = pytest.mark.gpu
 NB = 128
@@ -23,27 +24,8 @@ def ctx():
     c.check(c.lib.oisat_set_correlation(c.h, 0))
 
 
-def gc_ref(z):
-    """Gaspari-Cohn (1999), eq. 4.10, in z = distance / c, float64, the formula as printed."""
-    z = np.asarray(z, dtype=np.float64)
-    near = -z ** 5 / 4 + z ** 4 / 2 + 5 * z ** 3 / 8 - 5 * z ** 2 / 3 + 1
-    with np.errstate(divide="ignore", invalid="ignore"):
-        far = z ** 5 / 12 - z ** 4 / 2 + 5 * z ** 3 / 8 + 5 * z ** 2 / 3 - 5 * z + 4 - 2 / (3 * z)
-    return np.where(z <= 1, near, np.where(z < 2, np.maximum(far, 0.0), 0.0))
-
-
-def chord2(pa, pb):
-    """|p - q|^2 from coordinate differences, pa (3, na), pb (3, nb) -> (na, nb)."""
-    out = np.zeros((pa.shape[1], pb.shape[1]))
-    for k in range(3):
-        out += (pa[k][:, None] - pb[k][None, :]) ** 2
-    return out
-
-
 def corr_ref(pa, pb, L, model=GC):
-    g = dense.decay_constant(L)
-    d2 = chord2(pa, pb)
-    return gc_ref(np.sqrt(0.6 * g * d2)) if model == GC else np.exp(-g * d2)
+    return _corr_ref(pa, pb, L, model)
 
 
 def host_analysis(p, cell, y, L, sel, model=GC):
