@@ -854,6 +854,30 @@ int oisat_covariogram(oisat_ctx* h, const double* oxyz, const double* d, const d
                       int64_t* nobs_used_out);
 int oisat_covariogram_quantum(double umax, int64_t m, double* q_prod_out, double* q_chord_out);
 
+/* ---- buddy sums of the normalised innovations: quality control ahead of the dense analyses ------
+ * oisat_buddy_sums: oxyz dev double[3][m] unit vectors, u dev double[m] normalised innovations, n_out dev int32[m], sums_out
+ * dev double[3][m] = W[m] | P[m] | Q[m]; every pointer a device pointer.  Enqueued on the handle's stream, does not
+ * synchronise, no workspace on the handle.  The correlation model is the handle's (oisat_set_correlation), any of the three.
+ * An observation whose u is NaN or +-inf takes part in nothing, and its own outputs are n = 0, W = P = Q = 0 (the
+ * covariogram's convention).  For every used a, over the used b != a in ASCENDING b:
+ *   dx = xa - xb (dy, dz likewise), d2 = dx dx + dy dy + dz dz left to right (no FMA),
+ *   c = C(d2; g) by the library's float64 correlation function (the one behind oisat_corr_eval),
+ *   if c >= cmin:  n_a += 1, W_a += c, t = c u_b, P_a += t, Q_a += t u_b.
+ * So P / W is the correlation-weighted mean of the buddies' innovations and Q / W - (P / W)^2 their weighted spread.
+ * olat_sorted (dev double[m], degrees, or NULL) as for oisat_cov_residual / oisat_covariogram: valid only if the observations
+ * are stored in ASCENDING latitude; a block of 256 rows then visits only the columns whose latitude lies within the window
+ * angle of its first and last row, 2 asin(chord / 2) of the chord at which C has fallen to cmin (oisat_corr_cut_chord's chord
+ * at -log2(cmin) bits, here for any cmin below 1), widened by 1e-9 relative in chord^2 plus 1e-15 / g, and by 1e-9 degrees.
+ * Inside the window a pair whose d2 exceeds that widened squared chord is skipped without evaluating C.  Both skip only
+ * pairs that fail c >= cmin for certain.
+ * Deterministic: a row's four accumulators live in one lane's registers, which takes the columns in ascending order; rows
+ * are not split over workgroups; a skipped pair adds nothing.  The outputs are the same bits on every run, and the same bits
+ * with and without olat_sorted.  (They do depend on the ORDER of the observations, as any floating-point sum does.)
+ * 0 <= m <= 1 << 20 (m = 0: nothing is done; m = 1: zeros), g > 0 and finite, 2^-20 <= cmin < 1, non-NULL oxyz / u / n_out /
+ * sums_out where m > 0; anything else is OISAT_EINVAL and writes nothing. */
+int oisat_buddy_sums(oisat_ctx* h, const double* oxyz, const double* u, int64_t m, double g, double cmin,
+                     const double* olat_sorted, int32_t* n_out, double* sums_out /* W[m] | P[m] | Q[m] */);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1327,3 +1327,132 @@ def estimate_corr_length(Xa, Y, Sa, So, lat, lon, scale=1.0, corr="gaussian", **
     cg = innovation_covariogram(np.ravel(lat)[cell], np.ravel(lon)[cell], (np.ravel(Y) - np.ravel(Xa))[cell],
                                 sigma=np.sqrt(var[cell]), **cg_kw)
     return {**fit_correlation(cg, corr, **fit_kw), "covariogram": cg}
+
+
+# ---- quality control of the innovations: background check and buddy check ----------------------------
+BUDDY_CMIN = float(np.exp(-2.0))                     # buddies are the observations with C >= exp(-2): within 2 L for the Gaussian
+QC_KEPT, QC_BACKGROUND, QC_BUDDY, QC_NOT_FINITE = 0, 1, 2, 3
+
+
+def buddy_sums(obs_lat, obs_lon, u, L_km, corr="gaussian", cmin=BUDDY_CMIN, ctx=None):
+    """The buddy sums of the normalised innovations ``u`` on the device (``oisat_buddy_sums``; the pair rule is written out in
+    include/oisat.h): per observation, over the other observations with a finite ``u`` whose correlation ``c`` with it (model
+    ``corr`` at length ``L_km``) is at least ``cmin``: ``n`` their number, ``W = sum c``, ``P = sum c u_b``, ``Q = sum c u_b^2``.
+    An observation whose own ``u`` is not finite gets zeros.  Sorted by latitude for the kernel's window, returned in the
+    caller's order; bitwise repeatable.  -> dict ``n`` (int32), ``W``, ``P``, ``Q`` (float64)."""
+    kind = corr_kind(corr)
+    lat = np.ravel(np.asarray(obs_lat, dtype=np.float64))
+    lon = np.ravel(np.asarray(obs_lon, dtype=np.float64))
+    uu = np.ravel(np.asarray(u, dtype=np.float64))
+    m = int(uu.size)
+    if lat.size != m or lon.size != m:
+        raise ValueError("obs_lat, obs_lon and u must have the same size")
+    c = ctx or _hip.context()
+    n, sums = np.zeros(m, dtype=np.int32), np.zeros((3, m))
+    if m == 0:
+        return {"n": n, "W": sums[0], "P": sums[1], "Q": sums[2]}
+    o = latitude_order(lat)
+    bufs = [c.upload(unit_vectors(lat[o], lon[o])), c.upload(uu[o]), c.upload(lat[o]), c.alloc(4 * m), c.alloc(24 * m)]
+    try:
+        c.check(c.lib.oisat_set_correlation(c.h, kind))
+        try:
+            c.check(c.lib.oisat_buddy_sums(c.h, bufs[0].ptr, bufs[1].ptr, m, decay_constant(L_km), float(cmin), bufs[2].ptr,
+                                           bufs[3].ptr, bufs[4].ptr))
+            ns = c.download(bufs[3].ptr, (m,), np.int32)
+            ss = c.download(bufs[4].ptr, (3, m), np.float64)
+        finally:
+            c.check(c.lib.oisat_set_correlation(c.h, CORRELATIONS["gaussian"]))
+    finally:
+        for b in bufs:
+            b.free()
+    n[o] = ns
+    sums[:, o] = ss
+    return {"n": n, "W": sums[0], "P": sums[1], "Q": sums[2]}
+
+
+def buddy_stats(W, P, Q):
+    """``(mean, var)`` of the buddies' innovations from their sums: ``mean = P / W``, ``var = max(Q / W - mean^2, 0)``; NaN where
+    ``W`` is not positive."""
+    W, P, Q = (np.asarray(a, dtype=np.float64) for a in (W, P, Q))
+    has = W > 0
+    Ws = np.where(has, W, 1.0)
+    mean = np.where(has, P / Ws, np.nan)
+    with np.errstate(invalid="ignore", over="ignore"):
+        var = np.where(has, np.maximum(Q / Ws - mean * mean, 0.0), np.nan)
+    return mean, var
+
+
+def buddy_decide(u, n, W, P, Q, k_background=5.0, k_buddy=3.0, min_buddies=3):
+    """The decision of one pass, host only.  -> ``reason``, uint8 per observation, tested in this order: 3 = ``u`` is not finite;
+    1 = ``|u| > k_background`` (background check); 2 = ``n >= min_buddies`` and ``|u - mean| > k_buddy sqrt(1 + var)`` with
+    ``mean = P / W``, ``var = max(Q / W - mean^2, 0)`` (buddy check); 0 = kept.  ``u`` has unit variance under the model and
+    ``var`` is the buddies' own weighted spread: an outlier among the buddies widens its neighbours' thresholds instead of
+    getting them rejected, and the next pass judges them without it.  Fewer than ``min_buddies`` buddies, or ``W = 0``: the
+    background check alone."""
+    u = np.ravel(np.asarray(u, dtype=np.float64))
+    n = np.ravel(np.asarray(n))
+    mean, var = buddy_stats(np.ravel(W), np.ravel(P), np.ravel(Q))
+    fin = np.isfinite(u)
+    reason = np.zeros(u.size, dtype=np.uint8)
+    with np.errstate(invalid="ignore"):
+        judged = fin & (n >= min_buddies) & np.isfinite(mean) & np.isfinite(var)
+        dev = np.abs(np.where(judged, u - np.where(judged, mean, 0.0), 0.0))
+        buddy = judged & (dev > float(k_buddy) * np.sqrt(1.0 + np.where(judged, var, 0.0)))
+        reason[buddy] = QC_BUDDY
+        reason[fin & (np.abs(u) > float(k_background))] = QC_BACKGROUND
+    reason[~fin] = QC_NOT_FINITE
+    return reason
+
+
+def buddy_check(obs_lat, obs_lon, u, L_km, corr="gaussian", cmin=BUDDY_CMIN, k_background=5.0, k_buddy=3.0, min_buddies=3,
+                max_passes=4, ctx=None):
+    """Background check plus iterated buddy check of the normalised innovations ``u``.  Each pass computes the buddy sums over
+    the observations still in use (``buddy_sums``) and decides (``buddy_decide``); the newly rejected observations get
+    ``u = NaN`` on a copy, so that a rejected observation stops vouching for others; it ends when a pass rejects nothing or after
+    ``max_passes``.  An observation whose ``u`` is not finite to begin with is rejected in the first pass (reason 3).
+    -> dict ``rejected`` (bool), ``reason`` (uint8: the reason at the pass that rejected it, 0 = kept), ``passes`` (rejections
+    per pass), ``n`` / ``mean`` / ``spread`` (buddies, their weighted mean and standard deviation at the last pass; NaN without
+    buddies) and the settings."""
+    corr_kind(corr)
+    if int(max_passes) < 1:
+        raise ValueError(f"max_passes must be at least 1, not {max_passes!r}")
+    work = np.array(np.ravel(np.asarray(u, dtype=np.float64)))
+    m = int(work.size)
+    reason = np.zeros(m, dtype=np.uint8)
+    passes = []
+    s = {"n": np.zeros(m, dtype=np.int32), "W": np.zeros(m), "P": np.zeros(m), "Q": np.zeros(m)}
+    for _ in range(int(max_passes)):
+        s = buddy_sums(obs_lat, obs_lon, work, L_km, corr=corr, cmin=cmin, ctx=ctx)
+        r = buddy_decide(work, s["n"], s["W"], s["P"], s["Q"], k_background, k_buddy, min_buddies)
+        new = (r != 0) & (reason == 0)
+        reason[new] = r[new]
+        work[new] = np.nan
+        passes.append(int(new.sum()))
+        if not new.any():
+            break
+    mean, var = buddy_stats(s["W"], s["P"], s["Q"])
+    return {"rejected": reason != 0, "reason": reason, "passes": passes, "n": s["n"], "mean": mean, "spread": np.sqrt(var),
+            "L_km": float(L_km), "corr": corr, "cmin": float(cmin), "k_background": float(k_background), "k_buddy": float(k_buddy),
+            "min_buddies": int(min_buddies), "max_passes": int(max_passes)}
+
+
+def qc_innovations(Xa, Y, Sa, So, lat, lon, L_km, scale=1.0, corr="gaussian", **kw):
+    """``buddy_check`` with the gridded convention of ``OI_dense`` / ``estimate_corr_length`` (same ``ok`` mask, same clamp of
+    ``Y`` -- on a copy: the caller's arrays are not altered): u = (Y - Xa) / sqrt(Sa scale + So), the innovation over its
+    standard deviation under the model, at the observed cells; a cell where that variance is 0 or not finite is dropped and
+    never flagged.  ``kw``: the settings of ``buddy_check``.  -> its dict (per checked observation, ``"cells"`` their flat
+    indices) plus ``"rejected_cells"``, bool (ny, nx)."""
+    corr_kind(corr)                                           # (ValueError before anything is touched)
+    Xa, Sa, So = np.asarray(Xa, dtype=np.float64), np.asarray(Sa, dtype=np.float64), np.asarray(So, dtype=np.float64)
+    Y = np.array(Y, dtype=np.float64)
+    Y[Y < 0] = 0.0
+    with np.errstate(invalid="ignore", over="ignore"):
+        var = np.ravel(Sa) * float(scale) + np.ravel(So)
+    ok = (np.isfinite(np.ravel(Y)) & np.isfinite(np.ravel(So)) & np.isfinite(np.ravel(Xa)) & np.isfinite(np.ravel(Sa))
+          & np.isfinite(var) & (var > 0))
+    cell = np.flatnonzero(ok)
+    u = (np.ravel(Y) - np.ravel(Xa))[cell] / np.sqrt(var[cell])
+    out = buddy_check(np.ravel(lat)[cell], np.ravel(lon)[cell], u, L_km, corr=corr, **kw)
+    mask = np.zeros(Xa.size, dtype=bool)
+    mask[cell[out["rejected"]]] = True
+    return {**out, "cells": cell, "rejected_cells": mask.reshape(np.shape(Xa))}

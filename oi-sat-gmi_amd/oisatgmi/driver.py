@@ -98,6 +98,11 @@ class oisatgmi(object):
     #               through the factor the analysis leaves behind, with its own standard errors in oi_info["err_se"] /
     #               ["ak_obs_se"] (dense.DenseAnalysis.posterior_error_mc); tiled: ValueError -- the
     #               tiles' exact error is affordable
+    #   QC          attribute `oi_qc`          | env OISAT_OI_QC          off (default) | buddy | buddy:<k_buddy>  (dense, tiled;
+    #               diag ignores it): background check and buddy check of the innovations ahead of the analysis
+    #               (dense.qc_innovations) at the analysis' L -- under `auto` at the length fitted to all
+    #               observations (oi_info["qc"]["corr_fit_before"]), and the analysis' length is then refitted to the kept ones;
+    #               a rejected cell is analysed as unobserved; oi_info["qc"], oi_info["qc_rejected"]
     def _oi_setting(self, attr, env, default, cast=str):
         v = getattr(self, attr, None)
         if v is None:
@@ -132,6 +137,25 @@ class oisatgmi(object):
         if K < 128 or K % 128:
             raise ValueError(f"OISAT_OI_ERROR / oi_want_error: the number of probes must be a positive multiple of 128, not {K}")
         return "mc", K
+
+    @staticmethod
+    def _qc_setting(v):
+        """``OISAT_OI_QC`` / ``oi_qc`` -> ``None`` for ``off``, ``{"k_buddy": k}`` for ``buddy`` (k = 3) / ``buddy:<k_buddy>`` (a
+        positive finite float); anything else is a ``ValueError``."""
+        v = str(v).strip().lower()
+        if v == "off":
+            return None
+        if v == "buddy":
+            return {"k_buddy": 3.0}
+        try:
+            if not v.startswith("buddy:"):
+                raise ValueError
+            k = float(v[6:])
+            if not (0.0 < k < float("inf")):
+                raise ValueError
+        except ValueError:
+            raise ValueError(f"OISAT_OI_QC / oi_qc: expected off, buddy or buddy:<k_buddy> (a positive number), not {v!r}") from None
+        return {"k_buddy": k}
 
     def _oi_grid(self):
         lat, lon = getattr(self, "grid_lat", None), getattr(self, "grid_lon", None)
@@ -171,6 +195,7 @@ class oisatgmi(object):
         want_error, nprobe = self._oi_setting("oi_want_error", "OISAT_OI_ERROR", "1", self._error_setting)
         if want_error == "mc" and mode == "tiled":
             raise ValueError("OISAT_OI_ERROR / oi_want_error = mc belongs to the dense mode; a tiled analysis has the exact error (1)")
+        qc = self._oi_setting("oi_qc", "OISAT_OI_QC", "off", self._qc_setting)
         lat, lon = self._oi_grid()
         xa, y = np.asarray(xa), np.asarray(y)
         if lat.shape != xa.shape[:2] or lon.shape != xa.shape[:2]:
@@ -187,7 +212,7 @@ class oisatgmi(object):
         for tail in np.ndindex(*xa.shape[2:]):
             sl = (slice(None), slice(None)) + tail
             res, info = self._oi_spatial(mode, xa[sl], y[sl], np.asarray(Sa)[sl], np.asarray(So)[sl], lat, lon, L, tile,
-                                         unobserved, reg_index, want_error, corr=corr, nprobe=nprobe)
+                                         unobserved, reg_index, want_error, corr=corr, nprobe=nprobe, qc=qc)
             for o, r in zip(outs, res):
                 o[sl] = r
             infos.append(info)
@@ -195,8 +220,11 @@ class oisatgmi(object):
         self.oi_info = dict(infos[0]) if len(infos) == 1 else {**infos[0], "slices": infos}
 
     @staticmethod
-    def _oi_spatial(mode, xa, y, Sa, So, lat, lon, L, tile, unobserved, reg_index, want_error, corr="gaussian", nprobe=256):
-        """One (ny, nx) Gaussian-B analysis -> ((Xb, AK, increment, error), info) in the reference's attribute order."""
+    def _oi_spatial(mode, xa, y, Sa, So, lat, lon, L, tile, unobserved, reg_index, want_error, corr="gaussian", nprobe=256,
+                    qc=None):
+        """One (ny, nx) Gaussian-B analysis -> ((Xb, AK, increment, error), info) in the reference's attribute order.  ``qc``
+        (``_qc_setting``): not None = the innovations are checked first and the rejected cells analysed as unobserved, on a
+        copy of ``y``."""
         from . import dense
         from . import optimal_interpolation as oi_mod
         index, scale, curve, found = oi_mod.regularization_pick(Sa, So, reg_index)
@@ -210,6 +238,27 @@ class oisatgmi(object):
             else:                                                # (the knee_found convention: say so once, use the default)
                 L = 300.0
                 print("No correlation length could be fitted to the innovations; using 300 km")
+        qc_info = qc_mask = None
+        if qc is not None:
+            res = dense.qc_innovations(xa, y, Sa, So, lat, lon, L, scale=scale, corr=corr, **qc)
+            qc_mask = res["rejected_cells"]
+            qc_info = {"method": "buddy", "nrejected": int(res["rejected"].sum()),
+                       "n_background": int((res["reason"] == dense.QC_BACKGROUND).sum()),
+                       "n_buddy": int((res["reason"] == dense.QC_BUDDY).sum()), "passes": res["passes"],
+                       "k_background": res["k_background"], "k_buddy": res["k_buddy"], "min_buddies": res["min_buddies"],
+                       "cmin": res["cmin"], "L_km": res["L_km"]}
+            print(f"Quality control rejected {qc_info['nrejected']} of {res['rejected'].size} observations")
+            y = np.array(y, dtype=np.float64)                    # a copy: the rejected cells are unobserved from here on
+            y[qc_mask] = np.nan
+            if corr_fit is not None:                             # "auto": the analysis' length is the one the kept observations support
+                qc_info["corr_fit_before"] = corr_fit
+                corr_fit = dense.estimate_corr_length(xa, y, Sa, So, lat, lon, scale=scale, corr=corr)
+                corr_fit.pop("covariogram", None)
+                if corr_fit["found"]:
+                    L = float(corr_fit["L_km"])
+                else:
+                    L = 300.0
+                    print("No correlation length could be fitted to the kept innovations; using 300 km")
         if mode == "dense":
             xb, inc, info = dense.OI_dense(xa, y, Sa, So, lat, lon, L, scale=scale, want_error=want_error, corr=corr,
                                            nprobe=nprobe or 256)
@@ -241,6 +290,8 @@ class oisatgmi(object):
             out_info.update(error_method="mc", nprobe=info["nprobe"], err_se=info["err_se"], ak_obs_se=info["ak_obs_se"])
         if corr_fit is not None:
             out_info["corr_fit"] = corr_fit
+        if qc_info is not None:
+            out_info["qc"], out_info["qc_rejected"] = qc_info, qc_mask
         return (xb, ak, inc, err), out_info
 
     def scaling_factor(self):
