@@ -589,12 +589,29 @@ int oisat_potrs(oisat_ctx* h, const float* L, int64_t m, int64_t ld, double* z_i
 int oisat_cov_residual(oisat_ctx* h, const double* oxyz, const double* osig, const double* ovar, int64_t m,
                        double g, const double* d, const double* z, double* r_out, const double* olat_sorted);
 
+/* out = r_prev - (C.*sig sig^T + diag(var)) dz: the residual behind a correction z <- z + dz as an update of the one before it.
+ * The off-diagonal sums are evaluated in packed fp32 (coordinates, exponential, partial sums of at most 96 terms joined in
+ * double), the diagonal term and the subtraction in double: out is within OISAT_RESID_UPDATE_C |r_prev| (2-norm) of the float64
+ * value wherever |S dz| is of the order of |r_prev|, which is what a correction of the refinement gives.  Gaussian only, and only
+ * where the residual takes compact blocks of rows (the covariance's 2^-64 chord at most 0.5 on the unit sphere: L <= 340 km on
+ * the Earth); OISAT_EINVAL otherwise.  olat_sorted is required; the blocks come from oisat_set_obs_blocks as for
+ * oisat_cov_residual (one-shot; without a list: 64 consecutive latitudes).  out must not alias r_prev or dz.  Same inputs,
+ * same bits. */
+#define OISAT_RESID_UPDATE_C (1.0 / 1024.0)
+int oisat_cov_residual_update(oisat_ctx* h, const double* oxyz, const double* osig, const double* ovar, int64_t m,
+                              double g, const double* r_prev, const double* dz, double* out, const double* olat_sorted);
+
 /* Solve (H B H^T + R) z = d with the fp32 factor as a preconditioner: z = M^-1 d, then at most `refine` rounds of
  * { r = d - S z in float64; stop if |r| <= tol |d|; z += M^-1 r }.  The stopping test runs on the device (the launches of
  * the rounds after convergence return at once; nothing waits for the host).  tol: oisat_set_refine_tol, default 1e-6
  * (the increment is K r away from the exact one and |K| <= 1: fields within 1e-6 |d|); 0 = always run every round.
  * resid_host (may be NULL): relative residual norms before each round and after the last, refine+1 entries; rounds that
- * were not run repeat the last computed value.  Synchronises only when resid_host is given. */
+ * were not run repeat the last computed value.  Synchronises only when resid_host is given.
+ * A residual behind a correction is first formed as oisat_cov_residual_update forms it (Gaussian, compact blocks, tol > 0):
+ * t with | |t| - |r| | <= c |r_prev|, c = OISAT_RESID_UPDATE_C.  If |t| + c |r_prev| <= tol |d| -- which proves |r| <= tol |d| --
+ * the solve stops there and the norm reported for that round is |t|, within c |previous residual| of the float64 value;
+ * otherwise the float64 residual is evaluated and decides, as for every other model and form.  z never depends on t.
+ * OISAT_RESID_UPDATE=0 in the environment (read at every call) switches the update form off. */
 int oisat_gain_solve(oisat_ctx* h, const float* L, const double* oxyz, const double* osig, const double* ovar,
                      int64_t m, int64_t ld, double g, const double* d, int refine, double* z_out,
                      double* resid_host, const double* olat_sorted /* as for oisat_cov_residual; may be NULL */);

@@ -1536,12 +1536,16 @@ __global__ __launch_bounds__(256) void solve_prep_kernel(const double* __restric
 // |r_k|^2 (and |d|^2 at k = 0) in one block, fixed order; sets the convergence flag when |r_k| <= tol |d|
 // final: this is the check behind the LAST allowed correction -- a solve that is still above its tolerance here is counted in
 // the handle's status words (info[4], info[5]); tol2 = 0 ("run every round") never counts
+// keep (or nullptr): takes a copy of r -- the forward sweep that follows consumes r, and the update form of the next round's
+// residual (cov_residual_update) starts from the last fully evaluated one
 __global__ __launch_bounds__(1024) void resid_check_kernel(const double* __restrict__ r, const double* __restrict__ d, int64_t m, int k,
-                                                            double tol2, SolveState* __restrict__ st, int final, int* __restrict__ info) {
+                                                            double tol2, SolveState* __restrict__ st, int final, int* __restrict__ info,
+                                                            double* __restrict__ keep) {
     __shared__ double sr[1024], sd[1024];
     if (st->conv != 0) return;
     double a = 0.0, b = 0.0;
     for (int64_t i = threadIdx.x; i < m; i += 1024) {
+        if (keep != nullptr) keep[i] = r[i];
         a += r[i] * r[i];
         if (k == 0) b += d[i] * d[i];
     }
@@ -1561,6 +1565,29 @@ __global__ __launch_bounds__(1024) void resid_check_kernel(const double* __restr
         st->computed = k + 1;
         if (sr[0] <= tol2 * st->dd) st->conv = 1;
         else if (final && tol2 > 0.0) atomicAdd(&info[kInfoUnconverged], 1);
+    }
+}
+
+// The check behind the UPDATE form of round k's residual (t = r_{k-1} - S dz, S dz in fp32: cov_residual_update): |t|^2 in the
+// order of resid_check_kernel.  t is within c |r_{k-1}| of the float64 residual, so |t| + c |r_{k-1}| <= tol |d| proves that
+// the float64 test would pass: then, and only then, this round's norm is |t|^2 and the solve is converged -- the full residual,
+// its check and the later sweeps return at once.  Otherwise nothing is written and the float64 residual decides as before.
+__global__ __launch_bounds__(1024) void resid_update_check_kernel(const double* __restrict__ t, int64_t m, int k, double tol, double c,
+                                                                   SolveState* __restrict__ st) {
+    __shared__ double sr[1024];
+    if (st->conv != 0) return;
+    double a = 0.0;
+    for (int64_t i = threadIdx.x; i < m; i += 1024) a += t[i] * t[i];
+    sr[threadIdx.x] = a;
+    __syncthreads();
+    for (int q = 512; q > 0; q >>= 1) {
+        if ((int)threadIdx.x < q) sr[threadIdx.x] += sr[threadIdx.x + q];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0 && tol > 0.0 && k >= 1 && sqrt(sr[0]) + c * sqrt(st->norm[k - 1]) <= tol * sqrt(st->dd)) {
+        st->norm[k] = sr[0];
+        st->computed = k + 1;
+        st->conv = 1;
     }
 }
 
@@ -3027,6 +3054,19 @@ int oisat_cov_residual_if(oisat_ctx* h, const double* oxyz, const double* osig, 
                           const double* d, const double* z, double* r_out, const double* olat_sorted, const int* converged_dev,
                           const int* perm);
 const int* oisat_take_obs_perm(oisat_ctx* h, int64_t m);
+int oisat_cov_residual_update_if(oisat_ctx* h, const double* oxyz, const double* osig, const double* ovar, int64_t m, double g,
+                                 const double* r_prev, const double* dz, double* out, const double* olat_sorted, const int* converged_dev,
+                                 const int* perm);
+bool oisat_resid_update_applies(const oisat_ctx* h, double g, const double* olat_sorted, const int* perm);
+double oisat_resid_update_c();
+
+// OISAT_RESID_UPDATE=0: oisat_gain_solve forms every residual in float64, the launches and bits of the code before the update
+// form.  Read at every call; anything but 0 or 1 is an error (-1).
+static int resid_update_mode() {
+    const char* e = getenv("OISAT_RESID_UPDATE");
+    if (!e || !*e) return 1;
+    return ((e[0] == '0' || e[0] == '1') && e[1] == '\0') ? e[0] - '0' : -1;
+}
 
 // z = S^-1 d through the fp32 factor as a preconditioner:  z <- M^-1 d;  repeat { r = d - S z (float64, S regenerated from
 // coordinates);  stop if |r| <= tol |d|;  z <- z + M^-1 r }  at most `refine` times.  tol = 1e-6 (oisat_set_refine_tol; env OISAT_REFINE_TOL at init): the
@@ -3046,6 +3086,8 @@ extern "C" int oisat_gain_solve(oisat_ctx* h, const float* L, const double* oxyz
     h->factor.fwd_d = nullptr;
     ARG_CHECK(L && oxyz && osig && ovar && d && z_out && m > 0 && refine >= 0 && refine <= 8);
     ARG_CHECK(h->factor.S == L && h->factor.m == m && h->factor.ld == ld);
+    const int upd_mode = resid_update_mode();
+    ARG_CHECK(upd_mode >= 0 && "OISAT_RESID_UPDATE is 0 or 1");
     const double tol = h->refine_tol;
     const int64_t mp = h->factor.mp;
     double* w = (double*)oisat_ws(h, 5, sizeof(double) * (2 + 8) * mp);
@@ -3063,11 +3105,25 @@ extern "C" int oisat_gain_solve(oisat_ctx* h, const float* L, const double* oxyz
     int* info_dev = nullptr;
     if (int rs = status_ws(h, &info_dev, nullptr)) return rs;
     // (refine = 0 asks for the plain solve: no residual is formed -- unless the caller wants it reported -- and nothing is flagged)
+    // Behind a correction (it >= 1) the residual is first formed as an update of the last fully evaluated one, r_keep - S dz with
+    // S dz in packed fp32 (dz: what the backward sweep left in the padded right-hand side).  If that already proves the
+    // tolerance met (resid_update_check_kernel) the solve is converged and everything below returns at once; if not, nothing
+    // has changed and the float64 residual decides.  Gaussian on compact blocks with a tolerance only; vectors 2 and 3 of the
+    // slot (free here: the sliced residual's partial sums belong to the latitude-row form, oisat_potrs is another call).
+    const bool upd =upd_mode == 1 && refine > 0 && tol > 0.0 && oisat_resid_update_applies(h, g, olat_sorted, perm);
+    double* r_keep = upd ? w + 2 * mp : nullptr;
+    double* r_upd = w + 3 * mp;
     for (int it = 0; it <= refine && (refine > 0 || resid_host); ++it) {
+        if (upd && it >= 1) {
+            rc = oisat_cov_residual_update_if(h, oxyz, osig, ovar, m, g, r_keep, rhs, r_upd, olat_sorted, &st->conv, perm);
+            if (rc) return rc;
+            OISAT_LAUNCH(h, "resid_update_check", resid_update_check_kernel, dim3(1), dim3(1024), 0, (const double*)r_upd, m, it, tol,
+                         oisat_resid_update_c(), st);
+        }
         rc = oisat_cov_residual_if(h, oxyz, osig, ovar, m, g, d, z_out, rhs, olat_sorted, &st->conv, perm);
         if (rc) return rc;
         OISAT_LAUNCH(h, "resid_check", resid_check_kernel, dim3(1), dim3(1024), 0, (const double*)rhs, d, m, it, tol * tol, st,
-                     it == refine && refine > 0 ? 1 : 0, info_dev);
+                     it == refine && refine > 0 ? 1 : 0, info_dev, it < refine ? r_keep : (double*)nullptr);
         if (it == refine) break;
         rc = trsv_solve(h, h->factor, rhs, fwd, st, z_out, 1);
         if (rc) return rc;

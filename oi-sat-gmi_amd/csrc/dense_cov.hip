@@ -173,6 +173,18 @@ __global__ __launch_bounds__(256) void cov_residual_blocks_kernel(const double* 
     resid_compact_block<KIND, false>(oxyz, osig, ovar, m, g, d, z, r, olat, win_deg, perm, cut_chord, far_chord, (int64_t)blockIdx.x, W);
 }
 
+// ---- out = r_prev - S dz on the same compact blocks, S dz in packed fp32 (dense_solve_dev.inc: resid_update_block) ---------
+__global__ __launch_bounds__(256) void cov_residual_update_kernel(const double* __restrict__ oxyz, const double* __restrict__ osig,
+                                                                   const double* __restrict__ ovar, int64_t m, double g,
+                                                                   const double* __restrict__ r_prev, const double* __restrict__ dz,
+                                                                   double* __restrict__ out, const double* __restrict__ olat, double win_deg,
+                                                                   const int* __restrict__ converged, const int* __restrict__ perm,
+                                                                   double cut_chord) {
+    SOLVE_LDS(W);
+    if (converged != nullptr && *converged != 0) return;       // the refinement has met its tolerance: nothing left to evaluate
+    resid_update_block(oxyz, osig, ovar, m, g, r_prev, dz, out, olat, win_deg, perm, cut_chord, (int64_t)blockIdx.x, W);
+}
+
 // ---- inc_i = sig_i * sum_a C(i,a) w_a ; xa = xb + inc (dense_solve_dev.inc: increment_patch); blockIdx.x = patch / run ----
 template <int KIND, typename T, int CELLS, bool BATCH>
 __global__ __launch_bounds__(256) void apply_increment_kernel(const double* __restrict__ gxyz, const double* __restrict__ gsig,
@@ -558,6 +570,31 @@ extern "C" int oisat_cov_residual(oisat_ctx* h, const double* oxyz, const double
                                   const double* d, const double* z, double* r_out, const double* olat_sorted) {
     ARG_CHECK(h != nullptr);
     return oisat_cov_residual_if(h, oxyz, osig, ovar, m, g, d, z, r_out, olat_sorted, nullptr, oisat_take_obs_perm(h, m));
+}
+
+// The update form of the residual behind a correction (resid_update_block): where it applies -- the Gaussian on compact blocks
+bool oisat_resid_update_applies(const oisat_ctx* h, double g, const double* olat_sorted, const int* perm) {
+    return h->corr == OISAT_CORR_GAUSSIAN && perm != nullptr && olat_sorted != nullptr && residual_blocks_pay(h->corr, g);
+}
+
+double oisat_resid_update_c() { return kResidUpdateC; }
+
+int oisat_cov_residual_update_if(oisat_ctx* h, const double* oxyz, const double* osig, const double* ovar, int64_t m, double g,
+                                 const double* r_prev, const double* dz, double* out, const double* olat_sorted, const int* converged_dev,
+                                 const int* perm) {
+    ARG_CHECK(h && oxyz && osig && ovar && r_prev && dz && out && olat_sorted && m > 0 && g >= 0.0);
+    ARG_CHECK(out != r_prev && out != dz);
+    ARG_CHECK(h->corr == OISAT_CORR_GAUSSIAN && residual_blocks_pay(h->corr, g));
+    ARG_CHECK(cdiv(m, 64) < (int64_t)INT32_MAX);
+    OISAT_LAUNCH(h, "cov_residual_update", cov_residual_update_kernel, dim3((unsigned)cdiv(m, 64)), dim3(256), 0, oxyz, osig, ovar, m, g, r_prev,
+                 dz, out, olat_sorted, lat_window_deg(h->corr, g), converged_dev, perm, cut_chord_of(h->corr, g));
+    return OISAT_OK;
+}
+
+extern "C" int oisat_cov_residual_update(oisat_ctx* h, const double* oxyz, const double* osig, const double* ovar, int64_t m, double g,
+                                         const double* r_prev, const double* dz, double* out, const double* olat_sorted) {
+    ARG_CHECK(h != nullptr);
+    return oisat_cov_residual_update_if(h, oxyz, osig, ovar, m, g, r_prev, dz, out, olat_sorted, nullptr, oisat_take_obs_perm(h, m));
 }
 
 template <typename T, int CELLS, bool BATCH>

@@ -556,6 +556,107 @@ __device__ __forceinline__ void resid_compact_block(const double* __restrict__ o
     }
 }
 
+// ---- the residual behind a correction as an UPDATE of the last one: out = r_prev - S dz, S dz in packed fp32 ---------------
+// Behind a correction z <- z + dz the float64 residual is r_prev - S dz, and |S dz| ~ |r_prev|: a relative error e in S dz
+// moves the new residual by e |r_prev|, a few 1e-5 of a vector that is itself 1e-5 |d| -- far below what the refinement's
+// stopping test can see.  So every pair is evaluated the way the far tier above evaluates its own: fp32 coordinates,
+// v_pk_* / v_exp_f32, fp32 partial sums per flush joined into the phase's double sum.  Gaussian only.  Geometry, latitude span,
+// bounding sphere, the 2^-kCutBits cull and the candidate order are resid_compact_block's.  The survivors are staged as four
+// float arrays x[], y[], z[], w[] (w = sig dz) in the bytes of bxy | bzw: kUpdStage = 1536 entries, twice the float64 lists'.
+// A pass adds at most 256, hence the flush rule: evaluate once another pass might not fit (fill + 256 > kUpdStage), or behind
+// the last pass -- a rule of the counts alone.  The list is padded with weight-0 entries to a multiple of 16; column phase ph
+// takes the quads ph, ph + 4, ..: one 16-byte broadcast read per array, entries (0, 1) and (2, 3) of the quad in the two lanes
+// of two partial sums, joined in that order.  The diagonal term and the subtraction from r_prev stay double.  Deterministic.
+constexpr int kUpdStage = (int)(2 * sizeof(double2) * kStage / (4 * sizeof(float)));
+// the reported residual may be this form: it is within kResidUpdateC |r_prev| of the float64 one (8x the largest error measured
+// on the protocol's months and the tests' geometries, rounded up to a power of two: profiles/EXPERIMENTS.md, "The verification
+// residual as an update"); the stopping test charges that bound (resid_update_check_kernel, dense_chol.hip)
+constexpr double kResidUpdateC = OISAT_RESID_UPDATE_C;         // (include/oisat.h documents it to callers)
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ void resid_update_block(const double* __restrict__ oxyz, const double* __restrict__ osig,
+                                                   const double* __restrict__ ovar, int64_t m, double g,
+                                                   const double* __restrict__ r_prev, const double* __restrict__ dzv,
+                                                   double* __restrict__ out, const double* __restrict__ olat, double win_deg,
+                                                   const int* __restrict__ perm, double cut_chord, int64_t blk, const SolveLds& W) {
+    static_assert(kUpdStage % 16 == 0 && kUpdStage >= 512, "the padded list must fit");
+    float* const lx = (float*)W.bxy;                            // bxy and bzw are adjacent (solve_lds_carve)
+    float* const ly = lx + kUpdStage;
+    float* const lz = ly + kUpdStage;
+    float* const lw = lz + kUpdStage;
+    double (*part)[64] = (double (*)[64])W.part;
+    const int t = threadIdx.x;
+    const int lr = t & 63, ph = t >> 6;
+    const int64_t pos = blk * 64 + lr;
+    const bool live = pos < m;
+    const int64_t row = live ? (perm ? (int64_t)perm[pos] : pos) : 0;
+    const double ax = live ? oxyz[row] : 0.0, ay = live ? oxyz[m + row] : 0.0, az = live ? oxyz[2 * m + row] : 0.0;
+    if (ph == 0) {                                              // latitude span of the block's rows (wave 0 holds each row once)
+        double lo = live ? olat[row] : 1e9, hi = live ? olat[row] : -1e9;
+#pragma unroll
+        for (int o = 32; o >= 1; o >>= 1) { lo = fmin(lo, __shfl_xor(lo, o, kWave)); hi = fmax(hi, __shfl_xor(hi, o, kWave)); }
+        if (lr == 0) { W.s_lo[0] = lo; W.s_hi[0] = hi; }
+    }
+    __syncthreads();
+    const int64_t j0 = lower_bound_lat(olat, m, W.s_lo[0] - win_deg);
+    const int64_t j1 = lower_bound_lat(olat, m, W.s_hi[0] + win_deg + 1e-9);
+    const double sx1[1] = {ax}, sy1[1] = {ay}, sz1[1] = {az};
+    const bool lv1[1] = {live && ph == 0};
+    const BlockSphere bs = block_sphere<1>(sx1, sy1, sz1, lv1, cut_chord, (double)INFINITY, W.red);
+    const f32x2 fx = {(float)ax, (float)ax}, fy = {(float)ay, (float)ay}, fz = {(float)az, (float)az};
+    const float g2 = (float)(g * (double)kLog2e);
+    double acc = 0.0;
+    int fill = 0;
+    for (int64_t c0 = j0; c0 < j1; c0 += 256) {
+        {                                                       // one pass of 256 candidates: the survivors, in candidate order
+            const int lane = t & 63, w = t >> 6;
+            const int64_t c = c0 + t;
+            double x = 0.0, y = 0.0, zz = 0.0;
+            bool near = false;
+            if (c < j1) {
+                x = oxyz[c]; y = oxyz[m + c]; zz = oxyz[2 * m + c];
+                const double dx = x - bs.cx, dy = y - bs.cy, dz = zz - bs.cz;
+                near = dx * dx + dy * dy + dz * dz <= bs.r2cull;
+            }
+            const unsigned long long mask = __ballot(near);
+            if (lane == 0) W.wcnt[w] = __popcll(mask);
+            __syncthreads();
+            const int c0w = W.wcnt[0], c1w = W.wcnt[1], c2w = W.wcnt[2], c3w = W.wcnt[3];
+            if (near) {
+                const int p = fill + (w > 0 ? c0w : 0) + (w > 1 ? c1w : 0) + (w > 2 ? c2w : 0) + __popcll(mask & ((1ull << lane) - 1ull));
+                lx[p] = (float)x; ly[p] = (float)y; lz[p] = (float)zz;
+                lw[p] = (float)(osig[c] * dzv[c]);
+            }
+            fill += c0w + c1w + c2w + c3w;                      // <= kUpdStage: a pass starts at fill <= kUpdStage - 256
+            if (t < 16 && fill + t < ((fill + 15) & ~15)) {     // the padding behind the list (the next pass writes over it)
+                lx[fill + t] = 0.0f; ly[fill + t] = 0.0f; lz[fill + t] = 0.0f; lw[fill + t] = 0.0f;
+            }
+            __syncthreads();
+        }
+        if (fill + 256 > kUpdStage || c0 + 256 >= j1) {        // block-uniform
+            f32x2 s0 = {0.0f, 0.0f}, s1 = {0.0f, 0.0f};
+#pragma unroll 2
+            for (int j = 4 * ph; j < fill; j += 16) {           // this phase's quads; wave-uniform addresses: broadcast reads
+                const f32x4 ox = *reinterpret_cast<const f32x4*>(lx + j), oy = *reinterpret_cast<const f32x4*>(ly + j);
+                const f32x4 oz = *reinterpret_cast<const f32x4*>(lz + j), ow = *reinterpret_cast<const f32x4*>(lw + j);
+                s0 = far_pairs(fx - ox.xy, fy - oy.xy, fz - oz.xy, g2, ow.xy, s0);
+                s1 = far_pairs(fx - ox.zw, fy - oy.zw, fz - oz.zw, g2, ow.zw, s1);
+            }
+            acc += (double)s0.x;
+            acc += (double)s0.y;
+            acc += (double)s1.x;
+            acc += (double)s1.y;
+            fill = 0;
+            __syncthreads();
+        }
+    }
+    part[ph][lr] = acc;
+    __syncthreads();
+    if (ph == 0 && live) {
+        const double s = ((part[0][lr] + part[1][lr]) + part[2][lr]) + part[3][lr];
+        out[row] = r_prev[row] - (osig[row] * s + ovar[row] * dzv[row]);
+    }
+}
+
 // ---- inc_i = sig_i * sum_a C(i,a) w_a, w = osig.*z ; xa = xb + inc --------------------------------------------
 // Thread = CELLS grid cells, block = 256 threads; observations stream through LDS in chunks and
 // are read as wave-uniform (broadcast) 16-byte words.  |p-q|^2 is formed in double: with float

@@ -124,6 +124,7 @@ SIGNATURES = {
     "oisat_trsv_plan": (C.c_int, [_i64, C.c_int, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "oisat_potrs": (C.c_int, [_c_ctx, _ptr, _i64, _i64, _ptr]),
     "oisat_cov_residual": (C.c_int, [_c_ctx, _ptr, _ptr, _ptr, _i64, C.c_double, _ptr, _ptr, _ptr, _ptr]),
+    "oisat_cov_residual_update": (C.c_int, [_c_ctx, _ptr, _ptr, _ptr, _i64, C.c_double, _ptr, _ptr, _ptr, _ptr]),
     "oisat_gain_solve": (C.c_int, [_c_ctx, _ptr, _ptr, _ptr, _ptr, _i64, _i64, C.c_double, _ptr, C.c_int, _ptr,
                                    C.POINTER(C.c_double), _ptr]),
     "oisat_trsm_rows": (C.c_int, [_c_ctx, _ptr, _i64, _i64, _ptr, _i64, _i64]),

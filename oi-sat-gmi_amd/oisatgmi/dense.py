@@ -38,6 +38,9 @@ SCHEDULE_ENV_DAG, SCHEDULE_ENV_DAG_FWD = 1, 2      # oisat_potrf_env_fwd's sched
 # relative float64 residual |d - S z| / |d| at which the gain solve stops refining (oisat_gain_solve): the increment is K r
 # away from the exact one and |K| <= 1, so the fields are then within 1e-6 |d| -- a tenth of the 1e-5 bar
 REFINE_TOL = float(os.environ.get("OISAT_REFINE_TOL", "1e-6"))
+# OISAT_RESID_UPDATE_C (include/oisat.h): a residual reported behind a correction may be the update form r_prev - S dz with
+# S dz in fp32, within this fraction of |r_prev| of the float64 value
+RESID_UPDATE_C = 2.0 ** -10
 PROBE_PANEL = 128             # probes per pass of the randomized error estimate (one row panel of oisat_trsm_rows_bwd)
 
 
