@@ -414,14 +414,14 @@ int oisat_potrf(oisat_ctx* h, float* S, int64_t m, int64_t ld, int* info_host);
  * oisat_factor_envelope (host only): the same table for the fp32 FACTOR, which oisat_gain_solve uses as a
  * preconditioner only (it refines against the float64 residual of the full S, cut off at 2^-52 as before).  Where the
  * factorization is bound by tile work (more than ~1 500 K-loop steps per block row inside the narrow table) the
- * table is cut at the factor's own, larger correlation (kFactorCutBits, csrc/dense_chol.hip); for every smaller
+ * table is cut at the factor's own, larger correlation (kFactorCutBits, csrc/dense_tables.hip); for every smaller
  * system, whose factorization is its chain, it is oisat_envelope's table word for word.  first[] is nowhere smaller
  * than oisat_envelope's.  This is the table DenseAnalysis.run() builds, factors and sweeps with.
  * OISAT_FACTOR_CUT_BITS=<n> in the environment (read at every call; 1 <= n <= 52, anything else is OISAT_EINVAL) forces
  * the cut-off 2^-n for every size; 52 reproduces oisat_envelope's table exactly. */
 int oisat_envelope(const double* lat_sorted, int64_t m, double g, int32_t* env_out);
 int oisat_factor_envelope(const double* lat_sorted, int64_t m, double g, int32_t* env_out);
-/* The far stretch of the factor's K-loops (csrc/dense_chol.hip: kFactorFarBits).
+/* The far stretch of the factor's K-loops (csrc/dense_tables.hip: kFactorFarBits).
  * oisat_factor_far (host only): far_out[i], first[i] <= far_out[i] <= i, = the first block column of block row i that is NOT
  * far: every correlation between an observation of block row i and one of a block column k < far_out[i] is below the far
  * cut-off.  The enveloped task graph runs the K-blocks first[i] <= k < far_out[i] of the row's tiles with both operands
@@ -436,7 +436,7 @@ int oisat_factor_envelope(const double* lat_sorted, int64_t m, double g, int32_t
  * oisat_potrf_env_fwd on this handle, which consumes it whatever its outcome and checks it against its own first.  Without
  * it, and in every other factorization (oisat_potrf, the batched ones), there is no far stretch. */
 int oisat_factor_far(const double* lat_sorted, int64_t m, double g, const int32_t* first, int32_t* far_out);
-/* The middle stretch of the factor's K-loops (csrc/dense_chol.hip: kFactorMidBits).
+/* The middle stretch of the factor's K-loops (csrc/dense_tables.hip: kFactorMidBits).
  * oisat_factor_mid (host only): mid_out[i], far[i] <= mid_out[i] <= i, = the first block column of block row i that is NOT
  * middle: every correlation between an observation of block row i and one of a block column k < mid_out[i] is below the
  * middle cut-off.  The enveloped task graph runs the K-blocks far[i] <= k < mid_out[i] of the row's tiles as split bf16
@@ -594,7 +594,8 @@ int oisat_cov_residual(oisat_ctx* h, const double* oxyz, const double* osig, con
  * double), the diagonal term and the subtraction in double: out is within OISAT_RESID_UPDATE_C |r_prev| (2-norm) of the float64
  * value wherever |S dz| is of the order of |r_prev|, which is what a correction of the refinement gives.  Gaussian only, and only
  * where the residual takes compact blocks of rows (the covariance's 2^-64 chord at most 0.5 on the unit sphere: L <= 340 km on
- * the Earth); OISAT_EINVAL otherwise.  olat_sorted is required; the blocks come from oisat_set_obs_blocks as for
+ * the Earth -- 2^-64 is the chord that rule was measured with and keeps, although the sums themselves are cut at 2^-52);
+ * OISAT_EINVAL otherwise.  olat_sorted is required; the blocks come from oisat_set_obs_blocks as for
  * oisat_cov_residual (one-shot; without a list: 64 consecutive latitudes).  out must not alias r_prev or dz.  Same inputs,
  * same bits. */
 #define OISAT_RESID_UPDATE_C (1.0 / 1024.0)

@@ -12,6 +12,7 @@
 // olat_sorted.  No atomics, no workspace.  Built with the exact flags (-ffp-contract=off): d2 = dx dx + dy dy + dz dz, left to
 // right, and c by corr_f64<KIND>, the function behind oisat_corr_eval.
 #include "oisat_common.h"
+#include "dense_switches.h"                                     // for dense_solve_dev.inc, which sits inside the namespace below
 
 namespace {
 

@@ -27,17 +27,15 @@
 // The 128x128 diagonal blocks are factored and inverted by one workgroup in LDS; the panel below
 // a diagonal block is then a GEMM with the inverse (TRSM as GEMM, the MAGMA trick), so it also
 // runs on MFMA.  The inverses are kept: the triangular solves reuse them.
-#include "oisat_common.h"
+#include "dense_internal.h"
 
 #include <algorithm>
 
+using namespace oisat_dense;
+
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-constexpr int NB = 128;          // diagonal block / tile edge
-constexpr int BK = 32;           // K step
-constexpr int LDSW = 36;         // padded LDS row stride in floats (144 B, 16-B aligned)
+#include "dense_tile.inc"
 
 // ---- batched launches -------------------------------------------------------------------------
 // Many independent factorizations (the tiles of a localised analysis, the months of a batch) advance in LOCK-STEP:
@@ -1297,6 +1295,8 @@ constexpr unsigned long long kTrsvEmpty = 0x7ff80bad7ff80badull;      // a quiet
 
 constexpr int kInfoUnconverged = 4, kInfoUnconvergedMember = 5, kInfoDagTimeouts = 6;     // status words (status_ws below)
 
+// trsv_row and wait_payload may touch `error` ONLY: the task-graph launch hands them its own control block (DagCtl, whose
+// `error` sits at the same offset -- asserted at the cast, dense_dag.inc: dag_sweep_task); ticket and done are the kernels'.
 struct TrsvCtl {                         // zero when a sweep starts: zeroed at allocation, then by the last workgroup of every sweep
     unsigned ticket;
     unsigned error;
@@ -1700,9 +1700,8 @@ int launch_gemm(oisat_ctx* h, const char* name, float* C, int64_t ldc, const flo
     const int ntm = (int)(M / NB), ntn = (int)(N / NB);
     const int64_t ntiles = lower ? (int64_t)ntn * ntm - (int64_t)ntn * (ntn - 1) / 2 : (int64_t)ntm * ntn;
     if (ntiles <= 0) return OISAT_OK;
-    static const bool detail = getenv("OISAT_PROF_DETAIL") && atoi(getenv("OISAT_PROF_DETAIL")) != 0;
     char dname[64];
-    if (detail && h->prof) {                                // profiling aid: one record per launch shape
+    if (prof_detail() && h->prof) {                         // profiling aid: one record per launch shape
         snprintf(dname, sizeof(dname), "%s K%d t%lld n1", name, K, (long long)ntiles);
         name = dname;
     }
@@ -1832,9 +1831,8 @@ int launch_gemm_batched(oisat_ctx* h, const char* name, const ChBatch& bt, Batch
     if (cnt == 0) return OISAT_OK;
     constexpr int small_max = 700;
     // OISAT_PROF_DETAIL=1 (profiling aid): one profile record per launch shape -- "name K tiles members" -- instead of per name
-    static const bool detail = getenv("OISAT_PROF_DETAIL") && atoi(getenv("OISAT_PROF_DETAIL")) != 0;
     char dname[64];
-    if (detail && h->prof) {
+    if (prof_detail() && h->prof) {
         snprintf(dname, sizeof(dname), "%s K%d t%lld n%d", name, K, (long long)sum, cnt);
         name = dname;
     }
@@ -2135,19 +2133,16 @@ extern "C" int oisat_trsv_plan(int64_t nb, int band, int cu_count, int32_t* two_
 static int trsv_launch_shape(const oisat_ctx* h, const ChFactor& f, int nb, int* two_out, int* grid_out) {
     int32_t two = 0, grid = 0;
     if (int rc = oisat_trsv_plan(nb, f.env != nullptr ? f.band : 0, h->cu_count, &two, &grid)) return rc;
-    const char* e = getenv("OISAT_TRSV_TWO_TILES");
-    if (e && *e) {
-        ARG_CHECK((e[0] == '0' || e[0] == '1') && e[1] == '\0');
-        two = e[0] == '1';
+    const int forced = trsv_two_tiles_forced();
+    ARG_CHECK(forced != -2 && "OISAT_TRSV_TWO_TILES is 0 or 1");
+    if (forced >= 0) {
+        two = forced;
         grid = two && h->cu_count > 0 ? std::min(nb, h->cu_count) : nb;
     }
-    e = getenv("OISAT_TRSV_MAX_WGS");
-    if (e && *e) {
-        char* end = nullptr;
-        const long cap = strtol(e, &end, 10);
-        ARG_CHECK(end != e && *end == '\0' && cap >= 1);
-        if (cap < grid) grid = (int32_t)cap;
-    }
+    long cap = 0;
+    const int capped = trsv_max_wgs(&cap);
+    ARG_CHECK(capped >= 0 && "OISAT_TRSV_MAX_WGS is an integer >= 1");
+    if (capped && cap < grid) grid = (int32_t)cap;
     *two_out = two;
     *grid_out = grid;
     return OISAT_OK;
@@ -2441,29 +2436,12 @@ hipError_t dense_kernel_attributes() {
 // 128, 100,000: 140.8 vs 137.4 -- the task graph wins at every size.  A batch of more than 1024 systems keeps the lock-step
 // recursion, and so does any launch whose chains would not leave room for the tasks they wait for (dag_fits).
 static inline bool dag_wanted(const oisat_ctx* h, int64_t max_blocks, int nsys) {
-    const int mode = h->dag_mode >= 0 ? h->dag_mode : (getenv("OISAT_DAG") ? atoi(getenv("OISAT_DAG")) : -1);
+    const int mode = h->dag_mode >= 0 ? h->dag_mode : dag_env_mode();
     if (mode == 0 || nsys > 1024) return false;
     return max_blocks >= (mode == 1 ? 2 : 3);
 }
 
 }  // namespace
-
-void oisat_dag_plan_release(void* plan) { dag_plan_free((DagPlan*)plan); }
-
-extern "C" int oisat_dag_task_order(int nsys, const int32_t* block_rows, int wave, int32_t* tasks_out, int64_t capacity,
-                                    int64_t* ntasks_out, int32_t* reserve_out, int32_t* max_wave_chains_out) {
-    ARG_CHECK(nsys > 0 && block_rows && ntasks_out && (tasks_out || capacity == 0));
-    std::vector<int> nb_of(block_rows, block_rows + nsys);
-    for (int s = 0; s < nsys; ++s) ARG_CHECK(nb_of[s] >= 1 && (s == 0 || nb_of[s] <= nb_of[s - 1]));
-    DagOrder order;
-    dag_task_order(nb_of, wave, order);
-    *ntasks_out = (int64_t)order.tasks.size();
-    if (reserve_out) *reserve_out = order.reserve_chains;
-    if (max_wave_chains_out) *max_wave_chains_out = order.max_wave_chains;
-    if ((int64_t)order.tasks.size() > capacity) return capacity == 0 ? OISAT_OK : OISAT_EINVAL;
-    memcpy(tasks_out, order.tasks.data(), sizeof(int4) * order.tasks.size());
-    return OISAT_OK;
-}
 
 extern "C" int oisat_set_refine_tol(oisat_ctx* h, double tol) {
     ARG_CHECK(h != nullptr && tol >= 0.0 && tol < 1.0);
@@ -2492,25 +2470,6 @@ extern "C" int oisat_gemm_nt(oisat_ctx* h, float* C, int64_t ldc, const float* A
     ARG_CHECK(((uintptr_t)C % 16) == 0 && ((uintptr_t)A % 16) == 0 && ((uintptr_t)B % 16) == 0);
     ARG_CHECK((mode == 0 || mode == 1) && (!lower || M >= N));
     return launch_gemm(h, "gemm_nt", C, ldc, A, lda, B, ldb, M, N, (int)K, mode, lower);
-}
-
-// OISAT_FWD_IN_LAUNCH=0: oisat_potrf_env_fwd factors as oisat_potrf_env and leaves the whole first solve to oisat_gain_solve
-// (A/B timing, tests); read at every call
-static bool fwd_in_launch_off() {
-    const char* e = getenv("OISAT_FWD_IN_LAUNCH");
-    return e != nullptr && atoi(e) == 0;
-}
-
-// OISAT_FACTOR_SHADOW (read at every call): who reads the factor's shadow (dense_dag.inc "Shadow") -- unset or 1: the far and
-// the middle stretch (3); 0: there is none, both convert in their K-loops (A/B timing, tests); far / mid: only that stretch
-// reads it (1 / 2; the writers store all the same, so that each half can be judged alone).  Anything else: -1.
-static int factor_shadow_mode() {
-    const char* e = getenv("OISAT_FACTOR_SHADOW");
-    if (!e || !*e || strcmp(e, "1") == 0) return 3;
-    if (strcmp(e, "0") == 0) return 0;
-    if (strcmp(e, "far") == 0) return 1;
-    if (strcmp(e, "mid") == 0) return 2;
-    return -1;
 }
 
 struct PotrfEnv {                // the envelope of S and its stretches; all null: dense
@@ -2548,16 +2507,11 @@ static int potrf_impl(oisat_ctx* h, float* S, int64_t m, int64_t ld, int* info_h
     // cost 5.4-6.3 ms where the recursion's GEMMs cost 4.1.  See DESIGN.md section 4.
     bool lookahead = false;
     int64_t pw = 4;
-    if (const char* env = getenv("OISAT_POTRF")) {
-        if (strcmp(env, "recursive") == 0) lookahead = false;
-        else if (strncmp(env, "lookahead", 9) == 0) {
-            lookahead = mpb >= 2;
-            if (env[9] == ':' && atoi(env + 10) > 0) pw = atoi(env + 10);      // OISAT_POTRF=lookahead:4
-        }
-    }
+    const bool schedule_forced = potrf_schedule(&lookahead, &pw);
+    lookahead = lookahead && mpb >= 2;
     int rc;
     // (an enveloped ticket has ten bits for a block column: larger systems take the recursion, which reads the build's zeros)
-    if (!lookahead && !getenv("OISAT_POTRF") && dag_wanted(h, mpb, 1) && dag_fits(1, dag_slots(h)) && (!first || mpb <= kDagEnvMaxBlocks)) {
+    if (!lookahead && !schedule_forced && dag_wanted(h, mpb, 1) && dag_fits(1, dag_slots(h)) && (!first || mpb <= kDagEnvMaxBlocks)) {
         // the plan of this (S, tinv, ld, block rows, enveloped or not) -- a handle keeps the last few (a lane that factors its
         // tiles one after the other in ONE shared buffer meets the same few sizes month after month).  An enveloped plan's
         // ticket list belongs to ONE envelope: the table itself is compared, and another envelope refills the plan's buffers.
@@ -2683,230 +2637,6 @@ extern "C" int oisat_potrf(oisat_ctx* h, float* S, int64_t m, int64_t ld, int* i
     return potrf_impl(h, S, m, ld, info_host, PotrfEnv{});
 }
 
-// OISAT_ENVELOPE=0: the enveloped entry points behave as their dense counterparts (A/B timing, tests); read at every call
-bool oisat_envelope_off() {
-    const char* e = getenv("OISAT_ENVELOPE");
-    return e != nullptr && atoi(e) == 0;
-}
-
-static bool envelope_table_ok(const int32_t* first, int64_t nb) {
-    for (int64_t i = 0; i < nb; ++i)
-        if (first[i] < 0 || first[i] > (i > 0 ? i - 1 : 0) || (i > 0 && first[i] < first[i - 1])) return false;
-    return true;
-}
-
-// The fp32 factor's own cut-off.  The factor is only the preconditioner of oisat_gain_solve, which refines against the
-// float64 residual of the true S (that residual keeps kCutBits): entries of S far below what an fp32 factorization loses by
-// itself (first residual 3e-6 .. 2.4e-5) are work the result does not need.  Chosen by a sweep on MI355X over the headline
-// month in three species and the month of test_dense_config3_full_size_properties (profiles/EXPERIMENTS.md, "The factor's
-// own cut-off"): 40 .. 24 bits leave the first residual within 0.7 %, the number of solves and the
-// last residual (within 6 %) where 52 bits have them on all four months, 20 bits raise the first residual by 6 - 8 %.  Kept:
-// the smallest admissible value, 24, plus 4 bits of headroom for a month denser than the benchmark's (the dropped row sums
-// of a 1e5-observation month lie ~4 bits above those of a 2e4-observation month).  Headline: 2 520 648 of 4 549 882 K-steps.
-constexpr double kFactorCutBits = 28.0;
-// The narrow table is used only where it buys time: a step of the factorization's chain costs ~47 us, a 128-deep K-block
-// ~15.9 us of one of 512 workgroup slots, so tile work outlasts the chain once a block row holds more than
-// 47 x 512 / 15.9 ~ 1 500 K-steps.  Below that (config 2: 228, a 2e4-observation swath month: 251) the launch IS its chain,
-// fewer K-steps win nothing, and the factor keeps the 2^-52 table and with it the bits it has always had.
-constexpr double kFactorMinKstepsPerRow = 1500.0;
-
-// first | last for the pairs whose correlation can reach 2^-bits (lat_sorted checked by the caller): their latitudes differ
-// by at most the angle of that cut-off's chord, great-circle distance >= latitude difference
-static void envelope_table(int kind, const double* lat_sorted, int64_t m, double g, double bits, int32_t* env_out) {
-    const int64_t nb = cdiv(m, NB);
-    const double angle = g > 0.0 ? lat_window_deg(kind, g, bits) : 1e9;
-    int64_t k = 0;
-    for (int64_t i = 0; i < nb; ++i) {
-        const double lo = lat_sorted[i * NB] - angle;           // tile k is outside when lat_max(tile k) < lat_min(tile i) - angle
-        while (k < i && lat_sorted[std::min((k + 1) * NB, m) - 1] < lo) ++k;
-        env_out[i] = (int32_t)std::min<int64_t>(k, i > 0 ? i - 1 : 0);
-    }
-    for (int64_t b = 0, j = 0; b < nb; ++b) {                   // last[b] = max{ j : first[j] <= b }
-        while (j + 1 < nb && env_out[j + 1] <= b) ++j;
-        env_out[nb + b] = (int32_t)j;
-    }
-}
-
-// K-loop steps of the enveloped factorization: sum over the tiles (i, j) inside the table of j - max(first[i], first[j])
-static int64_t envelope_ksteps(const int32_t* first, int64_t nb) {
-    int64_t k = 0;
-    for (int64_t i = 0; i < nb; ++i)
-        for (int64_t j = first[i]; j <= i; ++j) k += j - std::max(first[i], first[j]);
-    return k;
-}
-
-static bool lat_sorted_ok(const double* lat_sorted, int64_t m) {
-    for (int64_t i = 1; i < m; ++i)
-        if (!(lat_sorted[i] >= lat_sorted[i - 1])) return false;
-    return true;
-}
-
-// <n> bits from the environment variable `name` (read at every call, like OISAT_ENVELOPE): lo <= n <= kCutBits into *bits and
-// *set = true; unset or empty: *bits stays
-static int env_bits(const char* name, double lo, double* bits, bool* set) {
-    const char* e = getenv(name);
-    *set = e && *e;
-    if (!*set) return OISAT_OK;
-    char* end = nullptr;
-    *bits = strtod(e, &end);
-    ARG_CHECK(end != e && *end == '\0' && *bits >= lo && *bits <= kCutBits);
-    return OISAT_OK;
-}
-
-// the default rule (kFactorMinKstepsPerRow): the narrow table `first` pays
-static bool narrow_table_pays(const int32_t* first, int64_t nb) {
-    return (double)envelope_ksteps(first, nb) > kFactorMinKstepsPerRow * (double)nb;
-}
-
-extern "C" int oisat_envelope_corr(int kind, const double* lat_sorted, int64_t m, double g, int32_t* env_out) {
-    ARG_CHECK(corr_kind_ok(kind) && lat_sorted && env_out && m > 0 && g >= 0.0);
-    ARG_CHECK(lat_sorted_ok(lat_sorted, m));
-    envelope_table(kind, lat_sorted, m, g, kCutBits, env_out);  // the same cut-off as the float64 residual and the increment
-    return OISAT_OK;
-}
-
-extern "C" int oisat_envelope(const double* lat_sorted, int64_t m, double g, int32_t* env_out) {
-    return oisat_envelope_corr(OISAT_CORR_GAUSSIAN, lat_sorted, m, g, env_out);
-}
-
-// kFactorCutBits, kFactorMinKstepsPerRow and kFactorFarBits below were measured for the Gaussian only.  Gaspari-Cohn reaches
-// 2^-28 and 2^-18 at 99.5 % and 97 % of its support radius, so there is no narrower table worth having: its factor's envelope
-// IS the support envelope (oisat_envelope_corr's, which drops exact zeros only), with no chain-bound fallback to decide, and
-// its far table is empty (far = first).  SOAR, and any model that is not the Gaussian, takes the same rule -- the 2^-52 table,
-// far = first, mid = far -- because nothing has been measured for it.  The environment variables still force their rules,
-// through cut_chord.
-extern "C" int oisat_factor_envelope_corr(int kind, const double* lat_sorted, int64_t m, double g, int32_t* env_out) {
-    ARG_CHECK(corr_kind_ok(kind) && lat_sorted && env_out && m > 0 && g >= 0.0);
-    ARG_CHECK(lat_sorted_ok(lat_sorted, m));
-    double bits = kFactorCutBits;
-    bool forced = false;
-    if (int rc = env_bits("OISAT_FACTOR_CUT_BITS", 1.0, &bits, &forced)) return rc;
-    if (kind != OISAT_CORR_GAUSSIAN && !forced) bits = kCutBits;
-    envelope_table(kind, lat_sorted, m, g, bits, env_out);
-    if (kind == OISAT_CORR_GAUSSIAN && !forced && !narrow_table_pays(env_out, cdiv(m, NB)))
-        envelope_table(kind, lat_sorted, m, g, kCutBits, env_out);     // chain-bound: nothing to win, keep the float64 sums' table
-    return OISAT_OK;
-}
-
-extern "C" int oisat_factor_envelope(const double* lat_sorted, int64_t m, double g, int32_t* env_out) {
-    return oisat_factor_envelope_corr(OISAT_CORR_GAUSSIAN, lat_sorted, m, g, env_out);
-}
-
-// The far stretch of the factor's K-loops.  Left of the 2^-kFactorCutBits table every entry of S is dropped; just inside it, in
-// the block columns first[i] <= k < far[i], every correlation between an observation of block row i and one of block column k
-// is still below 2^-kFactorFarBits, and the products L(i,k) L(j,k)^T of those K-blocks add terms bounded by such entries.  The
-// factor is a preconditioner (kFactorCutBits above): rounding BOTH operands of those products to bf16 -- relative error 2^-8
-// of a term that small -- is of the order of what the cut-off drops already, and the bf16 matrix pipe issues them at 1/16 of
-// the fp32 pipe's cycles (dense_dag.inc: dag_seg_bf16).  On by default only where the narrow table is: tile-work-bound
-// systems, no forced OISAT_FACTOR_CUT_BITS.  OISAT_FACTOR_FAR_BITS=<n> (read at every call): 0 = off; 1 .. 52 forces 2^-n
-// at every enveloped size (also under a forced cut-off; a value at or above the table's own cut-off leaves nothing far).
-// The value is a measurement, by the protocol of kFactorCutBits (profiles/EXPERIMENTS.md, "The far stretch on the bf16 pipe"): on
-// the same four months 24 .. 14 bits leave the first residual within 1.0 % of the run without a stretch, the number of solves
-// and the last residual (within 4 %) where they were; 12 bits raise the first residual by 6 - 14 %.  Kept: the smallest
-// admissible value, 14, plus 4 bits of headroom for a denser month.  Headline: 872 522 of 2 519 868 K-blocks are far (0.346),
-// potrf_dag 84.0 -> 67.2 ms, the step 100.6 -> 83.8 ms.
-constexpr double kFactorFarBits = 18.0;
-
-// A stretch of the factor's K-loops as a table: out[i] = the table of cut-off 2^-bits clamped into [lower[i], i] -- lower: the table
-// below it, `first` for the far stretch, `far` for the middle one -- or lower[i] where the stretch is off.  bits: `def` under the
-// default rule -- on exactly where the narrow table is: Gaussian, tile-work-bound, no forced OISAT_FACTOR_CUT_BITS --, or the <n>
-// of the variable `var`: 0 = off, 1 .. 52 forces 2^-n at every enveloped size.  Never on under OISAT_ENVELOPE=0.
-static int stretch_table(const char* var, double def, int kind, const double* lat_sorted, int64_t m, double g, const int32_t* lower, int32_t* out) {
-    const int64_t nb = cdiv(m, NB);
-    double bits = def;
-    bool on = false, forced = false;
-    if (int rc = env_bits(var, 0.0, &bits, &forced)) return rc;
-    std::vector<int32_t> t(2 * (size_t)nb);
-    if (forced) {
-        on = bits >= 1.0;
-        ARG_CHECK(on || bits == 0.0);
-    } else {
-        const char* c = getenv("OISAT_FACTOR_CUT_BITS");
-        if (!(c && *c) && kind == OISAT_CORR_GAUSSIAN) {        // the default rule's own choice: the narrow table, or not
-            envelope_table(kind, lat_sorted, m, g, kFactorCutBits, t.data());
-            on = narrow_table_pays(t.data(), nb);
-        }
-    }
-    on = on && !oisat_envelope_off();
-    if (on) envelope_table(kind, lat_sorted, m, g, bits, t.data());
-    for (int64_t i = 0; i < nb; ++i) out[i] = on ? std::min<int32_t>(std::max(t[i], lower[i]), (int32_t)i) : lower[i];
-    return OISAT_OK;
-}
-
-extern "C" int oisat_factor_far_corr(int kind, const double* lat_sorted, int64_t m, double g, const int32_t* first, int32_t* far_out) {
-    ARG_CHECK(corr_kind_ok(kind) && lat_sorted && first && far_out && m > 0 && g >= 0.0);
-    ARG_CHECK(lat_sorted_ok(lat_sorted, m));
-    ARG_CHECK(envelope_table_ok(first, cdiv(m, NB)));
-    return stretch_table("OISAT_FACTOR_FAR_BITS", kFactorFarBits, kind, lat_sorted, m, g, first, far_out);
-}
-
-extern "C" int oisat_factor_far(const double* lat_sorted, int64_t m, double g, const int32_t* first, int32_t* far_out) {
-    return oisat_factor_far_corr(OISAT_CORR_GAUSSIAN, lat_sorted, m, g, first, far_out);
-}
-
-extern "C" int oisat_set_factor_far(oisat_ctx* h, const int32_t* far, int64_t nb) {
-    ARG_CHECK(h != nullptr && nb >= 0 && (far != nullptr || nb == 0));
-    h->factor_far.assign(far, far + nb);
-    return OISAT_OK;
-}
-
-// the table the caller set for this factorization (empty: none) against its envelope
-static bool far_table_ok(const std::vector<int32_t>& far, const int32_t* first, int64_t nb) {
-    if (far.empty()) return true;
-    if ((int64_t)far.size() != nb) return false;
-    for (int64_t i = 0; i < nb; ++i)
-        if (far[i] < first[i] || far[i] > i) return false;
-    return true;
-}
-
-// The middle stretch of the factor's K-loops: the block columns far[i] <= k < mid[i] of block row i, between the far stretch
-// and the fp32 rest.  Every correlation between an observation of block row i and one of those block columns is below
-// 2^-kFactorMidBits; the products of those K-blocks run on the bf16 pipe as SPLIT products (dense_dag.inc: dag_seg_bf16x2,
-// hi hi^T + hi lo^T + lo hi^T, relative error ~2^-16 instead of the far stretch's 2^-8), 3/16 of the fp32 pipe's MFMA cycles.
-// The argument is the far stretch's, eight bits further in: an error of 2^-16 of a term bounded by 2^-f.  On by default exactly
-// where the far stretch is (Gaussian, tile-work-bound, no forced OISAT_FACTOR_CUT_BITS, not OISAT_ENVELOPE=0).
-// OISAT_FACTOR_MID_BITS=<n> (read at every call): 0 = off (mid = far); 1 .. 52 forces 2^-n at every enveloped size; an n at or
-// above the far cut-off in force leaves nothing in the middle (the table is clamped to far[i] <= mid[i] <= i), and with the far
-// stretch off the middle one starts at first[i].
-// The value is a measurement, by the protocol of kFactorFarBits (profiles/EXPERIMENTS.md, "The middle stretch as split bf16
-// products"; profiles/mid_band_sweep.json): on the same four months, far stretch at 2^-18, OISAT_FACTOR_MID_BITS = 16 .. 6
-// leave the first residual within +1.3 % / -0.6 % of the run without a middle stretch, one correction converges, the last
-// residual within 8 %; 4 bits, the smallest value swept, are still admissible by the rule (first residual <= 1.05 x: it is
-// 1.5 - 3.6 % up, the last residual 2 - 6 %) but the rise has begun -- the host emulation puts the break between 6 and 4.
-// Kept: the smallest admissible value, 4, plus 4 bits of headroom for a denser month.  Headline: 892 351 of 2 519 868 K-blocks
-// are middle (0.354) next to 872 522 far ones (0.346); the step falls by 2.9 ms per 0.1 of share, against 4.7 for the far
-// stretch: a middle K-block costs about 0.6 of an fp32 one.  potrf_dag 66.9 -> 56.5 ms, the step 84.6 - 84.8 -> 74.4 - 74.6 ms.
-constexpr double kFactorMidBits = 8.0;
-
-extern "C" int oisat_factor_mid_corr(int kind, const double* lat_sorted, int64_t m, double g, const int32_t* first, const int32_t* far,
-                                     int32_t* mid_out) {
-    ARG_CHECK(corr_kind_ok(kind) && lat_sorted && first && far && mid_out && m > 0 && g >= 0.0);
-    ARG_CHECK(lat_sorted_ok(lat_sorted, m));
-    const int64_t nb = cdiv(m, NB);
-    ARG_CHECK(envelope_table_ok(first, nb));
-    for (int64_t i = 0; i < nb; ++i) ARG_CHECK(far[i] >= first[i] && far[i] <= i);
-    return stretch_table("OISAT_FACTOR_MID_BITS", kFactorMidBits, kind, lat_sorted, m, g, far, mid_out);
-}
-
-extern "C" int oisat_factor_mid(const double* lat_sorted, int64_t m, double g, const int32_t* first, const int32_t* far, int32_t* mid_out) {
-    return oisat_factor_mid_corr(OISAT_CORR_GAUSSIAN, lat_sorted, m, g, first, far, mid_out);
-}
-
-extern "C" int oisat_set_factor_mid(oisat_ctx* h, const int32_t* mid, int64_t nb) {
-    ARG_CHECK(h != nullptr && nb >= 0 && (mid != nullptr || nb == 0));
-    h->factor_mid.assign(mid, mid + nb);
-    return OISAT_OK;
-}
-
-// the middle table the caller set for this factorization (empty: none) against its envelope and its far table (empty: first)
-static bool mid_table_ok(const std::vector<int32_t>& mid, const std::vector<int32_t>& far, const int32_t* first, int64_t nb) {
-    if (mid.empty()) return true;
-    if ((int64_t)mid.size() != nb || !far_table_ok(far, first, nb)) return false;
-    for (int64_t i = 0; i < nb; ++i)
-        if (mid[i] < (far.empty() ? first[i] : far[i]) || mid[i] > i) return false;
-    return true;
-}
-
 extern "C" int oisat_factor_shadow_layout(int nb, const int32_t* first, int64_t* rowoff_out, int64_t* ntiles_out) {
     ARG_CHECK(nb >= 1 && nb <= kDagEnvMaxBlocks && first && rowoff_out && ntiles_out);
     ARG_CHECK(envelope_table_ok(first, nb));
@@ -2931,28 +2661,6 @@ extern "C" int oisat_factor_shadow_tile(oisat_ctx* h, int r, int k, uint16_t* hi
         for (int g = 0; g < NB / 16; ++g)
             for (int row = 0; row < NB; ++row)
                 memcpy((plane ? lo_out : hi_out) + row * NB + g * 16, raw.data() + (plane * kShPlane + g * kShGroup + row * 32) / 2, 32);
-    return OISAT_OK;
-}
-
-extern "C" int oisat_dag_task_order_env(int nb, const int32_t* first, const int32_t* far, int32_t* tasks_out, int64_t capacity,
-                                        int64_t* ntasks_out) {
-    ARG_CHECK(nb >= 1 && nb <= kDagEnvMaxBlocks && first && ntasks_out && (tasks_out || capacity == 0));
-    ARG_CHECK(envelope_table_ok(first, nb));
-    if (far)
-        for (int i = 0; i < nb; ++i) ARG_CHECK(far[i] >= first[i] && far[i] <= i);
-    // Profiling aid, this query only (no launch reads it): OISAT_DAG_ORDER_LEAD_FAR = the order a far list would have at
-    // another ticket lead, 0 <= lead < 1 -- tools/dag_sched_model.py sets a traced launch's lead beside that launch's costs.
-    double lead_far = kDagEnvLeadFar;
-    if (const char* e = getenv("OISAT_DAG_ORDER_LEAD_FAR")) {
-        char* end = nullptr;
-        lead_far = strtod(e, &end);
-        ARG_CHECK(end != e && *end == 0 && lead_far >= 0.0 && lead_far < 1.0 && "OISAT_DAG_ORDER_LEAD_FAR is a number in [0, 1)");
-    }
-    DagOrder order;
-    dag_task_order(std::vector<int>{nb}, 0, order, first, far, lead_far);
-    *ntasks_out = (int64_t)order.tasks.size();
-    if ((int64_t)order.tasks.size() > capacity) return capacity == 0 ? OISAT_OK : OISAT_EINVAL;
-    memcpy(tasks_out, order.tasks.data(), sizeof(int4) * order.tasks.size());
     return OISAT_OK;
 }
 
@@ -3048,24 +2756,6 @@ extern "C" int oisat_potrs(oisat_ctx* h, const float* L, int64_t m, int64_t ld, 
     OISAT_LAUNCH(h, "potrs_resid", potrs_resid_kernel, dim3((unsigned)cdiv(mp * 64, 256)), dim3(256), 0, h->factor.S, ld, m, mp,
                  (const double*)lt, (const double*)d, (const int*)h->factor.env, rhs);
     return trsv_solve(h, h->factor, rhs, fwd, nullptr, z_inout, 1);                             // z_inout += M^-1 r
-}
-
-int oisat_cov_residual_if(oisat_ctx* h, const double* oxyz, const double* osig, const double* ovar, int64_t m, double g,
-                          const double* d, const double* z, double* r_out, const double* olat_sorted, const int* converged_dev,
-                          const int* perm);
-const int* oisat_take_obs_perm(oisat_ctx* h, int64_t m);
-int oisat_cov_residual_update_if(oisat_ctx* h, const double* oxyz, const double* osig, const double* ovar, int64_t m, double g,
-                                 const double* r_prev, const double* dz, double* out, const double* olat_sorted, const int* converged_dev,
-                                 const int* perm);
-bool oisat_resid_update_applies(const oisat_ctx* h, double g, const double* olat_sorted, const int* perm);
-double oisat_resid_update_c();
-
-// OISAT_RESID_UPDATE=0: oisat_gain_solve forms every residual in float64, the launches and bits of the code before the update
-// form.  Read at every call; anything but 0 or 1 is an error (-1).
-static int resid_update_mode() {
-    const char* e = getenv("OISAT_RESID_UPDATE");
-    if (!e || !*e) return 1;
-    return ((e[0] == '0' || e[0] == '1') && e[1] == '\0') ? e[0] - '0' : -1;
 }
 
 // z = S^-1 d through the fp32 factor as a preconditioner:  z <- M^-1 d;  repeat { r = d - S z (float64, S regenerated from
@@ -3393,10 +3083,6 @@ extern "C" int oisat_batch_destroy(oisat_ctx* h, int batch_id) {
     h->batches[batch_id] = nullptr;
     return OISAT_OK;
 }
-
-int oisat_cov_residual_batched(oisat_ctx* h, const SolveMember* mem_dev, const std::vector<SolveMember>& mem_host, int64_t max_m, double g);
-int oisat_apply_increment_batched(oisat_ctx* h, int dtype, const SolveMember* mem_dev, const std::vector<SolveMember>& mem_host, int64_t max_n,
-                                  double g);
 
 extern "C" int oisat_batch_set_solve(oisat_ctx* h, int batch_id, int nmat, const double* const* oxyz, const double* const* osig,
                                      const double* const* ovar, const double* const* d, const double* const* olat, double* const* z,

@@ -11,6 +11,7 @@
 // tile in registers from 3 floats per point, so these kernels are VALU/transcendental-bound
 // (v_exp_f32 is quarter rate), not HBM-bound -- except cov_build, which writes S once (4 m^2 B).
 #include "oisat_common.h"
+#include "dense_switches.h"
 
 #include <algorithm>
 

@@ -3,6 +3,9 @@
 // bounding-sphere cull, and the bodies of the float64 residual and of the increment as functions of a block index and a
 // carve-out of the caller's LDS.  Included inside each translation unit's anonymous namespace; no kernels here.
 // (No reference counterpart: the dense analysis is the north-star extension, SURVEY.md section 8 a-ext.)
+#ifndef OISAT_DENSE_SWITCHES_H
+#error "include dense_switches.h at file scope before dense_solve_dev.inc: this file is included inside a namespace and cannot"
+#endif
 
 constexpr float kLog2e = 1.4426950408889634f;
 // A pair of points whose correlation is below 2^-kCutBits is left out of the float64 sums (residual, increment): 2^-52 is the
@@ -350,12 +353,8 @@ static inline double cut_chord_of(int kind, double g) { return cut_chord(kind, g
 static inline bool far_chord_of(int kind, double g, double* chord_out, double bits = -1.0, bool default_on = true) {
     if (bits < 0.0) {
         bits = default_on ? kSolveFarBits : 0.0;
-        const char* e = getenv("OISAT_SOLVE_FAR_BITS");
-        if (e && *e) {
-            char* end = nullptr;
-            bits = strtod(e, &end);
-            if (end == e || *end != '\0' || !(bits >= 0.0 && bits <= kCutBits)) return false;
-        }
+        const int set = oisat_dense::solve_far_bits(&bits);     // (dense_switches.h)
+        if (set < 0 || (set > 0 && !(bits >= 0.0 && bits <= kCutBits))) return false;
     }
     const bool on = kind == OISAT_CORR_GAUSSIAN && bits > 0.0 && bits <= kCutBits;
     *chord_out = (double)INFINITY;
@@ -369,7 +368,8 @@ static inline bool far_chord_of(int kind, double g, double* chord_out, double bi
 // The compact-block residual pays where the covariance's reach is small against the domain: measured at 720x1440 / 1e5
 // observations, L = 300 km (reach 2 800 km): 6.6 -> 4.6 ms; a month's 50 tiles: 1.69 -> 1.59 ms; at 360x720 / 1e4 observations,
 // L = 500 km (reach 4 700 km) the staging costs more than the cull saves: 0.21 -> 0.26 ms.
-// (The rule is about the reach: the Gaussian's 2^-64 chord, as measured.  Gaspari-Cohn: the same 0.5 applied to its support
+// (The rule is about the reach: the Gaussian's 2^-64 chord, as measured -- the 64 below is that measurement's and did not follow
+// the sums' cut-off when kCutBits went from 64 to 52; include/oisat.h says the same of oisat_cov_residual_update.  Gaspari-Cohn: the same 0.5 applied to its support
 // chord; SOAR: to its 2^-52 chord (L <= 80 km) -- both reasoned from the Gaussian's figures, not measured.)
 static inline bool residual_blocks_pay(int kind, double g) {
     if (kind != OISAT_CORR_GAUSSIAN) return cut_chord(kind, g, kCutBits) <= 0.5;

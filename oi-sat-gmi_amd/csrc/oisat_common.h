@@ -96,7 +96,7 @@ struct ChBatch {                 // matrices factored in lock-step by oisat_batc
     int ord_total = 0;
     int64_t max_m = 0, max_n = 0, max_mp = 0;
     bool pairs = false;          // leaves of its recursion are pairs of block columns (many members: the leaf launches are HBM-bound)
-    void* dag = nullptr;         // task-graph plan of the batch (dense_dag.inc: DagPlan), owned
+    void* dag = nullptr;         // task-graph plan of the batch (dense_internal.h: DagPlan), owned
     void* dag_solve = nullptr;   // ... of the batch's factorization + solve phase in one launch (oisat_batch_analyse), made on first use
     int dag_solve_refine = -1, dag_solve_cells = 0;             // what that plan was made for
 };
@@ -143,7 +143,7 @@ struct oisat_ctx {
     int comm_rank = 0, comm_size = 1;
     hipEvent_t signal_event = nullptr;  // oisat_wait_for: recorded on this handle's stream, waited on by another handle's
     std::vector<ChBatch*> batches;      // oisat_batch_create
-    // task-graph plans of the last single-system factorizations on this handle (dense_dag.inc), keyed by what a plan depends on
+    // task-graph plans of the last single-system factorizations on this handle (dense_dag_plan.hip), keyed by what a plan depends on
     const int* obs_perm = nullptr;      // oisat_set_obs_blocks: space-filling order of the observations of the next gain solves
     int64_t obs_perm_m = 0;
     std::vector<int32_t> factor_far;    // oisat_set_factor_far: the far stretch of the NEXT enveloped factorization (one-shot)
@@ -182,8 +182,20 @@ struct oisat_ctx {
 // workspace slot `slot` of at least `bytes` (grow-only); returns nullptr + error on failure
 void* oisat_ws(oisat_ctx* h, int slot, size_t bytes);
 void* oisat_pinned(oisat_ctx* h, size_t bytes);
-bool oisat_envelope_off();                              // dense_chol.hip: OISAT_ENVELOPE=0 -- the enveloped entry points run dense
-void oisat_dag_plan_release(void* plan);                // dense_chol.hip: frees a task-graph plan (nullptr allowed)
+void oisat_dag_plan_release(void* plan);                // dense_dag_plan.hip: frees a task-graph plan (nullptr allowed)
+// dense_cov.hip, for dense_chol.hip: the residual and increment forms of the gain solve and of the batch API
+const int* oisat_take_obs_perm(oisat_ctx* h, int64_t m);
+int oisat_cov_residual_if(oisat_ctx* h, const double* oxyz, const double* osig, const double* ovar, int64_t m, double g,
+                          const double* d, const double* z, double* r_out, const double* olat_sorted, const int* converged_dev,
+                          const int* perm);
+int oisat_cov_residual_update_if(oisat_ctx* h, const double* oxyz, const double* osig, const double* ovar, int64_t m, double g,
+                                 const double* r_prev, const double* dz, double* out, const double* olat_sorted, const int* converged_dev,
+                                 const int* perm);
+bool oisat_resid_update_applies(const oisat_ctx* h, double g, const double* olat_sorted, const int* perm);
+double oisat_resid_update_c();
+int oisat_cov_residual_batched(oisat_ctx* h, const SolveMember* mem_dev, const std::vector<SolveMember>& mem_host, int64_t max_m, double g);
+int oisat_apply_increment_batched(oisat_ctx* h, int dtype, const SolveMember* mem_dev, const std::vector<SolveMember>& mem_host, int64_t max_n,
+                                  double g);
 
 int oisat_prof_begin(oisat_ctx* h, const char* name);   // returns pending index or -1
 void oisat_prof_end(oisat_ctx* h, int pending);

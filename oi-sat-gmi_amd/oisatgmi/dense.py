@@ -14,7 +14,7 @@ observation per cell: there C = I and K_ii = s Sa_i / (s Sa_i + So_i) (:27).  Th
 reference implementation of the dense form, so its parity is pinned only in that limit; away from
 it the check is the float64 restatement in ``oracle/`` ("parity unpinned").
 
-Pipeline (all in HBM, csrc/dense_cov.hip + csrc/dense_chol.hip):
+Pipeline (all in HBM, csrc/dense_cov.hip + csrc/dense_chol.hip; host tables and plans: dense_tables.hip, dense_dag_plan.hip):
 ``oisat_innovation`` -> ``oisat_cov_build`` (S, fp32) -> ``oisat_potrf`` (MFMA fp32 Cholesky) ->
 ``oisat_gain_solve`` (triangular solves + float64-residual refinement) -> ``oisat_apply_increment``
 (B H^T z generated on the fly, never stored).  ``DenseAnalysis.run()`` owns the latitude sort of its observations and
@@ -33,7 +33,7 @@ import numpy as np
 from . import _hip
 
 EARTH_RADIUS_KM = 6371.0
-NB = 128                      # Cholesky block edge (csrc/dense_chol.hip)
+NB = 128                      # Cholesky block edge (csrc/dense_tile.inc)
 SCHEDULE_ENV_DAG, SCHEDULE_ENV_DAG_FWD = 1, 2      # oisat_potrf_env_fwd's schedule_out: the enveloped task graph factored (include/oisat.h)
 # relative float64 residual |d - S z| / |d| at which the gain solve stops refining (oisat_gain_solve): the increment is K r
 # away from the exact one and |K| <= 1, so the fields are then within 1e-6 |d| -- a tenth of the 1e-5 bar

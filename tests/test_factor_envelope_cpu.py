@@ -11,7 +11,7 @@ from oisatgmi import _hip, dense, synthetic as syn
 from oracle import oi_oracle as orc
 from test_envelope_cpu import CASES, NB, counts, envelope, sorted_obs
 
-FACTOR_CUT_BITS = 28               # kFactorCutBits (csrc/dense_chol.hip)
+FACTOR_CUT_BITS = 28               # kFactorCutBits (csrc/dense_tables.hip)
 HEADLINE_KSTEPS = 2520648          # config 3 at 2^-28, counted with the rule of test_envelope_cpu.counts (4 549 882 at 2^-52)
 OVERRIDE = "OISAT_FACTOR_CUT_BITS"
 

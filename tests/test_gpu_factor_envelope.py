@@ -12,7 +12,7 @@ from oracle import oi_oracle as orc
 
 pytestmark = pytest.mark.gpu
 NB = 128
-FACTOR_CUT_BITS = 28               # kFactorCutBits (csrc/dense_chol.hip)
+FACTOR_CUT_BITS = 28               # kFactorCutBits (csrc/dense_tables.hip)
 OVERRIDE = "OISAT_FACTOR_CUT_BITS"
 
 

@@ -178,7 +178,7 @@ def test_tile_partition_polar_caps_and_halo():
 
 
 # ------------------------------------------------------------------------------------------------
-# task-graph factorization: the ticket order (csrc/dense_dag.inc), checked on the host
+# task-graph factorization: the ticket order (csrc/dense_dag_plan.hip), checked on the host
 # ------------------------------------------------------------------------------------------------
 def _dag_order(block_rows, wave=0):
     import ctypes as C
@@ -204,7 +204,7 @@ MONTH = sorted([137, 137] + [48, 47, 45, 44, 40, 33, 31] * 6 + [46] * 6, reverse
 @pytest.mark.parametrize("block_rows,wave", [([79], 0), (MONTH, 8), ([17, 12, 11, 8, 7, 5, 3, 3, 2, 1, 1], 2), ([20, 9, 9, 8, 8, 7, 3, 2, 1], 5)])
 def test_task_graph_ticket_order_is_topological_and_complete(block_rows, wave):
     """Every tile of every system is owned by exactly one task, and every input of a task carries a LOWER ticket or is a step of
-    its system's chain, whose own ticket is lower (csrc/dense_dag.inc).  Inputs of a task on tile (i, j) of system s: the final
+    its system's chain, whose own ticket is lower (csrc/dense_dag_plan.hip).  Inputs of a task on tile (i, j) of system s: the final
     blocks L(i, k), L(j, k), k < j (k < j - 1 for PRE), each produced by the tile task T(., k) of that row -- or by the chain for
     the sub-diagonal tile -- and the diagonal block j (chain)."""
     tasks, reserve, _ = _dag_order(block_rows, wave)
