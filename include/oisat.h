@@ -896,6 +896,55 @@ int oisat_covariogram_quantum(double umax, int64_t m, double* q_prod_out, double
 int oisat_buddy_sums(oisat_ctx* h, const double* oxyz, const double* u, int64_t m, double g, double cmin,
                      const double* olat_sorted, int32_t* n_out, double* sums_out /* W[m] | P[m] | Q[m] */);
 
+/* ---- superobservations: the observations of one box merged into one, ahead of the dense analysis ----
+ * BOXES: a reduced latitude-longitude grid of roughly equal area.  nbands = ceil(180 / box_deg) latitude bands; band j covers
+ * [lo_j, hi_j) with lo_j = -90 + (double)j box_deg and hi_j = min(-90 + (double)(j + 1) box_deg, 90) (the last band may be
+ * short, and it takes latitude 90 itself); mid_j = 0.5 (lo_j + hi_j); the band has
+ *   n_j = max(1, llrint(360 cos(mid_j (pi / 180)) / box_deg))          (left to right, pi / 180 one constant)
+ * longitude boxes of 360 / n_j degrees starting at longitude 0; offset_j = n_0 + .. + n_(j-1); box id = offset_j + k;
+ * nbox = offset_nbands.
+ * oisat_superob_boxes (host only, no device call, float64): writes n_out[nbands] (int32) and offset_out[nbands] (int64), HOST
+ * arrays of `cap` entries (cap = 0: neither is written, the two counts alone), *nbands_out and *nbox_out (either may be NULL).
+ * box_deg finite and in (0, 180], 180 / box_deg <= 1 << 23, and cap = 0 or >= nbands; anything else is OISAT_EINVAL and
+ * writes nothing.
+ * THE BOX OF AN OBSERVATION, on the device, one rounding per operation and no FMA:
+ *   j = min((int64)floor((lat + 90) / box_deg), nbands - 1)
+ *   r = lon / 360,  t = r - floor(r)                                   (t in [0, 1]; 1 for a tiny negative lon)
+ *   k = min((int64)(t * (double)n_j), n_j - 1),   box = offset_j + k.
+ * An observation takes part iff lat, lon, d, sigma_b and var are finite, |lat| <= 90, var > 0 and w = 1 / var is finite; every
+ * other observation gets box -1 and adds nothing.  oxyz is not tested: the caller supplies unit vectors, as everywhere else.
+ * oisat_superob: olat, olon (degrees), d, sigma_b, var: dev double[m]; oxyz: dev double[3][m] unit vectors; box_n (int32) and
+ * box_offset (int64): HOST arrays of nbands, with nbox the table of oisat_superob_boxes(box_deg) -- checked (nbands =
+ * ceil(180 / box_deg), every n_j >= 1, the offsets their running sum, nbox its end, nbox <= 1 << 23), because the device
+ * indexes the accumulators with it.  box_out: dev int32[m].  count_out: HOST int64[nbox].  sums_out: HOST
+ * double[OISAT_SUPEROB_NSUMS][nbox], quantity-major, or NULL: box ids and counts only (oxyz may then be NULL and no quantum is
+ * formed).  *nused_out (host, may be NULL): the observations that take part.  Two launches on the handle's stream (the maxima,
+ * the sums), then it SYNCHRONISES and copies the results to the host, like oisat_covariogram.  With w = 1 / var, per box:
+ *   count += 1, W += w, Q += sqrt(w), D += w d, V += (w d) d, G += w sigma_b, Px += w x, Py += w y, Pz += w z.
+ * The sums are exact integers by the covariogram's rule, hence independent of the order of the observations, of the launch
+ * shape and of the run, bit for bit.  With wmax, dmax, smax the largest w, |d|, |sigma_b| over the observations that take
+ * part (a device reduction), M = (double)max(m, 1), and for a bound b: q(b) = 2^(e - 62), e the frexp exponent of b M (1 if
+ * b M = 0; the exponent kept at -1022 or above):
+ *   q_W = q(wmax),  q_Q = q(2^ceil(e_w / 2)) with e_w the frexp exponent of wmax (sqrt(w) is below that power of two),
+ *   q_D = q(wmax dmax),  q_V = q(wmax dmax dmax),  q_G = q(wmax smax),  q_P = q(2 wmax) for all three components
+ * (products left to right, as the terms are formed, so no term exceeds its bound).  Each term is rounded once, to
+ * llrint(term / q) (an exact division, nearest even), the terms are added as int64 (below 2^63 by the choice of q) and a box's
+ * output is (double)sum * q.  So |sum - exact| <= count q / 2 plus the last bit of the result, for every quantity and box.
+ * 2 wmax M, wmax dmax dmax M and wmax smax M must be finite: OISAT_EINVAL after the launches otherwise, the host outputs untouched.
+ * 0 <= m <= 1 << 20 (m = 0: zeros), box_deg finite and in (0, 180], a table as above, non-NULL count_out and, where m > 0,
+ * non-NULL inputs and box_out; anything else is OISAT_EINVAL and writes nothing.
+ * Workspace: 64 B + 12 nbands B + 8 (1 + OISAT_SUPEROB_NSUMS) nbox B on the handle (1 degree boxes: 3.0 MB), grow-only,
+ * allocated at the first call that needs it (oisat_dense_reserve does not cover it).
+ * oisat_superob_quanta (host only): q_out[6] = q_W, q_Q, q_D, q_V, q_G, q_P by this rule, for tests and callers that bound the
+ * error; m outside 0 .. 1 << 20, a negative or NaN maximum, or one of the three products not finite is OISAT_EINVAL. */
+#define OISAT_SUPEROB_NSUMS 8              /* rows of sums_out: W, Q, D, V, G, Px, Py, Pz */
+int oisat_superob_boxes(double box_deg, int64_t cap, int32_t* n_out, int64_t* offset_out, int64_t* nbands_out, int64_t* nbox_out);
+int oisat_superob_quanta(double wmax, double dmax, double smax, int64_t m, double* q_out);
+int oisat_superob(oisat_ctx* h, const double* olat, const double* olon, const double* oxyz, const double* d,
+                  const double* sigma_b, const double* var, int64_t m, double box_deg, const int32_t* box_n,
+                  const int64_t* box_offset, int64_t nbands, int64_t nbox, int32_t* box_out, int64_t* count_out,
+                  double* sums_out, int64_t* nused_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -164,6 +164,10 @@ SIGNATURES = {
     "oisat_covariogram": (C.c_int, [_c_ctx, _ptr, _ptr, _ptr, _i64, C.c_double, C.c_int, _ptr, _ptr, _ptr, _ptr, C.POINTER(_i64)]),
     "oisat_covariogram_quantum": (C.c_int, [C.c_double, _i64, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "oisat_buddy_sums": (C.c_int, [_c_ctx, _ptr, _ptr, _i64, C.c_double, C.c_double, _ptr, _ptr, _ptr]),
+    "oisat_superob_boxes": (C.c_int, [C.c_double, _i64, _ptr, _ptr, C.POINTER(_i64), C.POINTER(_i64)]),
+    "oisat_superob_quanta": (C.c_int, [C.c_double, C.c_double, C.c_double, _i64, _ptr]),
+    "oisat_superob": (C.c_int, [_c_ctx, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _i64, C.c_double, _ptr, _ptr, _i64, _i64, _ptr, _ptr,
+                                _ptr, C.POINTER(_i64)]),
 }
 
 

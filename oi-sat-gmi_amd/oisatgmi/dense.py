@@ -21,6 +21,8 @@ Pipeline (all in HBM, csrc/dense_cov.hip + csrc/dense_chol.hip; host tables and 
 therefore builds and factors only the covariance's latitude envelope (``oisat_factor_envelope`` ->
 ``oisat_cov_build_env_zeroed`` -> ``oisat_potrf_env_fwd``; DESIGN.md section 4.2a: the fp32 factor, a preconditioner, has a
 cut-off of its own; the build does not re-zero what is zero, the factorization launch carries the first forward sweep).
+``OI_dense(..., superob=box_deg)`` first merges the observations of one box into a superobservation (``superob``,
+csrc/superob.hip: ``oisat_superob``), so that a month denser than HBM allows still has a dense analysis.
 """
 from __future__ import annotations
 
@@ -1068,7 +1070,7 @@ class MonthTileBatch:
 
 
 def OI_dense(Xa, Y, Sa, So, lat, lon, L_km, scale=1.0, refine=2, obs=None, dtype=None, want_error=False, tol=None,
-             corr="gaussian", nprobe=256, seed=0):
+             corr="gaussian", nprobe=256, seed=0, superob=None, superob_rho=0.0):
     """Dense-covariance analysis with the reference's gridded argument convention.
 
     ``Xa, Sa``: (ny, nx) background and its variance; ``Y, So``: (ny, nx) observations and their
@@ -1080,11 +1082,20 @@ def OI_dense(Xa, Y, Sa, So, lat, lon, L_km, scale=1.0, refine=2, obs=None, dtype
     ``want_error``: True = the exact ``err`` / ``ak`` / ``ak_obs`` (n m^2 flop); ``"mc"`` = their randomized estimates from
     ``nprobe`` probes (``DenseAnalysis.posterior_error_mc``) with ``err_se`` / ``ak_obs_se`` beside them and
     ``info["error_method"] = "mc"``.
+    ``superob``: None (default) = every observation is a row of the system; a number = the observations are first merged into
+    superobservations over boxes of that many degrees (``superob``) and the system has one row per
+    non-empty box; ``"auto"`` / ``"auto:<max_obs>"`` = nothing is done while the observations number at most ``max_obs``
+    (default 100 000), otherwise the smallest box of ``SUPEROB_LADDER`` that leaves at most ``max_obs``.  ``superob_rho``: the
+    correlation the errors of one box's members share.  With superobservations ``info["cells"]`` and ``info["nobs"]`` stay the raw ones,
+    ``info["z"]`` / ``["ak_obs"]`` / ``["ak_obs_se"]`` are per superobservation, ``info["superob"]`` tells what was merged and
+    ``info["ak"]`` gives member cell a of superobservation s the share ``ak_obs[s] w_a / W_s``.
     """
     corr_kind(corr)                                           # (ValueError before anything is touched)
     mc = isinstance(want_error, str)
     if mc and want_error != "mc":
         raise ValueError(f"want_error is False, True or 'mc', got {want_error!r}")
+    so_box, so_max = superob_setting(superob)
+    superob_rho = _superob_rho(superob_rho)
     Xa = np.asarray(Xa)
     if obs is None:
         Y[Y < 0] = 0.0                                        # same clamp as optimal_interpolation.py:14
@@ -1098,7 +1109,21 @@ def OI_dense(Xa, Y, Sa, So, lat, lon, L_km, scale=1.0, refine=2, obs=None, dtype
         ovar = np.ravel(obs["var"])
         cell = regular_grid_cell(lat, lon, olat, olon)
     dt = np.dtype(dtype) if dtype is not None else _hip.compute_dtype(Xa)
-    if cell.size == 0:                 # a month without a single usable observation: nothing to spread, x_a = x_b
+    xa_f = np.where(np.isfinite(Xa), Xa, 0.0)
+    sa_f = np.where(np.isfinite(Sa), Sa, 0.0)
+    so = None
+    if so_box is not None and not (so_box == "auto" and cell.size <= so_max):
+        # innovations as the plain path forms them (oisat_innovation: y - x_b[cell] with x_b in the field dtype) and sigma_b
+        # as load_obs takes it (sqrt(scale Sa) of the cell)
+        d_raw = np.asarray(oy, dtype=np.float64) - np.ravel(xa_f).astype(dt).astype(np.float64)[cell]
+        sig_raw = np.sqrt(float(scale) * np.ravel(np.asarray(sa_f, dtype=np.float64)))[cell]
+        if so_box == "auto":
+            so_box = superob_auto_box(olat, olon, d_raw, sig_raw, ovar, so_max)
+        so = _superob_fn(olat, olon, d_raw, sig_raw, ovar, so_box, rho=superob_rho)
+        so_info = {"box_deg": so["box_deg"], "rho": so["rho"], "nobs_raw": so["nobs_raw"], "nobs": so["nobs"],
+                   "count": so["count"], "spread": so["spread"], "index": so["index"]}
+    if cell.size == 0 or (so is not None and so["nobs"] == 0):
+        # a month without a single usable observation: nothing to spread, x_a = x_b
         _hip.context()                 # (still no CPU path: fail here if the library or the GPU is missing)
         extra = {}
         if want_error:
@@ -1107,13 +1132,17 @@ def OI_dense(Xa, Y, Sa, So, lat, lon, L_km, scale=1.0, refine=2, obs=None, dtype
             if mc:
                 extra.update(err=extra["err"].astype(np.float32), err_se=np.zeros(np.shape(Xa)), ak_obs_se=np.empty(0),
                              error_method="mc", nprobe=int(nprobe))
+        if so is not None:
+            extra["superob"] = so_info
         return (np.array(Xa, dtype=dt), np.zeros(np.shape(Xa), dtype=dt),
                 {"nobs": 0, "residuals": [], "cells": cell, "z": np.empty(0), **extra})
-    plan = DenseAnalysis(lat, lon, max_obs=int(cell.size), dtype=dt, diag_chunk_rows=4096 if want_error and not mc else 0)
-    xa_f = np.where(np.isfinite(Xa), Xa, 0.0)
-    sa_f = np.where(np.isfinite(Sa), Sa, 0.0)
+    plan = DenseAnalysis(lat, lon, max_obs=int(cell.size if so is None else so["nobs"]), dtype=dt,
+                         diag_chunk_rows=4096 if want_error and not mc else 0)
     plan.load_background(xa_f, sa_f, scale=scale)
-    plan.load_obs(olat, olon, cell, oy, ovar)
+    if so is None:
+        plan.load_obs(olat, olon, cell, oy, ovar)
+    else:                              # one row per superobservation: a point observation at the members' weighted centroid
+        plan.load_obs_direct(so["lat"], so["lon"], so["sigma_b"], so["var"], so["d"])
     resid = plan.run(L_km, refine=refine, check_pd=True, want_resid=True, tol=tol, corr=corr)
     xb, inc = plan.download()
     extra = {}
@@ -1121,10 +1150,15 @@ def OI_dense(Xa, Y, Sa, So, lat, lon, L_km, scale=1.0, refine=2, obs=None, dtype
         # diag(K H) at a cell = sum over the observations INSIDE that cell of diag(H K) at the observation
         # ((B H^T S^-1)[cell(a), a] = (H B H^T S^-1)[a, a]); with one observation per cell -- the reference's
         # case -- this is AK of optimal_interpolation.py:31.  np.add.at: deterministic for repeated cells.
-        est = plan.posterior_error_mc(nprobe=nprobe, seed=seed, gridded=obs is None) if mc else None
+        est = plan.posterior_error_mc(nprobe=nprobe, seed=seed, gridded=obs is None and so is None) if mc else None
         ak_obs = est["ak_obs"] if mc else plan.gain_diag()
         ak_sum = np.zeros(Xa.size)
-        np.add.at(ak_sum, cell, ak_obs)
+        if so is None:
+            np.add.at(ak_sum, cell, ak_obs)
+        else:                          # the share rule: member a of superobservation s carries ak_obs[s] w_a / W_s
+            mem = so["index"] >= 0
+            si = so["index"][mem]
+            np.add.at(ak_sum, cell[mem], ak_obs[si] * (1.0 / np.asarray(ovar, dtype=np.float64)[mem]) / so["W"][si])
         ak = np.full(Xa.size, np.nan)
         ak[cell] = ak_sum[cell]
         extra = {"ak": ak.reshape(np.shape(Xa)), "err": est["err"] if mc else plan.posterior_error(), "ak_obs": ak_obs}
@@ -1134,6 +1168,8 @@ def OI_dense(Xa, Y, Sa, So, lat, lon, L_km, scale=1.0, refine=2, obs=None, dtype
     if bad.any():
         xb = xb.copy()
         xb[bad] = np.nan
+    if so is not None:
+        extra["superob"] = so_info
     return xb, inc, {"nobs": int(cell.size), "residuals": resid, "cells": cell, "z": plan.download_z(), **extra}
 
 
@@ -1459,3 +1495,183 @@ def qc_innovations(Xa, Y, Sa, So, lat, lon, L_km, scale=1.0, corr="gaussian", **
     mask = np.zeros(Xa.size, dtype=bool)
     mask[cell[out["rejected"]]] = True
     return {**out, "cells": cell, "rejected_cells": mask.reshape(np.shape(Xa))}
+
+
+# ---- superobservations: the observations of one box merged into one ---------------------------------
+SUPEROB_MAX_OBS = 1 << 20                            # include/oisat.h: oisat_superob
+SUPEROB_LADDER = (0.5, 0.75, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0)     # box sizes "auto" tries, degrees, smallest first
+SUPEROB_AUTO_MAX_OBS = 100_000                       # "auto": the size the headline is measured at
+KM_PER_DEG = 111.19                                  # a degree of latitude on the sphere of EARTH_RADIUS_KM
+_SO_W, _SO_Q, _SO_D, _SO_V, _SO_G, _SO_PX = 0, 1, 2, 3, 4, 5   # rows of oisat_superob's sums_out (then Py, Pz)
+
+
+def _lib_check(lib, rc):
+    if rc != 0:
+        raise _hip.OisatError(f"liboisat_hip error {rc}: {lib.oisat_last_error().decode()}")
+
+
+def _superob_rho(rho) -> float:
+    rho = float(rho)
+    if not (0.0 <= rho < 1.0):
+        raise ValueError(f"superob_rho must be in [0, 1), not {rho!r}")
+    return rho
+
+
+def superob_setting(v):
+    """``None`` / ``"off"`` -> ``(None, 0)``; a positive number (or its string) -> ``(box_deg, 0)``; ``"auto"`` /
+    ``"auto:<max_obs>"`` -> ``("auto", max_obs)`` (default ``SUPEROB_AUTO_MAX_OBS``; a positive integer).  Anything else is a
+    ``ValueError``."""
+    if v is None:
+        return None, 0
+    bad = ValueError(f"superob: expected off, <degrees> in (0, 180], auto or auto:<max_obs> (a positive integer), not {v!r}")
+    if isinstance(v, str):
+        t = v.strip().lower()
+        if t == "off":
+            return None, 0
+        if t == "auto":
+            return "auto", SUPEROB_AUTO_MAX_OBS
+        if t.startswith("auto:"):
+            try:
+                n = int(t[5:])
+            except ValueError:
+                raise bad from None
+            if n < 1:
+                raise bad
+            return "auto", n
+        try:
+            v = float(t)
+        except ValueError:
+            raise bad from None
+    if isinstance(v, bool):
+        raise bad
+    try:
+        deg = float(v)
+    except (TypeError, ValueError):
+        raise bad from None
+    if not (0.0 < deg <= 180.0):
+        raise bad
+    return deg, 0
+
+
+def superob_boxes(box_deg):
+    """The box table of ``oisat_superob`` for boxes of ``box_deg`` degrees (host only, float64; the rule is in include/oisat.h):
+    -> dict ``box_deg``, ``nbands``, ``nbox``, ``n`` (int32 per latitude band: its longitude boxes), ``offset`` (int64: the id of
+    the band's first box)."""
+    lib = _hip.load_library()
+    box_deg = float(box_deg)
+    nbands, nbox = C.c_int64(0), C.c_int64(0)
+    _lib_check(lib, lib.oisat_superob_boxes(box_deg, 0, None, None, C.byref(nbands), C.byref(nbox)))
+    n, off = np.zeros(nbands.value, dtype=np.int32), np.zeros(nbands.value, dtype=np.int64)
+    _lib_check(lib, lib.oisat_superob_boxes(box_deg, n.size, n.ctypes.data, off.ctypes.data, C.byref(nbands), C.byref(nbox)))
+    return {"box_deg": box_deg, "nbands": int(nbands.value), "nbox": int(nbox.value), "n": n, "offset": off}
+
+
+def superob_quanta(wmax: float, dmax: float, smax: float, m: int) -> np.ndarray:
+    """The six quanta ``q_W, q_Q, q_D, q_V, q_G, q_P`` of ``oisat_superob`` (host only; ``OisatError`` outside its range)."""
+    lib = _hip.load_library()
+    q = np.zeros(6)
+    _lib_check(lib, lib.oisat_superob_quanta(float(wmax), float(dmax), float(smax), int(m), q.ctypes.data))
+    return q
+
+
+def _superob_inputs(obs_lat, obs_lon, innovation, sigma_b, obs_var):
+    d = np.ravel(np.asarray(innovation, dtype=np.float64))
+    arrs = [np.ravel(np.asarray(a, dtype=np.float64)) for a in (obs_lat, obs_lon)] + [d]
+    arrs += [np.ravel(np.broadcast_to(np.asarray(a, dtype=np.float64), np.shape(innovation))) for a in (sigma_b, obs_var)]
+    if any(a.size != d.size for a in arrs):
+        raise ValueError("obs_lat, obs_lon, innovation, sigma_b and obs_var must have the same size")
+    if d.size > SUPEROB_MAX_OBS:
+        raise ValueError(f"{d.size} observations; superobservations take at most {SUPEROB_MAX_OBS}")
+    return arrs
+
+
+def _superob_device(c, lat, lon, d, sig, var, table, with_sums):
+    """``oisat_superob`` on host arrays -> (box int32[m], count int64[nbox], sums float64[8][nbox] or None, nused)."""
+    m, nbox = int(d.size), table["nbox"]
+    count = np.zeros(nbox, dtype=np.int64)
+    sums = np.zeros((8, nbox)) if with_sums else None
+    used = C.c_int64(0)
+    if m == 0:
+        return np.zeros(0, dtype=np.int32), count, sums, 0
+    bufs = [c.upload(a) for a in (lat, lon, d, sig, var)] + [c.alloc(4 * m)]
+    if with_sums:
+        bufs.append(c.upload(unit_vectors(lat, lon)))
+    try:
+        c.check(c.lib.oisat_superob(c.h, bufs[0].ptr, bufs[1].ptr, bufs[6].ptr if with_sums else None, bufs[2].ptr, bufs[3].ptr,
+                                    bufs[4].ptr, m, table["box_deg"], table["n"].ctypes.data, table["offset"].ctypes.data,
+                                    table["nbands"], nbox, bufs[5].ptr, count.ctypes.data,
+                                    sums.ctypes.data if with_sums else None, C.byref(used)))
+        box = c.download(bufs[5].ptr, (m,), np.int32)
+    finally:
+        for b in bufs:
+            b.free()
+    return box, count, sums, int(used.value)
+
+
+def superob_count(obs_lat, obs_lon, innovation, sigma_b, obs_var, box_deg, ctx=None) -> int:
+    """The number of non-empty boxes of ``box_deg`` degrees, i.e. of superobservations ``superob`` would return (the kernel's
+    count-only form: no sums are formed)."""
+    lat, lon, d, sig, var = _superob_inputs(obs_lat, obs_lon, innovation, sigma_b, obs_var)
+    _, count, _, _ = _superob_device(ctx or _hip.context(), lat, lon, d, sig, var, superob_boxes(box_deg), False)
+    return int(np.count_nonzero(count))
+
+
+def superob_ladder_pick(counts, max_obs: int) -> float:
+    """The smallest box of ``SUPEROB_LADDER`` whose number of non-empty boxes is at most ``max_obs``.  ``counts``: a mapping
+    ``box_deg -> count`` or a callable giving it (called for the boxes in ascending order, up to the first that fits).  None
+    fits: a ``ValueError`` that names the counts."""
+    get = counts if callable(counts) else counts.__getitem__
+    seen = []
+    for box in SUPEROB_LADDER:
+        n = int(get(box))
+        seen.append((box, n))
+        if n <= int(max_obs):
+            return box
+    raise ValueError(f"superob auto: no box of the ladder leaves at most {int(max_obs)} superobservations (box_deg: count = "
+                     + ", ".join(f"{b:g}: {n}" for b, n in seen) + ")")
+
+
+def superob_auto_box(obs_lat, obs_lon, innovation, sigma_b, obs_var, max_obs, ctx=None) -> float:
+    """``superob_ladder_pick`` with the counts from ``superob_count``."""
+    return superob_ladder_pick(lambda box: superob_count(obs_lat, obs_lon, innovation, sigma_b, obs_var, box, ctx=ctx), max_obs)
+
+
+def superob(obs_lat, obs_lon, innovation, sigma_b, obs_var, box_deg, rho=0.0, ctx=None):
+    """Superobservations: the observations inside one box of a roughly equal-area grid of ``box_deg`` degrees merged into one,
+    the inverse-variance-weighted mean.  The per-box sums are formed on the device (``oisat_superob``: exact integer sums,
+    bitwise repeatable and independent of the order of the observations); with w = 1 / var and, per box, W = sum w,
+    Q = sum sqrt(w), D = sum w d, V = sum w d^2, G = sum w sigma_b, P = sum w (x, y, z):
+    position = P normalised; ``d = D / W``; ``sigma_b = G / W``; ``var = ((1 - rho) W + rho Q^2) / W^2``, the variance of that
+    mean when the members' errors share a uniform correlation ``rho`` (0 <= rho < 1; 0: 1 / W); ``spread = max(V / W - d^2, 0)``,
+    the members' weighted scatter (a diagnostic, not fed back).  An observation takes part iff its five numbers are finite,
+    |lat| <= 90 and 1 / var is finite; one that would but for ``var <= 0`` is a ``ValueError``.
+    -> dict, the superobservations of the non-empty boxes in ascending box id: ``lat``, ``lon``, ``d``, ``sigma_b``, ``var``,
+    ``spread``, ``count``, ``W``, ``box_id``; per observation ``box`` (int32, -1: takes no part) and ``index`` (its
+    superobservation, -1 likewise); ``nobs`` (superobservations), ``nobs_raw`` (observations that take part), ``box_deg``, ``rho``."""
+    rho = _superob_rho(rho)
+    lat, lon, d, sig, var = _superob_inputs(obs_lat, obs_lon, innovation, sigma_b, obs_var)
+    with np.errstate(invalid="ignore"):
+        wrong = np.isfinite(lat) & np.isfinite(lon) & np.isfinite(d) & np.isfinite(sig) & np.isfinite(var) & (np.abs(lat) <= 90) & (var <= 0)
+    if wrong.any():
+        raise ValueError(f"{int(wrong.sum())} observation(s) with an error variance <= 0 cannot be merged (first: index "
+                         f"{int(np.flatnonzero(wrong)[0])})")
+    table = superob_boxes(box_deg)
+    box, count, sums, nused = _superob_device(ctx or _hip.context(), lat, lon, d, sig, var, table, True)
+    ids = np.flatnonzero(count)
+    W, Q, D, V, G = (sums[k][ids] for k in (_SO_W, _SO_Q, _SO_D, _SO_V, _SO_G))
+    P = sums[_SO_PX:_SO_PX + 3][:, ids]
+    norm = np.sqrt(P[0] * P[0] + P[1] * P[1] + P[2] * P[2])
+    if ids.size and not (norm > 0).all():
+        raise ValueError(f"superob: the members of a {table['box_deg']:g} degree box cancel each other's position; use smaller boxes")
+    dm = D / W
+    index = np.full(box.size, -1, dtype=np.int64)
+    lookup = np.full(table["nbox"], -1, dtype=np.int64)
+    lookup[ids] = np.arange(ids.size)
+    index[box >= 0] = lookup[box[box >= 0]]
+    return {"lat": np.rad2deg(np.arcsin(np.clip(P[2] / norm, -1.0, 1.0))), "lon": np.rad2deg(np.arctan2(P[1], P[0])),
+            "d": dm, "sigma_b": G / W, "var": ((1.0 - rho) * W + rho * Q * Q) / (W * W),
+            "spread": np.maximum(V / W - dm * dm, 0.0), "count": count[ids], "W": W, "box_id": ids, "box": box, "index": index,
+            "nobs": int(ids.size), "nobs_raw": int(nused), "box_deg": table["box_deg"], "rho": rho}
+
+
+_superob_fn = superob                                # (``OI_dense`` has an argument of that name)

@@ -103,6 +103,12 @@ class oisatgmi(object):
     #               (dense.qc_innovations) at the analysis' L -- under `auto` at the length fitted to all
     #               observations (oi_info["qc"]["corr_fit_before"]), and the analysis' length is then refitted to the kept ones;
     #               a rejected cell is analysed as unobserved; oi_info["qc"], oi_info["qc_rejected"]
+    #   superob     attribute `oi_superob`     | env OISAT_OI_SUPEROB     off (default) | <deg> | auto | auto:<max_obs>  (dense only;
+    #               tiled: ValueError; diag ignores it): the KEPT observations of one box of <deg> degrees (a roughly equal-area
+    #               grid) are merged into one superobservation ahead of the analysis, whose system then has one row per
+    #               non-empty box (dense.superob); auto: nothing while the observations number at most
+    #               max_obs (default 100 000), else the smallest box of 0.5, 0.75, 1, 1.5, 2, 3, 4, 6 degrees that leaves at
+    #               most max_obs; a box wider than L / 2 is reported in one line; oi_info["superob"]
     def _oi_setting(self, attr, env, default, cast=str):
         v = getattr(self, attr, None)
         if v is None:
@@ -157,6 +163,19 @@ class oisatgmi(object):
             raise ValueError(f"OISAT_OI_QC / oi_qc: expected off, buddy or buddy:<k_buddy> (a positive number), not {v!r}") from None
         return {"k_buddy": k}
 
+    @staticmethod
+    def _superob_setting(v):
+        """``OISAT_OI_SUPEROB`` / ``oi_superob`` -> ``None`` for ``off``, the box size in degrees (a float in (0, 180]) for
+        ``<deg>``, ``"auto:<max_obs>"`` for ``auto`` (max_obs = 100 000) / ``auto:<max_obs>`` (a positive integer); anything else
+        is a ``ValueError``."""
+        from . import dense
+        try:
+            box, max_obs = dense.superob_setting(v)
+        except ValueError:
+            raise ValueError(f"OISAT_OI_SUPEROB / oi_superob: expected off, <degrees> in (0, 180], auto or auto:<max_obs> "
+                             f"(a positive integer), not {v!r}") from None
+        return f"auto:{max_obs}" if box == "auto" else box
+
     def _oi_grid(self):
         lat, lon = getattr(self, "grid_lat", None), getattr(self, "grid_lon", None)
         if lat is None or lon is None:
@@ -196,6 +215,10 @@ class oisatgmi(object):
         if want_error == "mc" and mode == "tiled":
             raise ValueError("OISAT_OI_ERROR / oi_want_error = mc belongs to the dense mode; a tiled analysis has the exact error (1)")
         qc = self._oi_setting("oi_qc", "OISAT_OI_QC", "off", self._qc_setting)
+        superob = self._oi_setting("oi_superob", "OISAT_OI_SUPEROB", "off", self._superob_setting)
+        if superob is not None and mode == "tiled":
+            raise ValueError("OISAT_OI_SUPEROB / oi_superob belongs to the dense mode; the tiles take observation values, not "
+                             "innovations (off)")
         lat, lon = self._oi_grid()
         xa, y = np.asarray(xa), np.asarray(y)
         if lat.shape != xa.shape[:2] or lon.shape != xa.shape[:2]:
@@ -212,7 +235,8 @@ class oisatgmi(object):
         for tail in np.ndindex(*xa.shape[2:]):
             sl = (slice(None), slice(None)) + tail
             res, info = self._oi_spatial(mode, xa[sl], y[sl], np.asarray(Sa)[sl], np.asarray(So)[sl], lat, lon, L, tile,
-                                         unobserved, reg_index, want_error, corr=corr, nprobe=nprobe, qc=qc)
+                                         unobserved, reg_index, want_error, corr=corr, nprobe=nprobe, qc=qc,
+                                         superob=superob)
             for o, r in zip(outs, res):
                 o[sl] = r
             infos.append(info)
@@ -221,10 +245,11 @@ class oisatgmi(object):
 
     @staticmethod
     def _oi_spatial(mode, xa, y, Sa, So, lat, lon, L, tile, unobserved, reg_index, want_error, corr="gaussian", nprobe=256,
-                    qc=None):
+                    qc=None, superob=None):
         """One (ny, nx) Gaussian-B analysis -> ((Xb, AK, increment, error), info) in the reference's attribute order.  ``qc``
         (``_qc_setting``): not None = the innovations are checked first and the rejected cells analysed as unobserved, on a
-        copy of ``y``."""
+        copy of ``y``.  ``superob`` (``_superob_setting``, dense mode): not None = the kept observations are merged into
+        superobservations ahead of the analysis; the ``observed`` mask stays the raw one."""
         from . import dense
         from . import optimal_interpolation as oi_mod
         index, scale, curve, found = oi_mod.regularization_pick(Sa, So, reg_index)
@@ -261,7 +286,11 @@ class oisatgmi(object):
                     print("No correlation length could be fitted to the kept innovations; using 300 km")
         if mode == "dense":
             xb, inc, info = dense.OI_dense(xa, y, Sa, So, lat, lon, L, scale=scale, want_error=want_error, corr=corr,
-                                           nprobe=nprobe or 256)
+                                           nprobe=nprobe or 256, superob=superob)
+            so = info.get("superob")
+            if so is not None and so["box_deg"] * dense.KM_PER_DEG > 0.5 * L:      # (the knee_found convention: say so once)
+                print(f"The superobservation box of {so['box_deg']:g} degrees ({so['box_deg'] * dense.KM_PER_DEG:.0f} km) is wider "
+                      f"than half the correlation length ({L:g} km)")
         else:
             xb, inc, info = dense.OI_tiled(xa, y, Sa, So, lat, lon, L, tile_deg=tile, scale=scale, want_error=want_error, corr=corr)
         xb, inc = np.array(xb, dtype=np.float64), np.array(inc, dtype=np.float64)
@@ -292,6 +321,8 @@ class oisatgmi(object):
             out_info["corr_fit"] = corr_fit
         if qc_info is not None:
             out_info["qc"], out_info["qc_rejected"] = qc_info, qc_mask
+        if info.get("superob") is not None:
+            out_info["superob"] = info["superob"]
         return (xb, ak, inc, err), out_info
 
     def scaling_factor(self):
