@@ -640,7 +640,10 @@ int oisat_apply_increment_grid(oisat_ctx* h, int dtype, const double* gxyz, cons
  * residual of the gain solves that follow on this handle for systems of exactly m observations (oisat_gain_solve,
  * oisat_cov_residual) then takes its blocks of 64 rows from this list: a block has a small bounding sphere, and of the
  * latitude window's observations only those within the covariance's reach (2^-52) of it are visited -- the residual's rows
- * are otherwise 64 consecutive LATITUDES, all around the globe.  Same terms per row in the same order.  NULL / m = 0 clears.
+ * are otherwise 64 consecutive LATITUDES, all around the globe.  Same terms per row, staged in the same (latitude) order; a row
+ * adds them as four column phases of the list that survives its block's cull, so another list groups the same terms
+ * differently: residuals agree to rounding between lists, not to the bit (z of a refined solve: ~1e-15 of its largest entry
+ * measured between the identity, the reversal and a Morton order).  NULL / m = 0 clears.
  * ONE-SHOT: the next oisat_gain_solve / oisat_cov_residual call on the handle takes the list (if its m matches) and the handle
  * forgets it, whatever that call returns -- perm must stay valid until that call's work has run, and is never read after. */
 int oisat_set_obs_blocks(oisat_ctx* h, const int32_t* perm, int64_t m);
@@ -740,7 +743,8 @@ int oisat_set_task_graph(oisat_ctx* h, int mode);
  * to the other group.  Results do not depend on either. */
 int oisat_set_share(oisat_ctx* h, int wave_prio, int gemm_wg_per_cu);
 
-/* Relative residual |d - S z| / |d| at which oisat_gain_solve stops refining on this handle (default 1e-6; 0: never). */
+/* Relative residual |d - S z| / |d| at which oisat_gain_solve stops refining on this handle (default 1e-6; 0: never, short of
+ * a residual that is exactly zero -- a system of one observation behind a correction or two). */
 int oisat_set_refine_tol(oisat_ctx* h, double tol);
 
 /* ---- batched factorization: many independent systems in lock-step ---------------------------------------------------
@@ -768,7 +772,13 @@ int oisat_batch_potrf(oisat_ctx* h, int batch_id, int* info_host);
  * handle, behind oisat_batch_potrf, no host hand-over -- the gain solve and the increment of ALL members with one launch
  * per step: pad, forward / backward sweep (tickets over (member, block row), rows ascending, so the factors of all systems
  * are streamed level by level), float64 residual, convergence test (per member, oisat_set_refine_tol), at most `refine`
- * corrections, increment.  Per member the arithmetic is that of oisat_gain_solve + oisat_apply_increment.
+ * corrections, increment.  Per member the arithmetic is that of oisat_gain_solve + oisat_apply_increment(_grid) -- the same bits
+ * for the plain solve, for every solve that takes no correction, for a refined solve on compact blocks of rows, and always for
+ * the increment of a given z -- with one exception: where the residual runs on latitude rows (no perm for some member, or a
+ * correlation length beyond the compact blocks' range) oisat_gain_solve cuts the columns into slices and adds the slices' sums
+ * in a second launch, the batched launch does not; the residuals agree to rounding and a z behind a correction differs in its
+ * last bits (2.7e-16 of its largest entry measured).  Every array is in the caller's order, whatever order the library keeps
+ * the members in; a refused oisat_batch_set_solve / oisat_batch_set_grid leaves the batch as it was.
  * Arrays are indexed like those of oisat_batch_create.  work[i]: dev double[2 * roundup(m_i, 128)]; state[i]: dev, 256
  * zeroed bytes; observations in ascending latitude (olat[i]); xa[i] | inc[i]: where the analysis and the increment of
  * member i go (dtype of oisat_batch_solve). */
@@ -827,8 +837,9 @@ int oisat_comm_destroy(oisat_ctx* h);
  *                                   solve, no residual is formed -- never count): z is the best
  *                                   iterate, NOT within the tolerance -- the exact gain of optimal_interpolation.py:27 is what
  *                                   the 1e-5 bar is measured against, so a caller must not take such fields for converged ones
- *   OISAT_STATUS_UNCONVERGED_MEMBER the caller's index (oisat_batch_create order) of the first such batch member; -1 = none,
- *                                   or a single-system solve
+ *   OISAT_STATUS_UNCONVERGED_MEMBER the LOWEST caller's index (oisat_batch_create order) among the batch members that ended so
+ *                                   since the last clear -- a minimum, whichever member's workgroup reports first, in
+ *                                   oisat_batch_solve and oisat_batch_analyse alike; -1 = none, or a single-system solve
  *   OISAT_STATUS_DAG_TIMEOUTS       task-graph factorizations that ended on a time-out (bounded spins): incomplete factors
  * A caller must see zeros in words 0-3 and 5 before it trusts z / the analysis fields. */
 enum { OISAT_STATUS_NOTPD_COL = 0, OISAT_STATUS_NOTPD_BLOCKS = 1, OISAT_STATUS_TRSV_TIMEOUTS = 2, OISAT_STATUS_UNCONVERGED = 3,

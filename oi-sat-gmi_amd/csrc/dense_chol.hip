@@ -1295,6 +1295,18 @@ constexpr unsigned long long kTrsvEmpty = 0x7ff80bad7ff80badull;      // a quiet
 
 constexpr int kInfoUnconverged = 4, kInfoUnconvergedMember = 5, kInfoDagTimeouts = 6;     // status words (status_ws below)
 
+// OISAT_STATUS_UNCONVERGED_MEMBER: the LOWEST caller index among the batch members that ended unconverged since the last clear,
+// kept as index + 1 with 0 = none -- a minimum, so the word does not depend on which workgroup reports first.
+__device__ __forceinline__ void note_unconverged_member(int* word, int which) {
+    const int v = which + 1;
+    int old = atomicCAS(word, 0, v);
+    while (old != 0 && old > v) {
+        const int seen = atomicCAS(word, old, v);
+        if (seen == old) break;
+        old = seen;
+    }
+}
+
 // trsv_row and wait_payload may touch `error` ONLY: the task-graph launch hands them its own control block (DagCtl, whose
 // `error` sits at the same offset -- asserted at the cast, dense_dag.inc: dag_sweep_task); ticket and done are the kernels'.
 struct TrsvCtl {                         // zero when a sweep starts: zeroed at allocation, then by the last workgroup of every sweep
@@ -2101,7 +2113,7 @@ __global__ __launch_bounds__(1024) void resid_check_batched_kernel(const SolveMe
         if (sr[0] <= tol2 * st->dd) st->conv = 1;
         else if (final && tol2 > 0.0) {
             atomicAdd(&info[kInfoUnconverged], 1);
-            atomicCAS(&info[kInfoUnconvergedMember], 0, mb->which + 1);
+            note_unconverged_member(&info[kInfoUnconvergedMember], mb->which);
         }
     }
 }
@@ -3095,7 +3107,7 @@ extern "C" int oisat_batch_set_solve(oisat_ctx* h, int batch_id, int nmat, const
     ARG_CHECK(oxyz && osig && ovar && d && olat && z && work && state && gxyz && gsig && glat && n && xb && xa && inc);
     std::vector<SolveMember> mem(nmat);
     std::vector<int> ord;
-    bt->max_m = bt->max_n = bt->max_mp = 0;
+    int64_t max_m = 0, max_n = 0, max_mp = 0;               // (committed behind the checks: a refused call leaves the batch as it was)
     for (int i = 0; i < nmat; ++i) {                         // table order (largest first); order[i] = the caller's index
         const int c = bt->order[i];
         const BatchMat& bm = bt->table[i];
@@ -3108,10 +3120,11 @@ extern "C" int oisat_batch_set_solve(oisat_ctx* h, int batch_id, int nmat, const
         sm.gxyz = gxyz[c]; sm.gsig = gsig[c]; sm.glat = glat[c]; sm.n = n[c]; sm.xb = xb[c]; sm.xa = xa[c]; sm.inc = inc[c];
         sm.perm = nullptr;
         sm.which = c;
-        if (bm.m > bt->max_m) bt->max_m = bm.m;
-        if (n[c] > bt->max_n) bt->max_n = n[c];
-        if ((int64_t)bm.mpb * NB > bt->max_mp) bt->max_mp = (int64_t)bm.mpb * NB;
+        if (bm.m > max_m) max_m = bm.m;
+        if (n[c] > max_n) max_n = n[c];
+        if ((int64_t)bm.mpb * NB > max_mp) max_mp = (int64_t)bm.mpb * NB;
     }
+    bt->max_m = max_m; bt->max_n = max_n; bt->max_mp = max_mp;
     // ticket -> (member, step): steps ascending, members in table order inside a step (a prefix: sorted by block count)
     for (int k = 0; k < bt->max_mpb; ++k)
         for (int i = 0; i < nmat && bt->table[i].mpb > k; ++i) ord.push_back((i << 12) | k);
@@ -3142,10 +3155,13 @@ extern "C" int oisat_batch_set_grid(oisat_ctx* h, int batch_id, int nmat, const 
     ARG_CHECK(h && nx && batch_id >= 0 && batch_id < (int)h->batches.size() && h->batches[batch_id]);
     ChBatch* bt = h->batches[batch_id];
     ARG_CHECK(nmat == (int)bt->table.size() && bt->solve_dev != nullptr && (int)bt->solve_host.size() == nmat);
+    for (int i = 0; i < nmat; ++i) {                         // (every check before the first change: a refused call leaves the batch as it was)
+        const int64_t w = nx[bt->order[i]];
+        ARG_CHECK(w >= 0 && w < (int64_t)INT32_MAX && (w == 0 || bt->solve_host[i].n % w == 0));
+    }
     for (int i = 0; i < nmat; ++i) {
         const int64_t w = nx[bt->order[i]];
         SolveMember& sm = bt->solve_host[i];
-        ARG_CHECK(w >= 0 && w < (int64_t)INT32_MAX && (w == 0 || sm.n % w == 0));
         sm.nx = (int)w;
         sm.perm = perm ? perm[bt->order[i]] : nullptr;
     }
@@ -3156,8 +3172,9 @@ extern "C" int oisat_batch_set_grid(oisat_ctx* h, int batch_id, int nmat, const 
     return OISAT_OK;
 }
 
-// the gain solve + increment of every member, each launch covering all of them (same arithmetic per member as
-// oisat_gain_solve + oisat_apply_increment; same stopping rule, per member)
+// the gain solve + increment of every member, each launch covering all of them (per member the arithmetic and the bits of
+// oisat_gain_solve + oisat_apply_increment(_grid), except that the single call slices its latitude-row residual and this one does
+// not -- include/oisat.h; same stopping rule, per member)
 extern "C" int oisat_batch_solve(oisat_ctx* h, int batch_id, int dtype, double g, int refine) {
     ARG_CHECK(h && batch_id >= 0 && batch_id < (int)h->batches.size() && h->batches[batch_id]);
     ChBatch& bt = *h->batches[batch_id];
@@ -3229,7 +3246,7 @@ extern "C" int oisat_batch_analyse(oisat_ctx* h, int batch_id, int dtype, double
     if (int rc = status_ws(h, &info_dev, &base)) return rc;
     HIP_TRY(dense_kernel_attributes());
     const int nmem = (int)bt.table.size();
-    const double g2 = g * (double)kLog2e;
+    const double g2 = corr_scale2_f64(OISAT_CORR_GAUSSIAN, g);  // (what oisat_apply_increment_batched hands its kernel)
     DagSolve sv{};
     sv.mem = bt.solve_dev;
     sv.g = g;

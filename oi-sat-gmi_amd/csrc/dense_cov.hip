@@ -605,7 +605,7 @@ static int increment_launch(oisat_ctx* h, unsigned gx, unsigned gy, const double
     double far_chord;
     ARG_CHECK(far_chord_of(h->corr, g, &far_chord));
     OISAT_LAUNCH_CORR(h, "apply_increment", apply_increment_kernel, OISAT_TARGS(T, CELLS, BATCH), dim3(gx, gy), dim3(256), 0, gxyz, gsig, n, oxyz,
-                      osig, z, m, corr_scale2(h->corr, g), (const T*)xb, (T*)xa, (T*)inc, glat, olat, win, mem, nx, cut_chord_of(h->corr, g),
+                      osig, z, m, corr_scale2_f64(h->corr, g), (const T*)xb, (T*)xa, (T*)inc, glat, olat, win, mem, nx, cut_chord_of(h->corr, g),
                       far_chord);
     return OISAT_OK;
 }

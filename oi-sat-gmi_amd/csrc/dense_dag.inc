@@ -1015,7 +1015,7 @@ __device__ __forceinline__ bool dag_res_task(const DagSys& sy, const SolveMember
         if (conv) dag_st(&ss->conv, 1);
         else if (e == sv.refine && sv.tol2 > 0.0) {             // every allowed correction is in and the tolerance is not met
             atomicAdd(&info[kInfoUnconverged], 1);
-            atomicCAS(&info[kInfoUnconvergedMember], 0, mb.which + 1);
+            note_unconverged_member(&info[kInfoUnconvergedMember], mb.which);
         }
         *s_kav = conv ? 1 : 0;
     }

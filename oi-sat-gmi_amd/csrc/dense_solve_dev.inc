@@ -7,7 +7,7 @@
 #error "include dense_switches.h at file scope before dense_solve_dev.inc: this file is included inside a namespace and cannot"
 #endif
 
-constexpr float kLog2e = 1.4426950408889634f;
+constexpr float kLog2e = 1.4426950408889634f;                   // (a FLOAT: cut-off chords and fp32 scales only; the float64 increment takes kLog2eD)
 // A pair of points whose correlation is below 2^-kCutBits is left out of the float64 sums (residual, increment): 2^-52 is the
 // last bit of a term of correlation 1, and a sum's terms cancel to ~1/500 of their absolute sum at swath densities, so what
 // is dropped stays below 1e-12 of the result (rounds 1-3 used 2^-64: 19 % more pairs for nothing measurable).
@@ -45,6 +45,12 @@ constexpr double kLn2D = 0.6931471805599453;
 static inline double corr_scale2(int kind, double g) {
     if (kind == OISAT_CORR_SOAR) return 2.0 * g * (kLog2eD * kLog2eD);
     return kind == OISAT_CORR_GASPARI_COHN ? kGcZ2PerG * g : g * (double)kLog2e;
+}
+// ... and what the FLOAT64 increment takes: the Gaussian's g2 with log2 e in double.  (The scale above serves the fp32 kernels --
+// the build of S, the probes -- which round it to float; the increment took it too, and the float constant put its exponent
+// 1.3e-8 off: the increment of a correlation length 7e-9 longer.  The fp32 kernels keep theirs, so S keeps its bits.)
+static inline double corr_scale2_f64(int kind, double g) {
+    return kind == OISAT_CORR_GAUSSIAN ? g * kLog2eD : corr_scale2(kind, g);
 }
 static inline double corr_scale(int kind, double g) {
     if (kind == OISAT_CORR_SOAR) return 2.0 * g;
@@ -87,7 +93,7 @@ __device__ __forceinline__ float soar_f32(float a, float d2) {
     return __builtin_fmaf(sp, (float)kLn2D, 1.0f) * __builtin_amdgcn_exp2f(-sp);
 }
 
-__device__ __forceinline__ double exp2_neg(double x);
+template <bool FULL> __device__ __forceinline__ double exp2_neg(double x);
 // fp32 (the build of S, the rows of H B): a = g2 | kz2 | 2 g (log2 e)^2
 template <int KIND>
 __device__ __forceinline__ float corr_f32(float a, float d2) {
@@ -111,9 +117,9 @@ __device__ __forceinline__ double corr_f64_exp2(double a, double d2) {
     if (KIND == OISAT_CORR_GASPARI_COHN) return gc_f64(a, d2);
     if (KIND == OISAT_CORR_SOAR) {
         const double sp = sqrt(a * d2);
-        return __builtin_fma(sp, kLn2D, 1.0) * exp2_neg(-sp);
+        return __builtin_fma(sp, kLn2D, 1.0) * exp2_neg<true>(-sp);
     }
-    return exp2_neg(-a * d2);
+    return exp2_neg<false>(-a * d2);                                        // (the Gaussian: its far tier's share sets the precision)
 }
 
 // ---- host: the chord at which the correlation has fallen to 2^-bits -------------------------------------------------------
@@ -322,21 +328,57 @@ __device__ __forceinline__ double far_local(double v) { asm volatile("" : "+v"(v
 __device__ __forceinline__ int far_local(int v) { asm volatile("" : "+v"(v)); return v; }
 __device__ __forceinline__ int far_local_uniform(int v) { asm volatile("" : "+s"(v)); return v; }
 
-// 2^x for x <= 0 in double to 2e-10 relative: x = n + f, |f| <= 1/2, 2^f = e^(f ln 2) by a degree-8 polynomial, 2^n by ldexp
+// 2^x for x <= 0 in double: x = n + f, |f| <= 1/2, 2^f = 1 + f q(f) with q a polynomial in f (the Chebyshev interpolant of
+// (2^f - 1) / f on that range -- FULL: of 2^f itself, whose constant term rounds to 1 -- with ln 2 in its coefficients; exactly 1 at
+// f = 0), 2^n by ldexp.
+// FULL: q of degree 10, 2e-17 from 2^f with these rounded coefficients -- what is left is the rounding of the last Horner steps, one
+// unit in the last place.  SOAR takes it: nothing else in its increment is coarser than float64.
+// !FULL: q of degree 8, 3.7e-14 of a term at the most.  The Gaussian takes it: its far tier (kSolveFarBits) already allows a term
+// 2^-28 x 2e-5 = 7.5e-14 of a term of correlation 1, a far observation has the one error and a near one the other, and three more
+// fused multiply-adds per pair cost the benchmark's increment 0.6 ms of 5 (profiles/EXPERIMENTS.md, "Batched solve at the ABI").
+// (Up to the tests of the batched calls at the ABI both took the degree-8 Taylor polynomial of e^t in t = f ln 2, 2e-10 of a term:
+// 1e2 .. 4e4 times the float64 bound those tests hold the increment to.)
+// The far tier's share is the DEFAULT tier's: with OISAT_SOLVE_FAR_BITS = 0 (no tier) or a tighter one the near terms keep their 3.7e-14
+// and that argument no longer covers them -- the increment is then good to 3.7e-14 of a term, not to float64 rounding.
+// No clamp of x (there was one at -1100).  n is converted by v_cvt_i32_f64 itself, which SATURATES (the instruction's definition;
+// a C++ cast of an out-of-range double would be undefined): |x| = g2 |p - q|^2 passes 2^31 in the L -> 0 limit that the
+// element-wise parity tests drive the dense analysis to, n then becomes INT_MIN, and ldexp gives 0 for every n below -1075 -- far
+// pairs outside any window: 2^x = 0.  A NaN x (a NaN coordinate) gives NaN; under the clamp it gave 0.
+__device__ __forceinline__ int cvt_i32_saturating(double v) {
+    int i;
+    asm("v_cvt_i32_f64 %0, %1" : "=v"(i) : "v"(v));
+    return i;
+}
+template <bool FULL>
 __device__ __forceinline__ double exp2_neg(double x) {
-    x = fmax(x, -1100.0);                                                   // (far pairs outside any window: 2^x = 0)
     const double n = __builtin_rint(x);
-    const double t = (x - n) * 0.6931471805599453;                          // |t| <= 0.3466
-    double p = 2.48015873015873e-05;                                        // 1/8!
-    p = __builtin_fma(p, t, 1.984126984126984e-04);
-    p = __builtin_fma(p, t, 1.388888888888889e-03);
-    p = __builtin_fma(p, t, 8.333333333333333e-03);
-    p = __builtin_fma(p, t, 4.1666666666666664e-02);
-    p = __builtin_fma(p, t, 1.6666666666666666e-01);
-    p = __builtin_fma(p, t, 0.5);
-    p = __builtin_fma(p, t, 1.0);
-    p = __builtin_fma(p, t, 1.0);
-    return __builtin_ldexp(p, (int)n);
+    const double f = x - n;                                                 // |f| <= 1/2, exact
+    double p;
+    if (FULL) {
+        p = 4.4558179124523303e-10;
+        p = __builtin_fma(p, f, 7.07419430501114e-09);
+        p = __builtin_fma(p, f, 1.0178057087710788e-07);
+        p = __builtin_fma(p, f, 1.3215432535868937e-06);
+        p = __builtin_fma(p, f, 1.5252733841556817e-05);
+        p = __builtin_fma(p, f, 0.0001540353046372444);
+        p = __builtin_fma(p, f, 0.001333355814640647);
+        p = __builtin_fma(p, f, 0.009618129107587256);
+        p = __builtin_fma(p, f, 0.055504108664821625);
+        p = __builtin_fma(p, f, 0.24022650695910158);
+        p = __builtin_fma(p, f, 0.6931471805599453);
+    } else {
+        p = 1.0203121073417321e-07;
+        p = __builtin_fma(p, f, 1.3255224894585756e-06);
+        p = __builtin_fma(p, f, 1.5252686846230125e-05);
+        p = __builtin_fma(p, f, 0.00015403455852394153);
+        p = __builtin_fma(p, f, 0.001333355817904315);
+        p = __builtin_fma(p, f, 0.009618129159402621);
+        p = __builtin_fma(p, f, 0.055504108664760424);
+        p = __builtin_fma(p, f, 0.2402265069581299);
+        p = __builtin_fma(p, f, 0.6931471805599453);
+    }
+    p = __builtin_fma(p, f, 1.0);
+    return __builtin_ldexp(p, cvt_i32_saturating(n));
 }
 
 
@@ -745,7 +787,7 @@ __device__ __forceinline__ void increment_patch(const double* __restrict__ gxyz,
 #pragma unroll
                 for (int q = 0; q < CELLS; ++q) {
                     const double dx = px[q] - oxy.x, dy = py[q] - oxy.y, dz = pz[q] - ozw.x;
-                    // C = 2^x, x = -g2 |p - q|^2, in DOUBLE (exp2_neg, 2e-10).  Rounds 1-2 used v_exp_f32: good to 1 ulp = 1.2e-7 of
+                    // C = 2^x, x = -g2 |p - q|^2, in DOUBLE (exp2_neg, 3.7e-14).  Rounds 1-2 used v_exp_f32: good to 1 ulp = 1.2e-7 of
                     // the term, but the terms cancel (sum|term| is several hundred times the field at swath densities, more at
                     // larger L) and that alone put the fields 2.5e-6 of their scale off at 720x1440 / 1e5 obs, L = 300 km, and
                     // 1.3e-5 -- outside the 1e-5 bar -- at 360x720 / 1e4 gridded obs, L = 500 km; with this: 4e-8.  Twice the

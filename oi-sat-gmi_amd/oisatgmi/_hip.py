@@ -456,7 +456,7 @@ class Context:
         if st["trsv_timeouts"]:
             msgs.append(f"{st['trsv_timeouts']} triangular-solve workgroup(s) gave up waiting: z holds NaN fill")
         if st["unconverged"]:
-            who = f", first: batch member {st['unconverged_member']}" if st["unconverged_member"] >= 0 else ""
+            who = f", first: batch member {st['unconverged_member']} (the lowest index among them)" if st["unconverged_member"] >= 0 else ""
             msgs.append(f"{st['unconverged']} gain solve(s) ended above the refinement tolerance after every allowed round{who} "
                         "(raise `refine`, or the observation error / lower the correlation length: the fp32 factor is a poor preconditioner)")
         if msgs:
