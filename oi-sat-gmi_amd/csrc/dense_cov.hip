@@ -667,7 +667,7 @@ extern "C" int oisat_probe_spread(oisat_ctx* h, const double* gxyz, const double
     return OISAT_OK;
 }
 
-// ---- batched forms (oisat_batch_solve, dense_chol.hip): blockIdx.y = member of the device table --------------------------
+// ---- batched forms (oisat_batch_solve, dense_solve.hip): blockIdx.y = member of the device table --------------------------
 int oisat_cov_residual_batched(oisat_ctx* h, const SolveMember* mem_dev, const std::vector<SolveMember>& mem_host, int64_t max_m, double g) {
     const int kind = h->corr;
     const double win = lat_window_deg(kind, g);

@@ -1,7 +1,7 @@
 // Task-graph Cholesky: the whole factorization of one system -- or of a month's fifty -- as ONE persistent launch.
-// The device half and dag_launch.  (Included by dense_chol.hip inside its anonymous namespace; uses its tile constants, LDS-DMA
-// K-loop and diagonal-block waves.  The launch's types -- DagSys, DagCtl, DagSolve, the ticket kinds -- are in dense_internal.h; the
-// plan and the ticket order, host code, in dense_dag_plan.hip.)
+// The device half.  (Included by dense_dag.hip alone, inside its anonymous namespace, behind dense_tile.inc, dense_kloop.inc (LDS-DMA
+// K-loop), dense_diag.inc (diagonal-block waves), dense_trsv.inc (sweep rows) and dense_solve_dev.inc (residual, increment).  The launch's
+// types are in dense_internal.h, dag_launch in dense_dag.hip, the plan and the ticket order, host code, in dense_dag_plan.hip.)
 //
 // Why: for 4,000-18,000 observations the recursive schedule is a chain of ~3 dependent launches per diagonal block (diagonal
 // block 19 us on ONE workgroup, panel 9 us, rank-128 update 12 us: 3.4 of the 8 ms of a 10,000-observation analysis) next to
@@ -148,8 +148,8 @@ __device__ __forceinline__ void dag_split8(const float4& a, const float4& b, dag
 // segments poll instead, with the chain's images converted from its LDS image under the rank-128 update's MFMAs.  The chain's
 // panel step went back from 15.3 to 12.8 us, but its rank-128 update rose from 7.8 to 10.3 us and its diagonal block from 22.9
 // to 24.8 us: the headline step was the same to 0.1 ms, for a fourth progress array and a second writer.
-constexpr int64_t kShTile = 65536;                              // bytes of a shadow tile
-constexpr int kShPlane = 32768, kShGroup = 4096;                // ... of a plane, of a 16-column group of a plane
+// (kShTile, kShPlane, kShGroup -- bytes of a shadow tile, of a plane, of a 16-column group of a plane -- are in dense_internal.h:
+// the host sizes the shadow and reads a tile back with them, dense_chol.hip)
 constexpr int kShUnit = 16384;                                  // bytes of a unit in LDS; the workgroup's image holds four
 // The segment's RING: kShRing stages of 4 / kShRing units each, kShAhead stages' DMAs in flight while one is consumed.
 // 2 | 1: one 32 KiB stage ahead, every wait a vmcnt(0) -- the default.  4 | 3: three half-size stages ahead, counted waits;
@@ -874,7 +874,7 @@ __device__ __forceinline__ bool dag_after_sweeps(const DagSys& sy, const SolveMe
 }
 
 // The sweep tasks hand trsv_row this launch's control block as a TrsvCtl: it reads and raises `error`, nothing else
-// (dense_chol.hip: TrsvCtl), and that word is the same one in both blocks.
+// (dense_trsv.inc: TrsvCtl), and that word is the same one in both blocks.
 static_assert(offsetof(DagCtl, error) == offsetof(TrsvCtl, error) && sizeof(DagCtl::error) == sizeof(TrsvCtl::error),
               "trsv_row's error word is the launch's");
 
@@ -1270,67 +1270,3 @@ __global__ __launch_bounds__(256, 2) void potrf_dag_kernel(const DagSys* __restr
 #undef DAG_MFMA4                                                // (defined in dense_kloop.inc for dag_seg; dag_self_product above is their other user)
 #undef DAG_MFMA16
 
-// ---- host: the launch (its plan: dense_dag_plan.hip) ---------------------------------------------------------------------
-// OISAT_DAG_TRACE=file (profiling aid): the launch is followed by a synchronisation and its stamps are written to `file`:
-// int32 ntasks, chain_rows; int32[ntasks][4] tasks; int64[ntasks][4] ticket stamps; int64[chain_rows][8] chain stamps (100 MHz)
-// dag_timeouts: the handle's task-graph time-out word (status slot 4, word 6)
-int dag_launch(oisat_ctx* h, DagPlan& p, int* info_dev, unsigned* dag_timeouts, const DagSolve* solve = nullptr) {
-    const int slots = dag_slots(h);
-    if (!dag_fits(p.max_wave_chains, slots)) {                  // (callers check dag_fits before they make a plan; a handle's stream may have changed since)
-        oisat_set_error("task-graph factorization: %d chains of one wave on %d resident workgroups would not drain", p.max_wave_chains, slots);
-        return OISAT_EINVAL;
-    }
-    if ((solve != nullptr) != (p.solve_refine >= 0) || (solve && solve->refine != p.solve_refine)) {
-        oisat_set_error("task-graph launch: plan and solve arguments do not belong together");
-        return OISAT_EINVAL;
-    }
-    const int grid = p.ntasks < slots ? p.ntasks : slots;
-    const char* trace_file = dag_trace_file();
-    const size_t trace_words = 4 * ((size_t)p.ntasks + (size_t)p.qcap) + 8 * (size_t)p.chain_rows + 8 * (size_t)grid;
-    if (trace_file && !p.trace_dev) HIP_TRY(hipMalloc((void**)&p.trace_dev, sizeof(long long) * trace_words));       // (grid is a plan's constant)
-    if (trace_file) HIP_TRY(hipMemsetAsync(p.trace_dev, 0, sizeof(long long) * trace_words, h->stream));
-    int flags = 0;
-#ifdef OISAT_TEST_HOOKS
-    flags = dag_test_flags();
-#endif
-    if (p.fwd_only && (p.nsys != 1 || !solve || !solve->fwd_rhs || !solve->fwd_sol || solve->nsys != 1)) {
-        oisat_set_error("task-graph launch: the forward-sweep plan takes one system and its two work vectors");
-        return OISAT_EINVAL;
-    }
-    if (solve) {
-        if (solve->queue != p.queue_dev || solve->qcap != (int)p.qcap || solve->qcap0 != (int)p.qcap0) {
-            oisat_set_error("task-graph launch: the solve arguments carry another plan's ready queue");
-            return OISAT_EINVAL;
-        }
-        if (p.fwd_only) {
-            OISAT_LAUNCH(h, "potrf_dag", potrf_dag_kernel<DAG_SOLVE_FWD>, dim3((unsigned)grid), dim3(256), 0, (const DagSys*)p.sys_dev,
-                         (const int4*)p.tasks_dev, p.ntasks, p.ctl_dev, info_dev, dag_timeouts, p.state_dev, p.state_words, p.reserve_chains, flags,
-                         trace_file ? p.trace_dev : (long long*)nullptr, p.chain_rows, *solve);
-        } else {
-            OISAT_LAUNCH(h, "analyse_dag", potrf_dag_kernel<DAG_SOLVE_ALL>, dim3((unsigned)grid), dim3(256), 0, (const DagSys*)p.sys_dev,
-                         (const int4*)p.tasks_dev, p.ntasks, p.ctl_dev, info_dev, dag_timeouts, p.state_dev, p.state_words, p.reserve_chains, flags,
-                         trace_file ? p.trace_dev : (long long*)nullptr, p.chain_rows, *solve);
-        }
-    } else {
-        OISAT_LAUNCH(h, "potrf_dag", potrf_dag_kernel<DAG_SOLVE_NONE>, dim3((unsigned)grid), dim3(256), 0, (const DagSys*)p.sys_dev,
-                     (const int4*)p.tasks_dev, p.ntasks, p.ctl_dev, info_dev, dag_timeouts, p.state_dev, p.state_words, p.reserve_chains, flags,
-                     trace_file ? p.trace_dev : (long long*)nullptr, p.chain_rows, DagSolve{});
-    }
-    if (trace_file) {
-        std::vector<long long> host(trace_words);
-        HIP_TRY(hipStreamSynchronize(h->stream));
-        HIP_TRY(hipMemcpy(host.data(), p.trace_dev, sizeof(long long) * trace_words, hipMemcpyDeviceToHost));
-        if (FILE* f = fopen(trace_file, "wb")) {
-            const int hdr[2] = {p.ntasks + (int)p.qcap, p.chain_rows + grid};  // (rows ntasks .. are the ready tasks' stamps: their task is in word 3; behind the chains' rows one row per workgroup)
-            fwrite(hdr, sizeof(int), 2, f);
-            fwrite(p.tasks_host.data(), sizeof(int4), p.tasks_host.size(), f);
-            {
-                const std::vector<int4> pad((size_t)p.qcap, int4{-1, 0, 0, 0});
-                fwrite(pad.data(), sizeof(int4), pad.size(), f);
-            }
-            fwrite(host.data(), sizeof(long long), host.size(), f);
-            fclose(f);
-        }
-    }
-    return OISAT_OK;
-}

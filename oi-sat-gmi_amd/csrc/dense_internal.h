@@ -1,6 +1,11 @@
 // Internal to the dense solver (the dense_*.hip units of liboisat_hip.so): what crosses a file is declared here, once, in
-// namespace oisat_dense, so that the library exports no bare C++ names.  The run-time switches are in dense_switches.h; what
-// dense_cov.hip offers dense_chol.hip is in oisat_common.h.
+// namespace oisat_dense, so that the library exports no bare C++ names.  Only host functions cross: a kernel is launched by the unit
+// that holds it, and device code that two units need is a *.inc both take textually.  The run-time switches are in
+// dense_switches.h; what dense_cov.hip offers dense_solve.hip is in oisat_common.h.
+// The units: dense_gemm.hip (the four fp32 GEMMs), dense_dag.hip (the task-graph kernel of dense_dag.inc, the diagonal-block kernel
+// and their launches; the only unit with test hooks), dense_chol.hip (leaf pairs and the factorization schedules), dense_solve.hip
+// (sweeps, gain solve, status words, the oisat_batch_* API), dense_post.hip (posterior diagnostics, probes), dense_cov.hip, and the
+// host-only dense_tables.hip and dense_dag_plan.hip.
 #pragma once
 
 #include "oisat_common.h"
@@ -43,6 +48,8 @@ struct DagSys {                  // one system of a task-graph launch (device ta
     const int64_t* shrow;        // int64[nb]: rowoff[r] - first[r] (DagPlan::shrow_dev; rowoff: oisat_factor_shadow_layout)
     int shuse;                   // who READS it: 1 = the far stretch, 2 = the middle stretch (OISAT_FACTOR_SHADOW); the writers always store
 };
+constexpr int64_t kShTile = 65536;                              // bytes of a shadow tile
+constexpr int kShPlane = 32768, kShGroup = 4096;                // ... of a plane, of a 16-column group of a plane
 
 struct DagCtl {                  // zero when a launch starts
     int ticket, error, gone, pad;
@@ -129,6 +136,18 @@ struct DagSolveShape {                                          // refine < 0: a
 static inline bool dag_fits(int max_wave_chains, int slots) { return 4 * max_wave_chains <= slots; }
 static inline int dag_slots(const oisat_ctx* h) { return 2 * (h->cu_count > 0 ? h->cu_count : 256); }
 
+// Which factorizations run as a task graph: every system / batch of at least three block rows (below that there is nothing to
+// overlap), unless the handle says otherwise (oisat_set_task_graph) or the environment does (OISAT_DAG=0 | 1: the parity tests
+// compare the two schedules inside one process, so it is read at every call).  Measured against the recursion
+// (factorization alone, TFLOP/s): 10,000 observations 91.9 vs 53.9, 20,000: 126 vs 94, 30,000: 135 vs 115, 50,000: 138 vs
+// 128, 100,000: 140.8 vs 137.4 -- the task graph wins at every size.  A batch of more than 1024 systems keeps the lock-step
+// recursion, and so does any launch whose chains would not leave room for the tasks they wait for (dag_fits).
+static inline bool dag_wanted(const oisat_ctx* h, int64_t max_blocks, int nsys) {
+    const int mode = h->dag_mode >= 0 ? h->dag_mode : dag_env_mode();
+    if (mode == 0 || nsys > 1024) return false;
+    return max_blocks >= (mode == 1 ? 2 : 3);
+}
+
 constexpr double kDagEnvLeadFar = 0.3;                          // the ticket lead of a list with a far stretch (dag_task_order, dense_dag_plan.hip)
 constexpr int kDagEnvMaxBlocks = 1024;                          // an enveloped ticket has ten bits for a block column (dag_task_order)
 
@@ -146,5 +165,54 @@ int dag_plan_refill(DagPlan& p, const DagBands& bands, hipStream_t stream);
 bool envelope_table_ok(const int32_t* first, int64_t nb);
 bool far_table_ok(const std::vector<int32_t>& far, const int32_t* first, int64_t nb);
 bool mid_table_ok(const std::vector<int32_t>& mid, const std::vector<int32_t>& far, const int32_t* first, int64_t nb);
+
+// ---- the recursion's tree, the GEMM launches, the status words -----------------------------------------------------------
+// One launch of a batched GEMM kernel (dense_gemm.hip: batch_operands derives a member's operands from its table entry and the node)
+struct BatchArgs {
+    const BatchMat* mats;        // nullptr: not a batched launch
+    int kind;                    // 0: trailing update of node (b0, mid, b1);  1: TRSM of the panel below diagonal block b0
+    int b0, mid, b1;
+    const int* cum = nullptr;    // persistent kernel: prefix sums of the members' tile counts at this node (cum[cnt] = total):
+    int cnt = 0, total = 0;      // virtual ids 0 .. total-1 are exactly the real tiles, member = the w with cum[w] <= id < cum[w+1]
+    int prio = 0;                // wave priority of this group's kernels (oisat_set_share): where the waves of two groups share a
+};                               // SIMD the arbiter serves the higher one first -- the group with the longest dependent chain
+
+// Leaves of the recursion are PAIRS of block columns (pair_mid_kernel / pair_panel_kernel) where the leaf-level launches
+// are bound by HBM traffic, i.e. in lock-step batches of many systems (>= OISAT_LEAF_PAIRS_MIN members, default 8; 0 = never):
+// a month's 48 tiles factor in 23.6 ms instead of 25.6.  For one system or a couple of polar caps the same launches are
+// latency-bound and the extra one-workgroup step between the two diagonal blocks costs more than the saved pass
+// (10,000 observations: 8.6 ms per analysis against 8.0), so those keep single-block leaves.
+static const int kLeafPairsMin = 8;                     // lock-step batches of at least this many systems take leaf PAIRS (fewer: 8.6 vs 8.0 ms at 1e4 observations)
+static const bool kSinglePairs = false;                  // (single systems keep single-block leaves)
+// split point of the node [b0, b1): the left part gets ceil(half), rounded up to an even number of blocks when leaves are
+// pairs (so that the tree ends in pairs wherever it can); the one rule of potrf_rec, potrf_rec_batched and the tile tables
+static inline int64_t split_mid(int64_t b0, int64_t b1, bool pairs) {
+    const int64_t n = b1 - b0;
+    int64_t left = (n + 1) / 2;
+    if (pairs && n > 2 && (left & 1)) ++left;
+    if (left >= n) left = n - 1;
+    return b0 + left;
+}
+
+constexpr int kInfoUnconverged = 4, kInfoUnconvergedMember = 5, kInfoDagTimeouts = 6;     // status words (status_ws, dense_solve.hip)
+
+// dense_gemm.hip
+int launch_gemm(oisat_ctx* h, const char* name, float* C, int64_t ldc, const float* A, int64_t lda, const float* B, int64_t ldb,
+                int64_t M, int64_t N, int K, int mode, int lower);
+int launch_gemm_batched(oisat_ctx* h, const char* name, const ChBatch& bt, BatchArgs ba, int K, int mode, int lower);
+void build_cum_tables(ChBatch* bt, std::vector<int>& host);
+// dense_dag.hip: the task-graph launch, and the diagonal-block kernel for the other schedules (nsys workgroups: one system, or the
+// first nsys of the table `mats`)
+int dag_launch(oisat_ctx* h, DagPlan& p, int* info_dev, unsigned* dag_timeouts, const DagSolve* solve = nullptr);
+int launch_potrf_diag(oisat_ctx* h, unsigned nsys, float* S, int64_t ld, int64_t k0, float* tinv, int* info_dev, int block_index,
+                      const BatchMat* mats, int prio);
+// dense_chol.hip, for the batch API
+int potrf_rec_batched(oisat_ctx* h, const ChBatch& bt, int b0, int b1, int* info_dev);
+int pad_identity_batched(oisat_ctx* h, const ChBatch& bt);
+// dense_solve.hip: the handle's status words and solve state, the sweep kernels' attributes, the "copy_pad" launch in front of a solve
+int status_ws(oisat_ctx* h, int** info_dev, char** trsv_base);
+SolveState* solve_state(oisat_ctx* h);
+hipError_t dense_kernel_attributes();
+int solve_prep(oisat_ctx* h, const double* src, int64_t m, int64_t mp, double* rhs, double* fwd, SolveState* st);
 
 }  // namespace oisat_dense

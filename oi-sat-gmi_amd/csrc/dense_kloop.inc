@@ -1,7 +1,7 @@
 // The fp32 K-loop of the 128x128 tile GEMM as a function over a K-segment, for the task-graph launch (dense_dag.inc).
 // gemm_nt_big_kernel keeps its own copy of the loop (OISAT_DMA / OISAT_FRAG / OISAT_MFMA16): calling dag_seg there measured
 // +2.5 % at K = 2048 (profiles/EXPERIMENTS.md, "One low-precision K-segment").  The image layout is the same in both.
-// (Included by dense_chol.hip inside its anonymous namespace; uses its tile constants.)
+// (Included by dense_dag.hip alone, inside its anonymous namespace; expects dense_tile.inc before it.)
 
 struct DagLane {                 // a thread's fixed coordinates in the 128x128 tile GEMM
     int lane, wid, wr, wc, rl, lc, frow, fh, sw, arow, brow;

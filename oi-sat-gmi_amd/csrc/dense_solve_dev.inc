@@ -1,7 +1,8 @@
 // Device code shared by the solve-phase kernels (dense_cov.hip) and the task-graph launch (dense_dag.inc, which runs a
 // system's residuals and increment as tasks of the same persistent launch that factors it): the latitude window, the
 // bounding-sphere cull, and the bodies of the float64 residual and of the increment as functions of a block index and a
-// carve-out of the caller's LDS.  Included inside each translation unit's anonymous namespace; no kernels here.
+// carve-out of the caller's LDS.  Included inside the anonymous namespace of dense_cov.hip, dense_dag.hip, dense_solve.hip and dense_tables.hip
+// (host rules), dense_post.hip and buddy.hip (correlation functions); expects dense_switches.h at file scope before it; no kernels here.
 // (No reference counterpart: the dense analysis is the north-star extension, SURVEY.md section 8 a-ext.)
 #ifndef OISAT_DENSE_SWITCHES_H
 #error "include dense_switches.h at file scope before dense_solve_dev.inc: this file is included inside a namespace and cannot"
@@ -612,7 +613,7 @@ __device__ __forceinline__ void resid_compact_block(const double* __restrict__ o
 constexpr int kUpdStage = (int)(2 * sizeof(double2) * kStage / (4 * sizeof(float)));
 // the reported residual may be this form: it is within kResidUpdateC |r_prev| of the float64 one (8x the largest error measured
 // on the protocol's months and the tests' geometries, rounded up to a power of two: profiles/EXPERIMENTS.md, "The verification
-// residual as an update"); the stopping test charges that bound (resid_update_check_kernel, dense_chol.hip)
+// residual as an update"); the stopping test charges that bound (resid_update_check_kernel, dense_solve.hip)
 constexpr double kResidUpdateC = OISAT_RESID_UPDATE_C;         // (include/oisat.h documents it to callers)
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ void resid_update_block(const double* __restrict__ oxyz, const double* __restrict__ osig,

@@ -5,23 +5,23 @@
 // all of them (grep tests/ for the name).
 //
 //   variable                   values                               reader                                        tests, among others
-//   OISAT_DAG                  0 | 1 (atoi)                         dag_wanted (dense_chol.hip)                   test_gpu_readers_abi
+//   OISAT_DAG                  0 | 1 (atoi)                         dag_wanted (dense_internal.h)                 test_gpu_readers_abi
 //   OISAT_POTRF                recursive | lookahead[:<blocks>]     potrf_impl (dense_chol.hip)                   test_gpu_parity, test_gpu_far_band
 //   OISAT_FWD_IN_LAUNCH        0 = off (atoi)                       potrf_impl (dense_chol.hip)                   test_gpu_fwd_in_launch
 //   OISAT_FACTOR_SHADOW        0 | 1 | far | mid                    potrf_impl (dense_chol.hip)                   test_gpu_factor_shadow, test_gpu_seg_pipeline
-//   OISAT_DAG_TRACE            <file>                               dag_launch (dense_dag.inc)                    - (tools/dag_trace.py)
-//   OISAT_DAG_FLAGS            <int> (atoi), hooks build only       dag_launch (dense_dag.inc)                    test_gpu_dag
+//   OISAT_DAG_TRACE            <file>                               dag_launch (dense_dag.hip)                    - (tools/dag_trace.py)
+//   OISAT_DAG_FLAGS            <int> (atoi), hooks build only       dag_launch (dense_dag.hip)                    test_gpu_dag
 //   OISAT_DAG_ORDER_LEAD_FAR   <number in [0, 1)>                   oisat_dag_task_order_env (dense_dag_plan.hip) test_dag_sched_model_cpu
 //   OISAT_ENVELOPE             0 = off (atoi)                       the enveloped entry points (dense_chol.hip,   test_gpu_envelope, test_far_band_cpu
 //                                                                   dense_cov.hip), stretch_table (dense_tables.hip)
 //   OISAT_FACTOR_CUT_BITS      <number in [1, 52]>                  oisat_factor_envelope_corr (dense_tables.hip) test_factor_envelope_cpu
 //   OISAT_FACTOR_FAR_BITS      0 | <number in [1, 52]>              oisat_factor_far_corr (dense_tables.hip)      test_far_band_cpu
 //   OISAT_FACTOR_MID_BITS      0 | <number in [1, 52]>              oisat_factor_mid_corr (dense_tables.hip)      test_mid_band_cpu
-//   OISAT_TRSV_TWO_TILES       0 | 1                                trsv_launch_shape (dense_chol.hip)            test_gpu_sweep_tiles
-//   OISAT_TRSV_MAX_WGS         <integer >= 1>                       trsv_launch_shape (dense_chol.hip)            test_gpu_sweep_tiles
-//   OISAT_RESID_UPDATE         0 | 1                                oisat_gain_solve (dense_chol.hip)             test_gpu_resid_update
+//   OISAT_TRSV_TWO_TILES       0 | 1                                trsv_launch_shape (dense_solve.hip)           test_gpu_sweep_tiles
+//   OISAT_TRSV_MAX_WGS         <integer >= 1>                       trsv_launch_shape (dense_solve.hip)           test_gpu_sweep_tiles
+//   OISAT_RESID_UPDATE         0 | 1                                oisat_gain_solve (dense_solve.hip)            test_gpu_resid_update
 //   OISAT_SOLVE_FAR_BITS       <number in [0, 52]>                  far_chord_of (dense_solve_dev.inc)            test_solve_tiers_cpu, test_gpu_solve_tiers
-//   OISAT_PROF_DETAIL          0 | 1 (atoi), read once              launch_gemm(_batched) (dense_chol.hip)        - (profiling aid)
+//   OISAT_PROF_DETAIL          0 | 1 (atoi), read once              launch_gemm(_batched) (dense_gemm.hip)        - (profiling aid)
 #pragma once
 #define OISAT_DENSE_SWITCHES_H                                  // (dense_solve_dev.inc, included inside a namespace, checks for it)
 

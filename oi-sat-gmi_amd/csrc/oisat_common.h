@@ -28,6 +28,10 @@ struct ProfPending {
     hipEvent_t a, b;
 };
 
+namespace oisat_dense {
+struct DagPlan;                  // a task-graph plan (dense_internal.h), opaque outside the dense_*.hip units
+}
+
 struct ChFactor {                // what the triangular solves need besides L: the inverted diagonal blocks
     const float* S = nullptr;
     int64_t m = 0, mp = 0, ld = 0;
@@ -96,13 +100,13 @@ struct ChBatch {                 // matrices factored in lock-step by oisat_batc
     int ord_total = 0;
     int64_t max_m = 0, max_n = 0, max_mp = 0;
     bool pairs = false;          // leaves of its recursion are pairs of block columns (many members: the leaf launches are HBM-bound)
-    void* dag = nullptr;         // task-graph plan of the batch (dense_internal.h: DagPlan), owned
-    void* dag_solve = nullptr;   // ... of the batch's factorization + solve phase in one launch (oisat_batch_analyse), made on first use
+    oisat_dense::DagPlan* dag = nullptr;         // task-graph plan of the batch, owned
+    oisat_dense::DagPlan* dag_solve = nullptr;   // ... of the batch's factorization + solve phase in one launch (oisat_batch_analyse), made on first use
     int dag_solve_refine = -1, dag_solve_cells = 0;             // what that plan was made for
 };
 
 struct DagSingle {               // a cached single-system task-graph plan (oisat_potrf)
-    void* plan = nullptr;
+    oisat_dense::DagPlan* plan = nullptr;
     const float* S = nullptr;
     const float* tinv = nullptr;
     int64_t ld = 0, mpb = 0;
@@ -129,7 +133,7 @@ struct oisat_ctx {
     double scales_host[OISAT_MAX_SCALES] = {0};
     int scales_n = 0;
     const void* scales_dev = nullptr;
-    // the factor left by the last oisat_potrf on this handle (dense_chol.hip)
+    // the factor left by the last oisat_potrf on this handle (dense_chol.hip; its readers: dense_solve.hip, dense_post.hip)
     ChFactor factor;
     bool small_tiles = true;            // gemm_nt: 64x64 tiles for launches of <= 700 128x128 tiles (latency-bound ones)
     double refine_tol = 1e-6;           // oisat_set_refine_tol: relative residual at which the gain solve stops refining
@@ -182,8 +186,8 @@ struct oisat_ctx {
 // workspace slot `slot` of at least `bytes` (grow-only); returns nullptr + error on failure
 void* oisat_ws(oisat_ctx* h, int slot, size_t bytes);
 void* oisat_pinned(oisat_ctx* h, size_t bytes);
-void oisat_dag_plan_release(void* plan);                // dense_dag_plan.hip: frees a task-graph plan (nullptr allowed)
-// dense_cov.hip, for dense_chol.hip: the residual and increment forms of the gain solve and of the batch API
+void oisat_dag_plan_release(void* plan);                // dense_dag_plan.hip: frees a task-graph plan (nullptr allowed; void*: oisat_core.hip calls it too)
+// dense_cov.hip, for dense_solve.hip: the residual and increment forms of the gain solve and of the batch API
 const int* oisat_take_obs_perm(oisat_ctx* h, int64_t m);
 int oisat_cov_residual_if(oisat_ctx* h, const double* oxyz, const double* osig, const double* ovar, int64_t m, double g,
                           const double* d, const double* z, double* r_out, const double* olat_sorted, const int* converged_dev,

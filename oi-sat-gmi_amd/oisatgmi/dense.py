@@ -14,7 +14,8 @@ observation per cell: there C = I and K_ii = s Sa_i / (s Sa_i + So_i) (:27).  Th
 reference implementation of the dense form, so its parity is pinned only in that limit; away from
 it the check is the float64 restatement in ``oracle/`` ("parity unpinned").
 
-Pipeline (all in HBM, csrc/dense_cov.hip + csrc/dense_chol.hip; host tables and plans: dense_tables.hip, dense_dag_plan.hip):
+Pipeline (all in HBM; csrc/dense_cov.hip, dense_chol.hip with dense_gemm.hip and dense_dag.hip (factorization), dense_solve.hip,
+dense_post.hip; host tables and plans: dense_tables.hip, dense_dag_plan.hip):
 ``oisat_innovation`` -> ``oisat_cov_build`` (S, fp32) -> ``oisat_potrf`` (MFMA fp32 Cholesky) ->
 ``oisat_gain_solve`` (triangular solves + float64-residual refinement) -> ``oisat_apply_increment``
 (B H^T z generated on the fly, never stored).  ``DenseAnalysis.run()`` owns the latitude sort of its observations and
