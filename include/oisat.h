@@ -453,6 +453,23 @@ int oisat_factor_far(const double* lat_sorted, int64_t m, double g, const int32_
  * table set for the same call.  Without it, and in every other factorization, there is no middle stretch.  The ticket words
  * of oisat_dag_task_order_env do not carry it: the launch reads the table itself. */
 int oisat_factor_mid(const double* lat_sorted, int64_t m, double g, const int32_t* first, const int32_t* far, int32_t* mid_out);
+/* The near stretch of the factor's K-loops (csrc/dense_tables.hip: kFactorNearBits).
+ * oisat_factor_near (host only): near_out[i], mid[i] <= near_out[i] <= i, = the first block column of block row i that is NOT
+ * near.  The enveloped task graph runs the K-blocks mid[i] <= k < near_out[i] of the row's tiles as three-way split bf16
+ * products: each operand a = hi + mid + lo, hi = bf16(a), mid = bf16(a - hi), lo = bf16(a - hi - mid) (nearest even; both
+ * differences are exact), and a b^T becomes the eight products of those parts without lo lo^T, smallest first, with fp32
+ * accumulation: the split is exact and what is dropped is at most 2^-32 of a term.  first and mid are the tables of oisat_factor_envelope and oisat_factor_mid (mid == far == first: the near
+ * stretch starts at first[i]); the same argument checks as oisat_factor_mid, and mid is checked against first.  The stretch is
+ * on exactly where the far and middle stretches are on by default; everywhere else, and under OISAT_ENVELOPE=0,
+ * near_out == mid.
+ * OISAT_FACTOR_NEAR_BITS in the environment (read at every call): 0 switches the stretch off (near_out == mid: the launch
+ * without the stretch, bit for bit); 1 <= n <= 52 forces the table of cut-off 2^-n at every enveloped size; `all` forces the
+ * whole rest of every row, near_out[i] = i; anything else is OISAT_EINVAL.
+ * oisat_set_factor_near: hands the table (host int32[nb], copied; NULL / 0 = none) to the NEXT oisat_potrf_env /
+ * oisat_potrf_env_fwd on this handle, which consumes it whatever its outcome and checks it against its own first and the far
+ * and middle tables set for the same call.  Without it, and in every other factorization, there is no near stretch.  The
+ * ticket words do not carry it, and the launch that also solves (oisat_batch_analyse) ignores it. */
+int oisat_factor_near(const double* lat_sorted, int64_t m, double g, const int32_t* first, const int32_t* mid, int32_t* near_out);
 
 /* ---- the correlation model ----------------------------------------------------------------------------------------
  * OISAT_CORR_GAUSSIAN (default): C = exp(-g chord^2).  OISAT_CORR_GASPARI_COHN: the compactly supported fifth-order function
@@ -506,6 +523,9 @@ int oisat_set_factor_far(oisat_ctx* h, const int32_t* far, int64_t nb);
 int oisat_factor_mid_corr(int kind, const double* lat_sorted, int64_t m, double g, const int32_t* first, const int32_t* far,
                           int32_t* mid_out);       /* oisat_factor_mid for a model; not Gaussian: mid_out == far unless forced */
 int oisat_set_factor_mid(oisat_ctx* h, const int32_t* mid, int64_t nb);
+int oisat_factor_near_corr(int kind, const double* lat_sorted, int64_t m, double g, const int32_t* first, const int32_t* mid,
+                           int32_t* near_out);     /* oisat_factor_near for a model; not Gaussian: near_out == mid unless forced */
+int oisat_set_factor_near(oisat_ctx* h, const int32_t* near, int64_t nb);
 /* The factor's shadow (csrc/dense_dag.inc "Shadow"): where an enveloped factorization has a far or a
  * middle block, the task that makes a strictly-lower tile (r, k), first[r] <= k < r, final also stores its two bf16 images,
  * hi = bf16(a) (nearest even) and lo = bf16(a - hi), into a per-handle workspace of 64 KiB per tile, and the two stretches

@@ -483,6 +483,7 @@ struct PotrfEnv {                // the envelope of S and its stretches; all nul
     const int32_t* env_dev = nullptr;   // ... and device first[mpb] | last[mpb] (oisat_envelope)
     const int32_t* far = nullptr;       // host int32[mpb], with first, or null: the far stretch of every block row (oisat_factor_far), bf16 K-blocks in the task graph
     const int32_t* mid = nullptr;       // likewise: the middle stretch behind it (oisat_factor_mid), split bf16 K-blocks
+    const int32_t* near = nullptr;      // likewise: the near stretch behind that (oisat_factor_near), three-way split bf16 K-blocks
 };
 // fwd_d (device double[m]) or nullptr: the right-hand side whose first forward sweep rides in the task-graph launch
 // (oisat_potrf_env_fwd).  schedule_out (optional): OISAT_SCHEDULE_* of what ran.
@@ -525,8 +526,8 @@ static int potrf_impl(oisat_ctx* h, float* S, int64_t m, int64_t ld, int* info_h
         DagSingle* hit = nullptr;
         for (DagSingle& c : h->dag_cache)
             if (c.plan && c.S == S && c.tinv == tinv && c.ld == ld && c.mpb == mpb && c.enveloped == (first != nullptr) && c.fwd == ride) hit = &c;
-        if (hit && first && !hit->plan->bands.equals((size_t)mpb, first, env.far, env.mid))
-            if (int rf = dag_plan_refill(*hit->plan, DagBands((int)mpb, first, env.far, env.mid), h->stream)) return rf;
+        if (hit && first && !hit->plan->bands.equals((size_t)mpb, first, env.far, env.mid, env.near))
+            if (int rf = dag_plan_refill(*hit->plan, DagBands((int)mpb, first, env.far, env.mid, env.near), h->stream)) return rf;
         if (!hit) {
             DagSingle* slot = nullptr;
             for (DagSingle& c : h->dag_cache)
@@ -545,7 +546,7 @@ static int potrf_impl(oisat_ctx* h, float* S, int64_t m, int64_t ld, int* info_h
                 shape.fwd_only = true;
             }
             slot->plan = dag_plan_create(std::vector<BatchMat>{BatchMat{S, tinv, ld, m, (int)mpb, 0}}, h->stream, shape,
-                                         first ? DagBands((int)mpb, first, env.far, env.mid) : DagBands());
+                                         first ? DagBands((int)mpb, first, env.far, env.mid, env.near) : DagBands());
             if (!slot->plan) return OISAT_ENOMEM;
             slot->S = S; slot->tinv = tinv; slot->ld = ld; slot->mpb = mpb; slot->enveloped = first != nullptr; slot->fwd = ride;
             hit = slot;
@@ -674,14 +675,16 @@ extern "C" int oisat_factor_shadow_tile(oisat_ctx* h, int r, int k, uint16_t* hi
 static int potrf_env_entry(oisat_ctx* h, float* S, int64_t m, int64_t ld, const int32_t* first, const int32_t* env_dev, bool fwd, const double* d,
                            int* info_host, int* schedule_out) {
     ARG_CHECK(h != nullptr);
-    std::vector<int32_t> far, mid;
+    std::vector<int32_t> far, mid, near;
     far.swap(h->factor_far);                                    // one-shot, whatever this call's outcome
     mid.swap(h->factor_mid);                                    // likewise
+    near.swap(h->factor_near);                                  // likewise
     ARG_CHECK(first && env_dev && (!fwd || d) && m > 0);
     ARG_CHECK(envelope_table_ok(first, cdiv(m, NB)) && far_table_ok(far, first, cdiv(m, NB)) &&
-              mid_table_ok(mid, far, first, cdiv(m, NB)));
+              mid_table_ok(mid, far, first, cdiv(m, NB)) && near_table_ok(near, mid, far, first, cdiv(m, NB)));
     PotrfEnv env;
-    if (!oisat_envelope_off()) env = PotrfEnv{first, env_dev, far.empty() ? nullptr : far.data(), mid.empty() ? nullptr : mid.data()};
+    if (!oisat_envelope_off()) env = PotrfEnv{first, env_dev, far.empty() ? nullptr : far.data(), mid.empty() ? nullptr : mid.data(),
+                                                  near.empty() ? nullptr : near.data()};
     return potrf_impl(h, S, m, ld, info_host, env, d, schedule_out);
 }
 

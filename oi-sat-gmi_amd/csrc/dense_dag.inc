@@ -387,6 +387,109 @@ __device__ __forceinline__ void dag_seg_bf16x2(float* __restrict__ lds, const Da
 #undef DAG_CHUNK
 }
 
+// ... and as THREE-WAY split bf16 products -- the NEAR stretch of a bulk task's K-loop (knear, "Near stretch" at dag_task_order):
+// fp32's 24 bits through the bf16 pipe.  Every operand fragment a becomes hi = bf16(a), mid = bf16(a - hi), lo = bf16(a - hi - mid)
+// -- each rounded to nearest even by v_cvt_pk_bf16_f32, both differences exact in fp32; bf16 has fp32's exponent, so there is
+// no range to mind and nothing is scaled; three parts of eight significant bits hold fp32's 24, so a = hi + mid + lo exactly
+// (above bf16's denormal range) -- and a product a b^T becomes EIGHT, smallest terms first:  mid lo^T, lo mid^T, hi lo^T, lo hi^T,
+// mid mid^T, hi mid^T, mid hi^T, hi hi^T.  Only lo lo^T is dropped, <= 2^-32 |a||b| per term.  (Six products, without the first
+// two, were what the stretch was first written with: they lose up to 2^-23 of a term -- |mid| <= 2^-8 |a|, |lo| <= 2^-16 |a| at the
+// bottom of a binade --, 2^-24.2 as measured, and miss the 2^-25 the stretch is specified with; they were 1.4 ms of the headline
+// step faster.  The products are not what limits the stretch, though: with six OR eight the first residual of the headline's
+// gain solve rises 10 - 13 % when every fp32 K-block takes it -- the bf16 pipe's accumulation of eight partial products per
+// k-chunk is not the fp32 pipe's accumulation of exact products --, hence the cut-off kFactorNearBits, dense_tables.hip.)
+// 32 MFMAs per k-chunk into the same four accumulators, term by term, the quadrants 00,
+// 01, 10, 11 inside a term: no MFMA waits for the one in front of it.  1/2 of dag_seg's MFMA cycles per K-step (64 x 32
+// against 64 x 64); the split is ~5.5 VALU instructions per operand element (11 per pair: three packs, four unpacks, four
+// subtractions), operand by operand so that a raw fragment is dead before the next is split.
+// The same fp32 LDS image, LDS-DMA fill and fragment addresses as dag_seg_bf16x2 -- nothing changes in memory -- but the
+// fragment reads are written out (dag_lds_rd / dag_lds_wait, as in dag_seg_sh): left to the compiler the first ds_read of a
+// K-step waits for vmcnt(0), i.e. for the DMA of the NEXT K-step issued just in front of it, which dag_seg hides behind 4 096
+// MFMA cycles and this loop would not.  Here that DMA flies under the K-step's splits and MFMAs and is waited for once, in front
+// of the barrier.  A k-chunk's B fragments are read first and split while its A fragments arrive; the next k-chunk's reads
+// are issued before this one's MFMAs.  On entry no wave reads or fills the LDS image and this wave has no load in flight; on
+// return everything has landed, every read is back and every wave is past a barrier, as after dag_seg.
+__device__ __forceinline__ void dag_split2x3(unsigned x, unsigned y, unsigned& hi, unsigned& mid, unsigned& lo) {
+    const float fx = __builtin_bit_cast(float, x), fy = __builtin_bit_cast(float, y);
+    hi = dag_pk_bf16(fx, fy);
+    const float rx = fx - __builtin_bit_cast(float, hi << 16), ry = fy - __builtin_bit_cast(float, hi & 0xffff0000u);
+    mid = dag_pk_bf16(rx, ry);                                  // (= dag_pk_bf16_lo(fx, fy, hi): dag_split8's lo)
+    lo = dag_pk_bf16_lo(rx, ry, mid);
+}
+__device__ __forceinline__ void dag_split8x3(const dag_u32x4& a, const dag_u32x4& b, dag_u32x4& hi, dag_u32x4& mid, dag_u32x4& lo) {
+    unsigned h[4], m[4], l[4];
+    dag_split2x3(a.x, a.y, h[0], m[0], l[0]);
+    dag_split2x3(a.z, a.w, h[1], m[1], l[1]);
+    dag_split2x3(b.x, b.y, h[2], m[2], l[2]);
+    dag_split2x3(b.z, b.w, h[3], m[3], l[3]);
+    hi = dag_u32x4{h[0], h[1], h[2], h[3]};
+    mid = dag_u32x4{m[0], m[1], m[2], m[3]};
+    lo = dag_u32x4{l[0], l[1], l[2], l[3]};
+}
+#define DAG_BF(X) __builtin_bit_cast(dag_bf16x8, X)
+#define DAG_MFMA4_BF16(A0, A1, B0, B1)                                                          \
+    acc00 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(DAG_BF(A0), DAG_BF(B0), acc00, 0, 0, 0);    \
+    acc01 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(DAG_BF(A0), DAG_BF(B1), acc01, 0, 0, 0);    \
+    acc10 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(DAG_BF(A1), DAG_BF(B0), acc10, 0, 0, 0);    \
+    acc11 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(DAG_BF(A1), DAG_BF(B1), acc11, 0, 0, 0);
+__device__ __forceinline__ void dag_seg_bf16x3(float* __restrict__ lds, const DagLane& L, const float* Ad, int64_t lda, const float* Bd, int64_t ldb,
+                                               int nkt, f32x16& acc00, f32x16& acc01, f32x16& acc10, f32x16& acc11) {
+    typedef __attribute__((address_space(3))) const void* lcptr_t;
+    constexpr unsigned IMGB = NB * BK * 4;                      // bytes of one operand image; lds = [buf][A|B][image]
+    // the lane's row of each operand in buffer 0, and the byte offsets of its four logical chunks 4 c + 2 fh + e inside the
+    // 128-byte row: physical chunk = logical ^ sw, so they differ from the first by XORs of 16 (e) and 64 (c)
+    const unsigned a_row = (unsigned)(uintptr_t)(lcptr_t)lds + 4u * (unsigned)L.arow;
+    const unsigned b_row = (unsigned)(uintptr_t)(lcptr_t)lds + IMGB + 4u * (unsigned)L.brow;
+    const unsigned q = 16u * (unsigned)((2 * L.fh) ^ L.sw);
+    dag_u32x4 a0h, a0m, a0l, a1h, a1m, a1l, b0h, b0m, b0l, b1h, b1m, b1l;
+    dag_u32x4 rb0, rb1, rb2, rb3, ra0, ra1, ra2, ra3;
+    auto read = [&](unsigned turn, unsigned c64) {              // k-chunk c of the buffer at `turn` bytes: B's fragments, then A's
+        const unsigned pb = b_row + turn, pa = a_row + turn, e0 = q ^ c64, e1 = e0 ^ 16u;
+        rb0 = dag_lds_rd<0>(pb + e0); rb1 = dag_lds_rd<0>(pb + e1);
+        rb2 = dag_lds_rd<32 * BK * 4>(pb + e0); rb3 = dag_lds_rd<32 * BK * 4>(pb + e1);
+        ra0 = dag_lds_rd<0>(pa + e0); ra1 = dag_lds_rd<0>(pa + e1);
+        ra2 = dag_lds_rd<32 * BK * 4>(pa + e0); ra3 = dag_lds_rd<32 * BK * 4>(pa + e1);
+    };
+    auto split = [&]() {
+        dag_lds_wait<4>(rb0, rb1, rb2, rb3);                    // (LDS reads return in order)
+        dag_split8x3(rb0, rb1, b0h, b0m, b0l);
+        dag_split8x3(rb2, rb3, b1h, b1m, b1l);
+        dag_lds_wait<0>(ra0, ra1, ra2, ra3);
+        dag_split8x3(ra0, ra1, a0h, a0m, a0l);
+        dag_split8x3(ra2, ra3, a1h, a1m, a1l);
+    };
+    auto products = [&]() {
+        DAG_MFMA4_BF16(a0m, a1m, b0l, b1l)
+        DAG_MFMA4_BF16(a0l, a1l, b0m, b1m)
+        DAG_MFMA4_BF16(a0h, a1h, b0l, b1l)
+        DAG_MFMA4_BF16(a0l, a1l, b0h, b1h)
+        DAG_MFMA4_BF16(a0m, a1m, b0m, b1m)
+        DAG_MFMA4_BF16(a0h, a1h, b0m, b1m)
+        DAG_MFMA4_BF16(a0m, a1m, b0h, b1h)
+        DAG_MFMA4_BF16(a0h, a1h, b0h, b1h)
+    };
+    const int n = __builtin_amdgcn_readfirstlane(nkt);
+    dag_dma(lds, 0, L, (const char*)Ad, 4 * lda, (const char*)Bd, 4 * ldb);
+    dag_vm_wait<0>();
+    dag_ring_barrier();
+    for (int kt = 0; kt < n; ++kt) {
+        const int cur = kt & 1;
+        const unsigned turn = (unsigned)cur * 2u * IMGB;
+        if (kt + 1 < n)                                         // the other buffer is free since the last barrier
+            dag_dma(lds, cur ^ 1, L, (const char*)(Ad + (kt + 1) * BK), 4 * lda, (const char*)(Bd + (kt + 1) * BK), 4 * ldb);
+        read(turn, 0u);
+        split();
+        read(turn, 64u);                                        // (the raw fragments are dead: the second k-chunk's arrive under the first one's MFMAs)
+        products();
+        split();
+        products();
+        dag_vm_wait<0>();                                       // this wave's DMA pieces of K-step kt + 1 have landed ...
+        dag_ring_barrier();                                     // ... everyone else's too; every read of K-step kt is back
+    }
+}
+#undef DAG_MFMA4_BF16
+#undef DAG_BF
+
 // The writer: the final tile held in the accumulators -> its two planes at `tile` (a shadow tile).  Through LDS, so that the
 // stores are coalesced 16-byte ones: a wave's 64 x 64 quadrant is rows 64 wr .. + 63 of the groups 4 wc .. + 3 of each plane,
 // four runs of 2 KiB contiguous in memory, and it stages them -- [group][row][16 columns], the memory order -- in the two 8 KiB
@@ -506,6 +609,9 @@ __device__ __forceinline__ void dag_epilogue(float* Cg /* the wave's 64x64 quadr
 // kmid (wave-uniform, one scalar load from sy.mid per task, kfar <= kmid <= kend; no table: kfar): the block columns
 // kfar .. kmid - 1 are the row's MIDDLE stretch, split bf16 products (dag_seg_bf16x2); kmid .. kend - 1 run in fp32.
 // FAR = false ignores it too.
+// knear (wave-uniform, one scalar load from sy.near per task, kmid <= knear <= kend; no table: kmid): the block columns
+// kmid .. knear - 1 are the row's NEAR stretch, three-way split bf16 products from the fp32 tiles (dag_seg_bf16x3); only
+// knear .. kend - 1 run on the fp32 pipe.  FAR = false ignores it as well.
 // With a shadow (sy.shadow, "Shadow" above; FAR only) the far and / or middle segments (sy.shuse) read the operands' bf16
 // images instead, and a DAG_TILE task stores its tile's images in front of its publish.
 template <bool FAR>
@@ -531,6 +637,12 @@ __device__ __forceinline__ bool dag_tile_task(const DagSys& sy, int kind, int k0
         kmid = sy.mid[i];
         kmid = kmid < kfar ? kfar : kmid;
         kmid = kmid > kend ? (kend > kfar ? kend : kfar) : kmid;
+    }
+    int knear = kmid;
+    if (FAR && sy.near) {
+        knear = sy.near[i];
+        knear = knear < kmid ? kmid : knear;
+        knear = knear > kend ? (kend > kmid ? kend : kmid) : knear;
     }
     int k = k0;
     while (k < kend) {
@@ -562,6 +674,10 @@ __device__ __forceinline__ bool dag_tile_task(const DagSys& sy, int kind, int k0
             else
                 dag_seg_bf16x2(lds, L, dag_src(Arow + (int64_t)k * NB, sy.ld, L), sy.ld, dag_src(Brow + (int64_t)k * NB, sy.ld, L), sy.ld,
                                (kav - k) * (NB / BK), acc00, acc01, acc10, acc11);
+        } else if (FAR && k < knear) {                          // ... and the near one
+            kav = kav < knear ? kav : knear;
+            dag_seg_bf16x3(lds, L, dag_src(Arow + (int64_t)k * NB, sy.ld, L), sy.ld, dag_src(Brow + (int64_t)k * NB, sy.ld, L), sy.ld,
+                           (kav - k) * (NB / BK), acc00, acc01, acc10, acc11);
         } else {
             dag_seg(lds, L, dag_src(Arow + (int64_t)k * NB, sy.ld, L), sy.ld, dag_src(Brow + (int64_t)k * NB, sy.ld, L), sy.ld, (kav - k) * (NB / BK),
                     acc00, acc01, acc10, acc11);

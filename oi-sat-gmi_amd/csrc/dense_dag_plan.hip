@@ -32,12 +32,14 @@ static inline void dag_queue_entries(const std::vector<int>& nb_of, const DagSol
 // What changes in DagSys[0] of a single-system plan after its creation -- the middle table's pointer, this call's shadow (null:
 // none), its row table and its readers (DagSys::shuse) --, uploaded on `stream` when the host copy differs.  wait: launches that
 // read the system's words as they are may be in flight, and a change waits for them.
-static hipError_t dag_plan_sys0(DagPlan& p, const int* mid, char* shadow, const int64_t* shrow, int shuse, bool wait, hipStream_t stream) {
+static hipError_t dag_plan_sys0(DagPlan& p, const int* mid, const int* near, char* shadow, const int64_t* shrow, int shuse, bool wait,
+                                hipStream_t stream) {
     DagSys& sy = p.sys_host[0];
-    if (sy.mid == mid && sy.shadow == shadow && sy.shrow == shrow && sy.shuse == shuse) return hipSuccess;
+    if (sy.mid == mid && sy.near == near && sy.shadow == shadow && sy.shrow == shrow && sy.shuse == shuse) return hipSuccess;
     if (wait)
         if (hipError_t e = hipStreamSynchronize(stream)) return e;
     sy.mid = mid;
+    sy.near = near;
     sy.shadow = shadow;
     sy.shrow = shrow;
     sy.shuse = shuse;
@@ -61,8 +63,13 @@ static hipError_t dag_plan_install(DagPlan& p, DagOrder& order, const DagBands& 
     for (size_t i = 0; i < nb; ++i) any = any || bands.mid[i] > bands.far[i];
     if (any)
         if (hipError_t e = hipMemcpyAsync(p.mid_dev, p.bands.mid.data(), sizeof(int) * nb, hipMemcpyHostToDevice, stream)) return e;
+    bool any_near = false;                                      // ... and the near table and its pointer, by the same rule
+    for (size_t i = 0; i < nb; ++i) any_near = any_near || bands.near[i] > bands.mid[i];
+    if (any_near)
+        if (hipError_t e = hipMemcpyAsync(p.near_dev, p.bands.near.data(), sizeof(int) * nb, hipMemcpyHostToDevice, stream)) return e;
     const DagSys& sy = p.sys_host[0];
-    if (hipError_t e = dag_plan_sys0(p, any ? p.mid_dev : nullptr, sy.shadow, sy.shrow, sy.shuse, false, stream)) return e;
+    if (hipError_t e = dag_plan_sys0(p, any ? p.mid_dev : nullptr, any_near ? p.near_dev : nullptr, sy.shadow, sy.shrow, sy.shuse, false, stream))
+        return e;
     p.shrow.resize(nb);
     p.sh_tiles = dag_shadow_layout(p.bands.first.data(), (int64_t)nb, p.shrow.data());
     for (size_t r = 0; r < nb; ++r) p.shrow[r] -= p.bands.first[r];
@@ -81,6 +88,7 @@ void dag_plan_free(DagPlan* p) {
     if (p->ctl_dev) (void)hipFree(p->ctl_dev);
     if (p->queue_dev) (void)hipFree(p->queue_dev);
     if (p->mid_dev) (void)hipFree(p->mid_dev);
+    if (p->near_dev) (void)hipFree(p->near_dev);
     if (p->shrow_dev) (void)hipFree(p->shrow_dev);
     if (p->trace_dev) (void)hipFree(p->trace_dev);
     delete p;
@@ -103,6 +111,10 @@ void dag_plan_free(DagPlan* p) {
 // first word, and the words stay what they are: the table itself goes to the device (DagPlan::mid_dev, uploaded with the ticket
 // list by dag_plan_install) and a task clamps kmid = mid[i] into [kfar, kend] with one scalar load.  The ticket ORDER does not
 // depend on it.
+// Near stretch (oisat_factor_near: near[i] = first block column of block row i that is NOT near, mid[i] <= near[i] <= i): the
+// K-blocks kmid .. knear - 1 run as three-way split bf16 products from the fp32 tiles (dag_seg_bf16x3), the rest in fp32.  The
+// middle table's path throughout: DagPlan::near_dev, one scalar load per task, knear = near[i] clamped into [kmid, kend]; the
+// ticket words and their order do not know about it.
 // (kDagEnvMaxBlocks = 1024 and kDagEnvLeadFar: dense_internal.h)
 // lead_far: kDagEnvLeadFar for every launch; the query oisat_dag_task_order_env alone may be given another (its comment).
 void dag_task_order(const std::vector<int>& nb_of, int wave_arg, DagOrder& out, const int* first, const int* far, double lead_far) {
@@ -240,7 +252,7 @@ int64_t dag_shadow_layout(const int* first, int64_t nb, int64_t* rowoff) {
 // This call's shadow (null: none) and its readers (DagSys::shuse) into the plan's system; a change waits for the launches
 // that read the system's words as they are.
 hipError_t dag_plan_shadow(DagPlan& p, char* shadow, int use, hipStream_t stream) {
-    return dag_plan_sys0(p, p.sys_host[0].mid, shadow, shadow ? p.shrow_dev : nullptr, use, true, stream);
+    return dag_plan_sys0(p, p.sys_host[0].mid, p.sys_host[0].near, shadow, shadow ? p.shrow_dev : nullptr, use, true, stream);
 }
 
 // systems in table order (largest first)
@@ -287,6 +299,7 @@ DagPlan* dag_plan_create(const std::vector<BatchMat>& table, hipStream_t stream,
               hipMalloc((void**)&p->state_dev, sizeof(int) * words) == hipSuccess &&
               hipMalloc((void**)&p->ctl_dev, sizeof(DagCtl)) == hipSuccess &&
               (!env || hipMalloc((void**)&p->mid_dev, sizeof(int) * bands.first.size()) == hipSuccess) &&
+              (!env || hipMalloc((void**)&p->near_dev, sizeof(int) * bands.first.size()) == hipSuccess) &&
               (!env || hipMalloc((void**)&p->shrow_dev, sizeof(int64_t) * bands.first.size()) == hipSuccess) &&
               (p->qcap == 0 || (p->qcap < (int64_t)INT32_MAX / 4 && hipMalloc((void**)&p->queue_dev, 16 * (size_t)p->qcap) == hipSuccess));
     if (ok && p->qcap > 0) ok = hipMemsetAsync(p->queue_dev, 0, 16 * (size_t)p->qcap, stream) == hipSuccess;

@@ -47,6 +47,7 @@ struct DagSys {                  // one system of a task-graph launch (device ta
     char* shadow;
     const int64_t* shrow;        // int64[nb]: rowoff[r] - first[r] (DagPlan::shrow_dev; rowoff: oisat_factor_shadow_layout)
     int shuse;                   // who READS it: 1 = the far stretch, 2 = the middle stretch (OISAT_FACTOR_SHADOW); the writers always store
+    const int* near;             // int32[nb]: first block column of each block row that is not "near" (DagPlan::near_dev), or null: no near stretch
 };
 constexpr int64_t kShTile = 65536;                              // bytes of a shadow tile
 constexpr int kShPlane = 32768, kShGroup = 4096;                // ... of a plane, of a 16-column group of a plane
@@ -79,19 +80,21 @@ struct DagSolve {                // the solve phase of a launch (dense_dag.inc, 
 
 // ---- host: the plan of a task-graph launch ---------------------------------------------------------------------------
 // The envelope an enveloped single-system plan was made for and its stretches, normalised: no far stretch (oisat_factor_far) is
-// far = first, no middle stretch (oisat_factor_mid) is mid = far.  Empty: a dense plan.
+// far = first, no middle stretch (oisat_factor_mid) is mid = far, no near stretch (oisat_factor_near) is near = mid.  Empty: a dense plan.
 struct DagBands {
-    std::vector<int> first, far, mid;
+    std::vector<int> first, far, mid, near;
     DagBands() {}
-    DagBands(int nb, const int* first_, const int* far_, const int* mid_)
-        : first(first_, first_ + nb), far(far_ ? std::vector<int>(far_, far_ + nb) : first), mid(mid_ ? std::vector<int>(mid_, mid_ + nb) : far) {}
-    bool operator==(const DagBands& o) const { return first == o.first && far == o.far && mid == o.mid; }
+    DagBands(int nb, const int* first_, const int* far_, const int* mid_, const int* near_)
+        : first(first_, first_ + nb), far(far_ ? std::vector<int>(far_, far_ + nb) : first), mid(mid_ ? std::vector<int>(mid_, mid_ + nb) : far),
+          near(near_ ? std::vector<int>(near_, near_ + nb) : mid) {}
+    bool operator==(const DagBands& o) const { return first == o.first && far == o.far && mid == o.mid && near == o.near; }
     // ... against a caller's raw tables of nb rows, normalised the same way, without building one
-    bool equals(size_t nb, const int* first_, const int* far_, const int* mid_) const {
+    bool equals(size_t nb, const int* first_, const int* far_, const int* mid_, const int* near_) const {
         far_ = far_ ? far_ : first_;
         mid_ = mid_ ? mid_ : far_;
+        near_ = near_ ? near_ : mid_;
         return first.size() == nb && std::equal(first.begin(), first.end(), first_) && std::equal(far.begin(), far.end(), far_) &&
-               std::equal(mid.begin(), mid.end(), mid_);
+               std::equal(mid.begin(), mid.end(), mid_) && std::equal(near.begin(), near.end(), near_);
     }
 };
 
@@ -111,6 +114,7 @@ struct DagPlan {
     std::vector<int4> tasks_host;
     DagBands bands;                                             // what this plan's ticket list was made for
     int* mid_dev = nullptr;                                     // the device copy of bands.mid (an enveloped plan's int32[nb]); DagSys::mid points here while a stretch exists
+    int* near_dev = nullptr;                                    // likewise bands.near; DagSys::near points here while a row has a near block
     std::vector<int64_t> shrow;                                 // the shadow's row table of `first`: rowoff[r] - first[r] (dag_shadow_layout), and its device copy
     int64_t* shrow_dev = nullptr;
     int64_t sh_tiles = 0;                                       // tiles of that shadow: sum of r - first[r]
@@ -160,11 +164,13 @@ hipError_t dag_plan_shadow(DagPlan& p, char* shadow, int use, hipStream_t stream
 DagPlan* dag_plan_create(const std::vector<BatchMat>& table, hipStream_t stream, const DagSolveShape& shape = DagSolveShape(),
                          const DagBands& bands_arg = DagBands());
 int dag_plan_refill(DagPlan& p, const DagBands& bands, hipStream_t stream);
-// dense_tables.hip (host only): a caller's envelope table, and the far and middle tables it set for a factorization (empty:
+// dense_tables.hip (host only): a caller's envelope table, and the far, middle and near tables it set for a factorization (empty:
 // none), checked against each other
 bool envelope_table_ok(const int32_t* first, int64_t nb);
 bool far_table_ok(const std::vector<int32_t>& far, const int32_t* first, int64_t nb);
 bool mid_table_ok(const std::vector<int32_t>& mid, const std::vector<int32_t>& far, const int32_t* first, int64_t nb);
+bool near_table_ok(const std::vector<int32_t>& near, const std::vector<int32_t>& mid, const std::vector<int32_t>& far, const int32_t* first,
+                   int64_t nb);
 
 // ---- the recursion's tree, the GEMM launches, the status words -----------------------------------------------------------
 // One launch of a batched GEMM kernel (dense_gemm.hip: batch_operands derives a member's operands from its table entry and the node)

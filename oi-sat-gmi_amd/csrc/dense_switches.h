@@ -17,6 +17,7 @@
 //   OISAT_FACTOR_CUT_BITS      <number in [1, 52]>                  oisat_factor_envelope_corr (dense_tables.hip) test_factor_envelope_cpu
 //   OISAT_FACTOR_FAR_BITS      0 | <number in [1, 52]>              oisat_factor_far_corr (dense_tables.hip)      test_far_band_cpu
 //   OISAT_FACTOR_MID_BITS      0 | <number in [1, 52]>              oisat_factor_mid_corr (dense_tables.hip)      test_mid_band_cpu
+//   OISAT_FACTOR_NEAR_BITS     0 | <number in [1, 52]> | all        oisat_factor_near_corr (dense_tables.hip)     test_near_band_cpu
 //   OISAT_TRSV_TWO_TILES       0 | 1                                trsv_launch_shape (dense_solve.hip)           test_gpu_sweep_tiles
 //   OISAT_TRSV_MAX_WGS         <integer >= 1>                       trsv_launch_shape (dense_solve.hip)           test_gpu_sweep_tiles
 //   OISAT_RESID_UPDATE         0 | 1                                oisat_gain_solve (dense_solve.hip)            test_gpu_resid_update
@@ -93,11 +94,17 @@ inline int number_switch(const char* name, bool empty_is_unset, double* out) {
     *out = strtod(e, &end);
     return end != e && *end == '\0' ? 1 : -1;
 }
-// OISAT_DAG_ORDER_LEAD_FAR (oisat_dag_task_order_env only); OISAT_FACTOR_CUT_BITS, OISAT_FACTOR_FAR_BITS, OISAT_FACTOR_MID_BITS;
+// OISAT_DAG_ORDER_LEAD_FAR (oisat_dag_task_order_env only); OISAT_FACTOR_CUT_BITS, OISAT_FACTOR_FAR_BITS, OISAT_FACTOR_MID_BITS,
+// OISAT_FACTOR_NEAR_BITS;
 // OISAT_SOLVE_FAR_BITS: the readers check the range
 inline int dag_order_lead_far(double* out) { return number_switch("OISAT_DAG_ORDER_LEAD_FAR", false, out); }
 inline int factor_bits_switch(const char* name, double* out) { return number_switch(name, true, out); }
 inline int solve_far_bits(double* out) { return number_switch("OISAT_SOLVE_FAR_BITS", true, out); }
+// OISAT_FACTOR_NEAR_BITS=all: the one spelling of that switch that is not a number
+inline bool factor_near_all() {
+    const char* e = getenv("OISAT_FACTOR_NEAR_BITS");
+    return e && strcmp(e, "all") == 0;
+}
 // a forced OISAT_FACTOR_CUT_BITS switches the stretches' default rule off, whatever it holds
 inline bool factor_cut_bits_set() {
     const char* c = getenv("OISAT_FACTOR_CUT_BITS");

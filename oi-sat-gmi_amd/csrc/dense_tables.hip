@@ -1,7 +1,7 @@
 // The dense solver's factor tables: pure host arithmetic, no kernel and no device call, which the *_cpu tests drive without a
-// GPU.  The envelope of S in block rows (oisat_envelope*), the factor's own narrower envelope and its far and middle stretches
-// (oisat_factor_envelope* / _far* / _mid*, with the measurements behind their cut-offs), and the checks of the tables a caller
-// hands back (envelope_table_ok, far_table_ok, mid_table_ok: dense_internal.h).
+// GPU.  The envelope of S in block rows (oisat_envelope*), the factor's own narrower envelope and its far, middle
+// and near stretches (oisat_factor_envelope* / _far* / _mid* / _near*, with the measurements behind their cut-offs), and the checks of
+// the tables a caller hands back (envelope_table_ok, far_table_ok, mid_table_ok, near_table_ok: dense_internal.h).
 #include "dense_internal.h"
 
 using namespace oisat_dense;
@@ -133,23 +133,34 @@ constexpr double kFactorFarBits = 18.0;
 // below it, `first` for the far stretch, `far` for the middle one -- or lower[i] where the stretch is off.  bits: `def` under the
 // default rule -- on exactly where the narrow table is: Gaussian, tile-work-bound, no forced OISAT_FACTOR_CUT_BITS --, or the <n>
 // of the variable `var`: 0 = off, 1 .. 52 forces 2^-n at every enveloped size.  Never on under OISAT_ENVELOPE=0.
-static int stretch_table(const char* var, double def, int kind, const double* lat_sorted, int64_t m, double g, const int32_t* lower, int32_t* out) {
+// all_ok (the near stretch): the variable may also say `all`, and `def` may be kFactorNearAll -- the whole rest of the row, out[i] = i,
+// no cut-off at all; a `def` of 0 is a stretch that is off unless forced.
+constexpr double kFactorNearAll = -1.0;
+static int stretch_table(const char* var, double def, int kind, const double* lat_sorted, int64_t m, double g, const int32_t* lower, int32_t* out,
+                         bool all_ok = false) {
     const int64_t nb = cdiv(m, NB);
     double bits = def;
     bool on = false, forced = false;
-    if (int rc = env_bits(var, 0.0, &bits, &forced)) return rc;
+    if (all_ok && factor_near_all()) {
+        bits = kFactorNearAll;
+        forced = true;
+    } else if (int rc = env_bits(var, 0.0, &bits, &forced)) {
+        return rc;
+    }
     std::vector<int32_t> t(2 * (size_t)nb);
     if (forced) {
-        on = bits >= 1.0;
+        on = bits >= 1.0 || bits == kFactorNearAll;
         ARG_CHECK(on || bits == 0.0);
-    } else {
+    } else if (def != 0.0) {
         if (!factor_cut_bits_set() && kind == OISAT_CORR_GAUSSIAN) {        // the default rule's own choice: the narrow table, or not
             envelope_table(kind, lat_sorted, m, g, kFactorCutBits, t.data());
             on = narrow_table_pays(t.data(), nb);
         }
     }
     on = on && !oisat_envelope_off();
-    if (on) envelope_table(kind, lat_sorted, m, g, bits, t.data());
+    if (on && bits != kFactorNearAll) envelope_table(kind, lat_sorted, m, g, bits, t.data());
+    if (on && bits == kFactorNearAll)
+        for (int64_t i = 0; i < nb; ++i) t[i] = (int32_t)i;
     for (int64_t i = 0; i < nb; ++i) out[i] = on ? std::min<int32_t>(std::max(t[i], lower[i]), (int32_t)i) : lower[i];
     return OISAT_OK;
 }
@@ -225,5 +236,53 @@ bool oisat_dense::mid_table_ok(const std::vector<int32_t>& mid, const std::vecto
     if ((int64_t)mid.size() != nb || !far_table_ok(far, first, nb)) return false;
     for (int64_t i = 0; i < nb; ++i)
         if (mid[i] < (far.empty() ? first[i] : far[i]) || mid[i] > i) return false;
+    return true;
+}
+
+// The near stretch of the factor's K-loops: the block columns mid[i] <= k < near[i] of block row i, between the middle stretch
+// and what is left for the fp32 pipe.  Their products run on the bf16 pipe as THREE-WAY split products (dense_dag.inc:
+// dag_seg_bf16x3: eight bf16 products per fp32 one, only lo lo^T dropped: <= 2^-32 of a term), 1/2 of the fp32 pipe's MFMA cycles.
+// The split is exact and the products are accurate far beyond fp32's rounding, and still the stretch is NOT free next to the
+// diagonal, where L's entries are large: the sum of eight partial products per k-chunk, each rounded into the fp32 accumulator, is
+// not the fp32 pipe's sum of exact products.  So the cut-off is a measurement like the other two.  On by default exactly where they
+// are (Gaussian, tile-work-bound, no forced OISAT_FACTOR_CUT_BITS, not OISAT_ENVELOPE=0).  OISAT_FACTOR_NEAR_BITS (read at every
+// call): 0 = off (near = mid, the launch of the code before the stretch, bit for bit); 1 .. 52 forces the table of 2^-n at every
+// enveloped size (clamped to mid[i] <= near[i] <= i); `all` = the whole rest of every row, near[i] = i (kFactorNearAll).  The
+// chain's own products stay fp32 whatever the table says.
+// The value, by the protocol of kFactorMidBits (profiles/EXPERIMENTS.md, "The near stretch as three-way split bf16 products";
+// profiles/near_band_sweep.json): on the same four months, far 2^-18 and middle 2^-8, OISAT_FACTOR_NEAR_BITS = 2 leaves the first
+// residual within +1.7 % of the run without the stretch; 1 raises it by 2.7 - 4.4 % (admissible: <= 1.05 x, one correction, last
+// residual <= 1.12 x); `all` raises it by 11.5 - 12.4 % on all four and is NOT admissible (with six products: 10 - 13 %, the
+// same).  Kept: the widest admissible value, 1.  Headline: 650 997 of 2 519 868 K-blocks are near (0.258), 0.041 stay on the fp32
+// pipe; the step falls by 1.1 - 1.3 ms.
+constexpr double kFactorNearBits = 1.0;
+
+extern "C" int oisat_factor_near_corr(int kind, const double* lat_sorted, int64_t m, double g, const int32_t* first, const int32_t* mid,
+                                      int32_t* near_out) {
+    ARG_CHECK(corr_kind_ok(kind) && lat_sorted && first && mid && near_out && m > 0 && g >= 0.0);
+    ARG_CHECK(lat_sorted_ok(lat_sorted, m));
+    const int64_t nb = cdiv(m, NB);
+    ARG_CHECK(envelope_table_ok(first, nb));
+    for (int64_t i = 0; i < nb; ++i) ARG_CHECK(mid[i] >= first[i] && mid[i] <= i);
+    return stretch_table("OISAT_FACTOR_NEAR_BITS", kFactorNearBits, kind, lat_sorted, m, g, mid, near_out, true);
+}
+
+extern "C" int oisat_factor_near(const double* lat_sorted, int64_t m, double g, const int32_t* first, const int32_t* mid, int32_t* near_out) {
+    return oisat_factor_near_corr(OISAT_CORR_GAUSSIAN, lat_sorted, m, g, first, mid, near_out);
+}
+
+extern "C" int oisat_set_factor_near(oisat_ctx* h, const int32_t* near, int64_t nb) {
+    ARG_CHECK(h != nullptr && nb >= 0 && (near != nullptr || nb == 0));
+    h->factor_near.assign(near, near + nb);
+    return OISAT_OK;
+}
+
+// the near table the caller set for this factorization (empty: none) against its envelope and the tables below it (empty: the one below)
+bool oisat_dense::near_table_ok(const std::vector<int32_t>& near, const std::vector<int32_t>& mid, const std::vector<int32_t>& far,
+                                const int32_t* first, int64_t nb) {
+    if (near.empty()) return true;
+    if ((int64_t)near.size() != nb || !mid_table_ok(mid, far, first, nb)) return false;
+    for (int64_t i = 0; i < nb; ++i)
+        if (near[i] < (!mid.empty() ? mid[i] : !far.empty() ? far[i] : first[i]) || near[i] > i) return false;
     return true;
 }

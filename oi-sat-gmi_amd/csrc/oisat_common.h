@@ -152,6 +152,7 @@ struct oisat_ctx {
     int64_t obs_perm_m = 0;
     std::vector<int32_t> factor_far;    // oisat_set_factor_far: the far stretch of the NEXT enveloped factorization (one-shot)
     std::vector<int32_t> factor_mid;    // oisat_set_factor_mid: ... and its middle stretch (one-shot)
+    std::vector<int32_t> factor_near;   // oisat_set_factor_near: ... and its near stretch (one-shot)
     // the factor's shadow (dense_dag.inc "Shadow": bf16 images of the final tiles, workspace slot 10)
     int64_t shadow_cap = -1;            // oisat_set_factor_shadow_cap: most bytes it may take, -1 = no limit
     const char* shadow_last = nullptr;  // the shadow the last factorization on this handle filled (nullptr: it had none) ...

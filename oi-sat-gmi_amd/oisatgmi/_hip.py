@@ -114,6 +114,9 @@ SIGNATURES = {
     "oisat_factor_envelope_corr": (C.c_int, [C.c_int, _ptr, _i64, C.c_double, _ptr]),
     "oisat_factor_far_corr": (C.c_int, [C.c_int, _ptr, _i64, C.c_double, _ptr, _ptr]),
     "oisat_factor_mid_corr": (C.c_int, [C.c_int, _ptr, _i64, C.c_double, _ptr, _ptr, _ptr]),
+    "oisat_factor_near": (C.c_int, [_ptr, _i64, C.c_double, _ptr, _ptr, _ptr]),
+    "oisat_factor_near_corr": (C.c_int, [C.c_int, _ptr, _i64, C.c_double, _ptr, _ptr, _ptr]),
+    "oisat_set_factor_near": (C.c_int, [_ptr, _ptr, _i64]),
     "oisat_dag_task_order_env": (C.c_int, [C.c_int, _ptr, _ptr, _ptr, _i64, C.POINTER(_i64)]),
     "oisat_cov_build_env": (C.c_int, [_c_ctx, _ptr, _ptr, _ptr, _i64, C.c_double, _ptr, _i64, _ptr]),
     "oisat_potrf_env": (C.c_int, [_c_ctx, _ptr, _i64, _i64, _ptr, _ptr, C.POINTER(C.c_int)]),

@@ -215,7 +215,7 @@ class DenseAnalysis:
             self.perm.shared_with_other_streams()
         # the block envelope of the latitude-sorted system (``oisat_factor_envelope``): first | last, 2 x mp_max / 128 words
         self.env = c.alloc(2 * (self.mp_max // NB) * 4)
-        self._env_host, self._env_key, self._far_host, self._mid_host = None, None, None, None
+        self._env_host, self._env_key, self._far_host, self._mid_host, self._near_host = None, None, None, None, None
         self._kind = 0                                         # the correlation model of the last run / run_build
         # What this plan knows about its S between runs (``oisat_cov_build_env_zeroed``): after a build and an enveloped
         # task-graph factorization with table T nothing outside T has been written, so every lower tile left of T is still the
@@ -286,8 +286,11 @@ class DenseAnalysis:
                                                               far.ctypes.data))
             self.ctx.check(self.ctx.lib.oisat_factor_mid_corr(kind, self._lat_sorted.ctypes.data, self.m, g, env.ctypes.data,
                                                               far.ctypes.data, mid.ctypes.data))
+            near = np.empty(nb, dtype=np.int32)
+            self.ctx.check(self.ctx.lib.oisat_factor_near_corr(kind, self._lat_sorted.ctypes.data, self.m, g, env.ctypes.data,
+                                                               mid.ctypes.data, near.ctypes.data))
             self.ctx.upload_into(self.env.ptr, env)
-            self._env_host, self._env_key, self._far_host, self._mid_host = env, (g, kind), far, mid
+            self._env_host, self._env_key, self._far_host, self._mid_host, self._near_host = env, (g, kind), far, mid, near
         return self._env_host
 
     def _unsort(self, per_obs):
@@ -342,6 +345,7 @@ class DenseAnalysis:
         info = C.c_int(0)
         c.check(lib.oisat_set_factor_far(h, self._far_host.ctypes.data, self._far_host.size))        # per run: handles are shared
         c.check(lib.oisat_set_factor_mid(h, self._mid_host.ctypes.data, self._mid_host.size))
+        c.check(lib.oisat_set_factor_near(h, self._near_host.ctypes.data, self._near_host.size))
         c.check(lib.oisat_potrf_env_fwd(h, self.S.ptr, m, ld, first.ctypes.data, self.env.ptr, self.d.ptr,
                                         C.byref(info) if check_pd else None, C.byref(schedule)))
         self.last_schedule = schedule.value                    # (SCHEDULE_*: which factorization ran, for tests and profiles)
