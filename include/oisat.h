@@ -728,6 +728,32 @@ int oisat_probe_spread(oisat_ctx* h, const double* gxyz, const double* gsig, int
 int oisat_probe_diag(oisat_ctx* h, const float* U, int64_t nprobe, int64_t ldu, int64_t m, int accumulate,
                      double* sum2_out, double* sum4_out);
 
+/* ---- analysis error of linear functionals: regional means --------------------------------------
+ * For K functionals W (K x n, a row = weights over cells) the analysis error covariance is
+ *   A_W = W B W^T - G^T S^-1 G,   G = H B W^T (m x K),   S = H B H^T + R,
+ * K refined gain solves through the factor (oisat_gain_solve) and two pair sums, G and T = B W^T; the caller
+ * (oisatgmi/dense.py: functional_covariance) forms prior = W T^T and the reduction G^T Y + R^T Y, R = G - S Y.
+ * Both device calls are asynchronous on the handle's stream and use no workspace.
+ *
+ * oisat_functional_gather: out[k][p] = psig_p sum_j C(p, j) ssig_j W[k][j], k < nfun, p < npts, j < nsrc, under the handle's
+ * correlation model.  pxyz / sxyz: dev double[3 * npts] / [3 * nsrc], unit vectors x | y | z; psig, ssig: dev double[npts] /
+ * [nsrc]; W: dev double[nfun][ldw], ldw >= nsrc; out: dev double[nfun][ldo], ldo >= npts, columns npts..ldo are not written.
+ * The sources must be stored in ASCENDING latitude when slat_sorted is given.  plat / slat_sorted (degrees; both or the pair
+ * counts as NULL) enable the latitude window and the bounding-sphere cull at the library's 2^-52 chord per run of 256
+ * consecutive targets: the terms left out are below 2^-52 of a full term; NULL: every pair is evaluated.  Float64 throughout:
+ * |p - q|^2 from the double coordinates, the correlation that oisat_corr_eval evaluates, one fused multiply-add per pair and
+ * functional; no fp32 tier.  The sums run in source order; same inputs, same bits.  1 <= nfun <= 64, npts >= 1,
+ * 1 <= nsrc < 2^31, anything else is OISAT_EINVAL with nothing launched.
+ *
+ * oisat_rows_dot: out[k][l] = sum_p A[k][p] B[l][p] in double, A: dev double[na][lda], B: dev double[nb][ldb], lda, ldb >= len,
+ * out: dev double[na][nb] (dense).  1 <= na, nb <= 64, len >= 1.  The summation tree depends on len alone (thread t of 256
+ * adds p = t, t + 256, ..; lanes by butterfly, waves as (0 + 1) + (2 + 3)): same inputs, same bits on any device. */
+int oisat_functional_gather(oisat_ctx* h, const double* pxyz, const double* psig, const double* plat, int64_t npts,
+                            const double* sxyz, const double* ssig, const double* slat_sorted, int64_t nsrc,
+                            const double* W, int64_t nfun, int64_t ldw, double g, double* out, int64_t ldo);
+int oisat_rows_dot(oisat_ctx* h, const double* A, int64_t lda, int64_t na, const double* B, int64_t ldb, int64_t nb,
+                   int64_t len, double* out);
+
 /* The ticket list of a task-graph launch over nsys systems of block_rows[s] block rows (largest first), as the library would
  * build it -- host only, no device: int32 quadruples (kind, system, i, j) with kind 0 = chain of `system` (i = first row of its
  * trace stamps), 1 = tile task T(i, j), 2 = SUB(j) (tile (j+1, j)), 3 = PRE(j) (tile (j, j)).  (The solve tasks of

@@ -341,20 +341,6 @@ __global__ __launch_bounds__(256) void probe_spread_kernel(const double* __restr
     }
 }
 
-// launch KERNEL<KIND, ...> for the handle's correlation model (h->corr, oisat_set_correlation): one instantiation per model,
-// no test of the model inside a kernel
-#define OISAT_LAUNCH_CORR(h, NAME, KERNEL, TARGS, grid, block, shmem, ...)                                         \
-    do {                                                                                                           \
-        if ((h)->corr == OISAT_CORR_GASPARI_COHN) {                                                                \
-            OISAT_LAUNCH(h, NAME, (KERNEL<OISAT_CORR_GASPARI_COHN, TARGS>), grid, block, shmem, __VA_ARGS__);      \
-        } else if ((h)->corr == OISAT_CORR_SOAR) {                                                                 \
-            OISAT_LAUNCH(h, NAME, (KERNEL<OISAT_CORR_SOAR, TARGS>), grid, block, shmem, __VA_ARGS__);              \
-        } else {                                                                                                   \
-            OISAT_LAUNCH(h, NAME, (KERNEL<OISAT_CORR_GAUSSIAN, TARGS>), grid, block, shmem, __VA_ARGS__);          \
-        }                                                                                                          \
-    } while (0)
-#define OISAT_TARGS(...) __VA_ARGS__
-
 }  // namespace
 
 extern "C" int oisat_set_correlation(oisat_ctx* h, int kind) {

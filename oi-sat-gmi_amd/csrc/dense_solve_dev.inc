@@ -2,7 +2,7 @@
 // system's residuals and increment as tasks of the same persistent launch that factors it): the latitude window, the
 // bounding-sphere cull, and the bodies of the float64 residual and of the increment as functions of a block index and a
 // carve-out of the caller's LDS.  Included inside the anonymous namespace of dense_cov.hip, dense_dag.hip, dense_solve.hip and dense_tables.hip
-// (host rules), dense_post.hip and buddy.hip (correlation functions); expects dense_switches.h at file scope before it; no kernels here.
+// (host rules), dense_functional.hip (window, cull, corr_f64), dense_post.hip and buddy.hip (correlation functions); expects dense_switches.h at file scope before it; no kernels here.
 // (No reference counterpart: the dense analysis is the north-star extension, SURVEY.md section 8 a-ext.)
 #ifndef OISAT_DENSE_SWITCHES_H
 #error "include dense_switches.h at file scope before dense_solve_dev.inc: this file is included inside a namespace and cannot"

@@ -218,6 +218,20 @@ void oisat_prof_end(oisat_ctx* h, int pending);
         }                                                                                      \
     } while (0)
 
+// launch KERNEL<KIND, ...> for the handle's correlation model (h->corr, oisat_set_correlation): one instantiation per model,
+// no test of the model inside a kernel
+#define OISAT_LAUNCH_CORR(h, NAME, KERNEL, TARGS, grid, block, shmem, ...)                                         \
+    do {                                                                                                           \
+        if ((h)->corr == OISAT_CORR_GASPARI_COHN) {                                                                \
+            OISAT_LAUNCH(h, NAME, (KERNEL<OISAT_CORR_GASPARI_COHN, TARGS>), grid, block, shmem, __VA_ARGS__);      \
+        } else if ((h)->corr == OISAT_CORR_SOAR) {                                                                 \
+            OISAT_LAUNCH(h, NAME, (KERNEL<OISAT_CORR_SOAR, TARGS>), grid, block, shmem, __VA_ARGS__);              \
+        } else {                                                                                                   \
+            OISAT_LAUNCH(h, NAME, (KERNEL<OISAT_CORR_GAUSSIAN, TARGS>), grid, block, shmem, __VA_ARGS__);          \
+        }                                                                                                          \
+    } while (0)
+#define OISAT_TARGS(...) __VA_ARGS__
+
 static inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
 // memory-bound grid sizing: enough blocks to fill 256 CUs x 8, grid-stride the rest

@@ -139,6 +139,9 @@ SIGNATURES = {
     "oisat_probe_spread": (C.c_int, [_c_ctx, _ptr, _ptr, _i64, _i64, _ptr, _ptr, _ptr, _i64, _i64, _i64, C.c_double, _ptr, _ptr,
                                      C.c_int, _ptr, _ptr]),
     "oisat_probe_diag": (C.c_int, [_c_ctx, _ptr, _i64, _i64, _i64, C.c_int, _ptr, _ptr]),
+    "oisat_functional_gather": (C.c_int, [_c_ctx, _ptr, _ptr, _ptr, _i64, _ptr, _ptr, _ptr, _i64, _ptr, _i64, _i64, C.c_double, _ptr,
+                                          _i64]),
+    "oisat_rows_dot": (C.c_int, [_c_ctx, _ptr, _i64, _i64, _ptr, _i64, _i64, _i64, _ptr]),
     "oisat_apply_increment": (C.c_int, [_c_ctx, C.c_int, _ptr, _ptr, _i64, _ptr, _ptr, _ptr, _i64, C.c_double, _ptr,
                                         _ptr, _ptr, _ptr, _ptr]),
     "oisat_apply_increment_grid": (C.c_int, [_c_ctx, C.c_int, _ptr, _ptr, _i64, _i64, _ptr, _ptr, _ptr, _i64, C.c_double, _ptr,

@@ -24,6 +24,8 @@ therefore builds and factors only the covariance's latitude envelope (``oisat_fa
 cut-off of its own; the build does not re-zero what is zero, the factorization launch carries the first forward sweep).
 ``OI_dense(..., superob=box_deg)`` first merges the observations of one box into a superobservation (``superob``,
 csrc/superob.hip: ``oisat_superob``), so that a month denser than HBM allows still has a dense analysis.
+``OI_dense(..., regions=labels)`` / ``DenseAnalysis.functional_covariance`` report the exact analysis error of regional means, error
+correlations between cells included (csrc/dense_functional.hip: ``oisat_functional_gather``, ``oisat_rows_dot``).
 """
 from __future__ import annotations
 
@@ -175,6 +177,9 @@ class DenseAnalysis:
         c = self.ctx
         self.gxyz = c.upload(unit_vectors(grid_lat, grid_lon))
         self.glat = c.upload(np.ravel(grid_lat), dtype=np.float64)       # latitude window of apply_increment
+        # (functional_covariance: the support of a set of functionals is cut out of these on the host)
+        self._glat_host = np.ravel(np.asarray(grid_lat, dtype=np.float64))
+        self._glon_host = np.ravel(np.asarray(grid_lon, dtype=np.float64))
         item = self.dt.itemsize
         if out_ptr is None:
             # xb | xa | inc; read by torch's RCCL stream when the fields are gathered (parallel.FieldGather)
@@ -217,6 +222,8 @@ class DenseAnalysis:
         self.env = c.alloc(2 * (self.mp_max // NB) * 4)
         self._env_host, self._env_key, self._far_host, self._mid_host, self._near_host = None, None, None, None, None
         self._kind = 0                                         # the correlation model of the last run / run_build
+        self._g = None                                         # ... and its decay constant: None until a run has happened
+        self._fun_bufs = {}                                    # functional_covariance: grow-only device buffers by name
         # What this plan knows about its S between runs (``oisat_cov_build_env_zeroed``): after a build and an enveloped
         # task-graph factorization with table T nothing outside T has been written, so every lower tile left of T is still the
         # exact zero of the fill.  Kept only by a plan that owns its S (a shared or batched buffer is written by others), as
@@ -457,6 +464,116 @@ class DenseAnalysis:
                 "q": q.reshape(self.shape), "q_se": np.sqrt(q_var).reshape(self.shape),
                 "s": self._unsort(s), "s_se": self._unsort(np.sqrt(s_var))}
 
+    # ---- analysis error of linear functionals: regional means
+    def _functional_buffer(self, name, nbytes):
+        """Grow-only device buffer ``name`` of this plan."""
+        bufs = self._fun_bufs
+        if name not in bufs or bufs[name].nbytes < nbytes:
+            bufs[name] = self.ctx.alloc(int(nbytes))
+        return bufs[name]
+
+    def _functional_support(self, W):
+        """``W`` as (K, n) float64 and the support of its rows: the cells where any row is non-zero and the background sigma
+        is finite and positive, in ascending latitude (stable).  Pure host work; every bad argument is a ``ValueError``."""
+        W = np.asarray(W, dtype=np.float64)
+        if W.ndim == 3 and W.shape[1:] == tuple(self.shape):
+            W = W.reshape(W.shape[0], -1)
+        if W.ndim != 2 or W.shape[1] != self.n:
+            raise ValueError(f"W must be (K, {self.n}) or (K,) + {tuple(self.shape)}, not {W.shape}")
+        if not 1 <= W.shape[0] <= 64:
+            raise ValueError(f"1 to 64 functionals per call, not {W.shape[0]}")
+        sig = getattr(self, "_gsig_host", None)
+        if sig is None:
+            raise ValueError("load_background() first: the functionals are weighted by the background error")
+        with np.errstate(invalid="ignore"):
+            ok = np.isfinite(sig) & (sig > 0.0)
+        sup = np.flatnonzero((W != 0.0).any(axis=0) & ok)
+        sup = sup[latitude_order(self._glat_host[sup])]
+        return W, sup
+
+    def _functional_upload(self, W, sup):
+        """Unit vectors, sigma, latitudes and the K x nsrc weight block of the support -> device (grow-only buffers)."""
+        c = self.ctx
+        K, ns = W.shape[0], sup.size
+        sx = self._functional_buffer("sxyz", 3 * ns * 8)
+        ss = self._functional_buffer("ssig", ns * 8)
+        sl = self._functional_buffer("slat", ns * 8)
+        sw = self._functional_buffer("W", K * ns * 8)
+        c.upload_into(sx.ptr, unit_vectors(self._glat_host[sup], self._glon_host[sup]))
+        c.upload_into(ss.ptr, self._gsig_host[sup], dtype=np.float64)
+        c.upload_into(sl.ptr, self._glat_host[sup], dtype=np.float64)
+        c.upload_into(sw.ptr, W[:, sup], dtype=np.float64)
+        return sx, ss, sl, sw
+
+    def functional_prior(self, W, L_km=None, corr=None):
+        """``W B W^T`` alone, (K, K) float64, symmetric: the error covariance of the functionals before any observation.
+        Needs the background only; ``L_km`` / ``corr`` default to those of the last ``run()``."""
+        if L_km is None and self._g is None:
+            raise ValueError("functional_prior() without L_km must follow run()")
+        W, sup = self._functional_support(W)
+        K, ns = W.shape[0], int(sup.size)
+        if ns == 0:
+            return np.zeros((K, K))
+        g = self._g if L_km is None else decay_constant(L_km)
+        kind = self._kind if corr is None else corr_kind(corr)
+        c, lib, h = self.ctx, self.ctx.lib, self.ctx.h
+        sx, ss, sl, sw = self._functional_upload(W, sup)
+        T = self._functional_buffer("T", K * ns * 8)
+        small = self._functional_buffer("small", (3 * 64 + 2) * 64 * 8)
+        c.check(lib.oisat_set_correlation(h, kind))
+        c.check(lib.oisat_functional_gather(h, sx.ptr, ss.ptr, sl.ptr, ns, sx.ptr, ss.ptr, sl.ptr, ns, sw.ptr, K, ns, g, T.ptr, ns))
+        c.check(lib.oisat_rows_dot(h, sw.ptr, ns, K, T.ptr, ns, K, ns, small.ptr))
+        prior = c.download(small.ptr, (K, K), np.float64)
+        return 0.5 * (prior + prior.T)
+
+    def functional_covariance(self, W, refine: int = 2, tol=None):
+        """Exact analysis error covariance of K linear functionals ``W`` ((K, ny, nx) or (K, n); a row = weights over cells,
+        e.g. ``region_weights``): A_W = W B W^T - G^T S^-1 G with G = H B W^T, through the factor that ``run()`` left in HBM.
+        Two float64 pair sums (``oisat_functional_gather``: G at the observations, T = B W^T at the support), one refined
+        gain solve S y_k = g_k per functional, its float64 residual r_k = g_k - S y_k, and the residual-corrected reduction
+        G^T Y + R^T Y = G^T S^-1 G - R^T S^-1 R, whose error is second order in the residual and never understates a
+        variance.  Returns ``prior``, ``reduction``, ``posterior`` ((K, K) float64, symmetric), ``resid`` ((K,), |r_k| / |g_k|)
+        and ``support`` (cells that carry weight).  A functional with empty support gives zero rows and columns."""
+        if not self.m or self._g is None:
+            raise ValueError("functional_covariance() must follow run(): it reads the factor that run() leaves behind")
+        W, sup = self._functional_support(W)
+        K, ns, m, mp = W.shape[0], int(sup.size), self.m, self.mp
+        zero = np.zeros((K, K))
+        if ns == 0:
+            return {"prior": zero, "reduction": zero.copy(), "posterior": zero.copy(), "resid": np.zeros(K), "support": 0}
+        live = np.flatnonzero((W[:, sup] != 0.0).any(axis=1))
+        c, lib, h = self.ctx, self.ctx.lib, self.ctx.h
+        g, kind = self._g, self._kind
+        sx, ss, sl, sw = self._functional_upload(W, sup)
+        T = self._functional_buffer("T", K * ns * 8)
+        gyr = self._functional_buffer("GYR", 3 * K * self.mp_max * 8)       # G | Y | R, rows of mp doubles (g_k is a right-hand side)
+        small = self._functional_buffer("small", (3 * 64 + 2) * 64 * 8)   # W T^T | G^T Y | R^T Y | |g_k|^2 | |r_k|^2
+        G, Y, R = gyr.at(0), gyr.at(K * mp * 8), gyr.at(2 * K * mp * 8)
+        c.check(lib.oisat_memset(h, gyr.ptr, 0, 3 * K * mp * 8))
+        c.check(lib.oisat_memset(h, small.ptr, 0, (3 * K + 2) * K * 8))
+        c.check(lib.oisat_set_correlation(h, kind))
+        c.check(lib.oisat_functional_gather(h, self.oxyz.ptr, self.osig.ptr, self.olat.ptr, m, sx.ptr, ss.ptr, sl.ptr, ns, sw.ptr, K,
+                                            ns, g, G, mp))
+        c.check(lib.oisat_functional_gather(h, sx.ptr, ss.ptr, sl.ptr, ns, sx.ptr, ss.ptr, sl.ptr, ns, sw.ptr, K, ns, g, T.ptr, ns))
+        KK = K * K * 8
+        c.check(lib.oisat_rows_dot(h, sw.ptr, ns, K, T.ptr, ns, K, ns, small.at(0)))
+        for k in map(int, live):
+            gk, yk, rk = G + k * mp * 8, Y + k * mp * 8, R + k * mp * 8
+            c.check(lib.oisat_set_refine_tol(h, REFINE_TOL if tol is None else float(tol)))      # per call: handles are shared
+            c.check(lib.oisat_set_correlation(h, kind))
+            c.check(lib.oisat_set_obs_blocks(h, self.perm.ptr, m))                               # (one-shot: the solve takes it)
+            c.check(lib.oisat_gain_solve(h, self.S.ptr, self.oxyz.ptr, self.osig.ptr, self.ovar.ptr, m, mp, g, gk, int(refine), yk,
+                                         None, self.olat.ptr))
+            c.check(lib.oisat_cov_residual(h, self.oxyz.ptr, self.osig.ptr, self.ovar.ptr, m, g, gk, yk, rk, self.olat.ptr))
+            c.check(lib.oisat_rows_dot(h, gk, mp, 1, gk, mp, 1, m, small.at(3 * KK + k * 8)))     # |g_k|^2, |r_k|^2
+            c.check(lib.oisat_rows_dot(h, rk, mp, 1, rk, mp, 1, m, small.at(3 * KK + (K + k) * 8)))
+        c.check(lib.oisat_rows_dot(h, G, mp, K, Y, mp, K, m, small.at(KK)))
+        c.check(lib.oisat_rows_dot(h, R, mp, K, Y, mp, K, m, small.at(2 * KK)))
+        self.check()
+        out = c.download(small.ptr, ((3 * K + 2) * K,), np.float64)
+        prior, gy, ry = out[:3 * K * K].reshape(3, K, K)
+        return assemble_functional_covariance(prior, gy, ry, out[3 * K * K:3 * K * K + K], out[3 * K * K + K:], ns)
+
     # ---- outputs
     def check(self):
         """Wait for this handle's stream and raise ``OisatError`` if any solve enqueued on it since the last check met a
@@ -480,6 +597,64 @@ class DenseAnalysis:
     def flops(m: int) -> float:
         """Algorithmic flops of the gain solve as BASELINE.md counts them: m^3/3 + 2 m^2."""
         return m ** 3 / 3.0 + 2.0 * m ** 2
+
+
+def assemble_functional_covariance(prior, gy, ry, gg_diag, rr_diag, support=0):
+    """The result of ``DenseAnalysis.functional_covariance`` from its (K, K) products, pure NumPy: ``prior`` = W T^T, ``gy`` =
+    G^T Y, ``ry`` = R^T Y with y_k the computed solve of S y = g_k and r_k = g_k - S y_k, ``gg_diag`` / ``rr_diag`` = |g_k|^2 /
+    |r_k|^2.  With y = S^-1 (g - r): G^T Y + R^T Y = G^T S^-1 G - R^T S^-1 R -- the reduction's error is second order in the
+    residual, bounded by tol^2 cond(S) of the prior, and it can only make the reduction smaller, the variance larger.  (The plain
+    G^T Y is G^T S^-1 G - G^T S^-1 R: first order, either sign.)  Everything is symmetrised."""
+    prior, gy, ry = (np.asarray(a, dtype=np.float64) for a in (prior, gy, ry))
+    prior = 0.5 * (prior + prior.T)
+    red = gy + ry
+    red = 0.5 * (red + red.T)
+    gg, rr = np.asarray(gg_diag, dtype=np.float64), np.asarray(rr_diag, dtype=np.float64)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        resid = np.where(gg > 0.0, np.sqrt(rr / gg), 0.0)
+    return {"prior": prior, "reduction": red, "posterior": prior - red, "resid": resid, "support": int(support)}
+
+
+def region_weights(labels, lat, valid=None, area_weighted=True):
+    """Regional-mean functionals from a label map, pure NumPy.  ``labels``: (ny, nx) integers, values <= 0 = no region;
+    ``lat``: (ny, nx) cell-centre latitudes in degrees; ``valid``: (ny, nx) bool, the cells that may carry weight (default:
+    all).  Returns ``(ids, W)``: the sorted distinct positive labels and W (K, ny, nx) float64 with W[k] = cos(lat) over the
+    valid cells of region ids[k] (1 with ``area_weighted=False``), normalised to sum 1.  More than 64 regions, or a region
+    without a valid cell, is a ``ValueError`` that names the label."""
+    labels = np.asarray(labels)
+    lat = np.asarray(lat, dtype=np.float64)
+    if labels.ndim != 2 or labels.shape != lat.shape:
+        raise ValueError(f"labels must be a (ny, nx) map on the grid {lat.shape}, not {labels.shape}")
+    if not np.issubdtype(labels.dtype, np.integer):
+        if not np.all(np.isfinite(labels)) or np.any(labels != np.rint(labels)):
+            raise ValueError("labels must hold integers")
+        labels = labels.astype(np.int64)
+    valid = np.ones(labels.shape, dtype=bool) if valid is None else np.asarray(valid, dtype=bool)
+    if valid.shape != labels.shape:
+        raise ValueError(f"valid must have the labels' shape {labels.shape}, not {valid.shape}")
+    ids = np.unique(labels[labels > 0])
+    if ids.size > 64:
+        raise ValueError(f"{ids.size} regions; at most 64 per call (label {int(ids[64])} is the 65th)")
+    w = np.cos(np.deg2rad(lat)) if area_weighted else np.ones(lat.shape)
+    W = np.zeros((ids.size,) + labels.shape)
+    for k, r in enumerate(ids):
+        wk = np.where((labels == r) & valid, w, 0.0)
+        tot = wk.sum()
+        if not tot > 0.0:
+            raise ValueError(f"region {int(r)} has no valid cell")
+        W[k] = wk / tot
+    return ids, W
+
+
+def _region_info(ids, W, Xa, xa_an, fc):
+    """``info["regions"]`` of ``OI_dense`` from the functionals' covariances and the two fields."""
+    Wf = W.reshape(W.shape[0], -1)
+    xb64 = np.ravel(np.asarray(Xa, dtype=np.float64))
+    ok = np.isfinite(xb64)
+    xa64 = np.ravel(np.asarray(xa_an, dtype=np.float64))
+    return {"ids": ids, "background_mean": Wf[:, ok] @ xb64[ok], "analysis_mean": Wf[:, ok] @ xa64[ok],
+            "prior_sd": np.sqrt(np.maximum(np.diag(fc["prior"]), 0.0)), "posterior_sd": np.sqrt(np.maximum(np.diag(fc["posterior"]), 0.0)),
+            "prior_cov": fc["prior"], "posterior_cov": fc["posterior"], "resid": fc["resid"]}
 
 
 def tile_partition(lat2, lon2, obs_lat, obs_lon, tile_deg=30.0, halo_km=900.0, merge_polar=True):
@@ -1075,7 +1250,7 @@ class MonthTileBatch:
 
 
 def OI_dense(Xa, Y, Sa, So, lat, lon, L_km, scale=1.0, refine=2, obs=None, dtype=None, want_error=False, tol=None,
-             corr="gaussian", nprobe=256, seed=0, superob=None, superob_rho=0.0):
+             corr="gaussian", nprobe=256, seed=0, superob=None, superob_rho=0.0, regions=None):
     """Dense-covariance analysis with the reference's gridded argument convention.
 
     ``Xa, Sa``: (ny, nx) background and its variance; ``Y, So``: (ny, nx) observations and their
@@ -1094,8 +1269,15 @@ def OI_dense(Xa, Y, Sa, So, lat, lon, L_km, scale=1.0, refine=2, obs=None, dtype
     correlation the errors of one box's members share.  With superobservations ``info["cells"]`` and ``info["nobs"]`` stay the raw ones,
     ``info["z"]`` / ``["ak_obs"]`` / ``["ak_obs_se"]`` are per superobservation, ``info["superob"]`` tells what was merged and
     ``info["ak"]`` gives member cell a of superobservation s the share ``ak_obs[s] w_a / W_s``.
+    ``regions``: an (ny, nx) integer label map (values <= 0: no region, at most 64 regions).  ``info["regions"]`` then holds, per
+    region in the order of ``ids``, the area-weighted ``background_mean`` and ``analysis_mean`` over the cells with a finite
+    background and the EXACT error of that mean before and after the analysis, ``prior_sd`` / ``posterior_sd``, with the full
+    ``prior_cov`` / ``posterior_cov`` between the regions and the solves' ``resid`` (``DenseAnalysis.functional_covariance``;
+    DESIGN.md section 4.2h).  The functionals are taken on whatever system the plan solved: ``obs=`` and ``superob=`` alike.
     """
     corr_kind(corr)                                           # (ValueError before anything is touched)
+    if regions is not None:                                   # (and so are a bad label map's)
+        reg_ids, reg_W = region_weights(regions, lat, valid=np.isfinite(np.asarray(Xa)))
     mc = isinstance(want_error, str)
     if mc and want_error != "mc":
         raise ValueError(f"want_error is False, True or 'mc', got {want_error!r}")
@@ -1139,6 +1321,12 @@ def OI_dense(Xa, Y, Sa, So, lat, lon, L_km, scale=1.0, refine=2, obs=None, dtype
                              error_method="mc", nprobe=int(nprobe))
         if so is not None:
             extra["superob"] = so_info
+        if regions is not None:        # nothing observed: the error of a regional mean stays the background's
+            plan = DenseAnalysis(lat, lon, max_obs=1, dtype=dt)
+            plan.load_background(xa_f, sa_f, scale=scale)
+            prior = plan.functional_prior(reg_W, L_km=L_km, corr=corr)
+            fc = {"prior": prior, "posterior": prior.copy(), "resid": np.zeros(len(reg_ids))}
+            extra["regions"] = _region_info(reg_ids, reg_W, Xa, xa_f, fc)
         return (np.array(Xa, dtype=dt), np.zeros(np.shape(Xa), dtype=dt),
                 {"nobs": 0, "residuals": [], "cells": cell, "z": np.empty(0), **extra})
     plan = DenseAnalysis(lat, lon, max_obs=int(cell.size if so is None else so["nobs"]), dtype=dt,
@@ -1169,6 +1357,8 @@ def OI_dense(Xa, Y, Sa, So, lat, lon, L_km, scale=1.0, refine=2, obs=None, dtype
         extra = {"ak": ak.reshape(np.shape(Xa)), "err": est["err"] if mc else plan.posterior_error(), "ak_obs": ak_obs}
         if mc:
             extra.update(err_se=est["err_se"], ak_obs_se=est["ak_obs_se"], error_method="mc", nprobe=est["nprobe"])
+    if regions is not None:
+        extra["regions"] = _region_info(reg_ids, reg_W, Xa, xb, plan.functional_covariance(reg_W, refine=refine, tol=tol))
     bad = ~np.isfinite(Xa)
     if bad.any():
         xb = xb.copy()

@@ -109,6 +109,12 @@ class oisatgmi(object):
     #               non-empty box (dense.superob); auto: nothing while the observations number at most
     #               max_obs (default 100 000), else the smallest box of 0.5, 0.75, 1, 1.5, 2, 3, 4, 6 degrees that leaves at
     #               most max_obs; a box wider than L / 2 is reported in one line; oi_info["superob"]
+    #   regions     attribute `oi_regions`     | env OISAT_OI_REGIONS     off (default) | an (ny, nx) integer label map, or the
+    #               path of a .npy file that holds one (the variable: a path)  (dense only; diag, tiled: ValueError): values <= 0
+    #               are no region, at most 64 regions.  The analysis then reports each region's area-weighted mean before and
+    #               after and the EXACT error of that mean, error correlations between cells included, with the covariances
+    #               between the regions (dense.DenseAnalysis.functional_covariance); region_OI,
+    #               oi_info["regions"]
     def _oi_setting(self, attr, env, default, cast=str):
         v = getattr(self, attr, None)
         if v is None:
@@ -176,6 +182,20 @@ class oisatgmi(object):
                              f"(a positive integer), not {v!r}") from None
         return f"auto:{max_obs}" if box == "auto" else box
 
+    def _regions_setting(self):
+        """``oi_regions`` (an array or a path) / ``OISAT_OI_REGIONS`` (a path) -> the label map, or ``None`` when neither is set."""
+        v = getattr(self, "oi_regions", None)
+        if v is None:
+            v = os.environ.get("OISAT_OI_REGIONS") or None
+        if v is None:
+            return None
+        if isinstance(v, (str, os.PathLike)):
+            try:
+                v = np.load(os.fspath(v), allow_pickle=False)
+            except (OSError, ValueError) as e:
+                raise ValueError(f"OISAT_OI_REGIONS / oi_regions: cannot read a .npy label map from {v!r}: {e}") from None
+        return np.asarray(v)
+
     def _oi_grid(self):
         lat, lon = getattr(self, "grid_lat", None), getattr(self, "grid_lon", None)
         if lat is None or lon is None:
@@ -198,6 +218,10 @@ class oisatgmi(object):
         Sa, So = (xa * error_ctm / 100.0) ** 2, self.sat_averaged_error ** 2
         mode = self._oi_setting("oi_mode", "OISAT_OI_MODE", "diag").lower()
         reg_index = getattr(self, "oi_reg_index", None)
+        regions = self._regions_setting()
+        if regions is not None and mode in ("diag", "tiled"):
+            raise ValueError("OISAT_OI_REGIONS / oi_regions belongs to the dense mode; the error of a regional mean needs the error "
+                             "correlations between cells, and regions cross tiles (off)")
         if mode == "diag":
             self.ctm_averaged_vcd_corrected, self.ak_OI, self.increment_OI, self.error_OI = OI(
                 xa, y, Sa, So, regularization_on=True, reg_index=reg_index)
@@ -236,20 +260,23 @@ class oisatgmi(object):
             sl = (slice(None), slice(None)) + tail
             res, info = self._oi_spatial(mode, xa[sl], y[sl], np.asarray(Sa)[sl], np.asarray(So)[sl], lat, lon, L, tile,
                                          unobserved, reg_index, want_error, corr=corr, nprobe=nprobe, qc=qc,
-                                         superob=superob)
+                                         superob=superob, regions=regions)
             for o, r in zip(outs, res):
                 o[sl] = r
             infos.append(info)
         self.ctm_averaged_vcd_corrected, self.ak_OI, self.increment_OI, self.error_OI = outs
         self.oi_info = dict(infos[0]) if len(infos) == 1 else {**infos[0], "slices": infos}
+        if regions is not None:                                  # (one dict per (month, year) slice when there are several)
+            self.region_OI = infos[0]["regions"] if len(infos) == 1 else [i["regions"] for i in infos]
 
     @staticmethod
     def _oi_spatial(mode, xa, y, Sa, So, lat, lon, L, tile, unobserved, reg_index, want_error, corr="gaussian", nprobe=256,
-                    qc=None, superob=None):
+                    qc=None, superob=None, regions=None):
         """One (ny, nx) Gaussian-B analysis -> ((Xb, AK, increment, error), info) in the reference's attribute order.  ``qc``
         (``_qc_setting``): not None = the innovations are checked first and the rejected cells analysed as unobserved, on a
         copy of ``y``.  ``superob`` (``_superob_setting``, dense mode): not None = the kept observations are merged into
-        superobservations ahead of the analysis; the ``observed`` mask stays the raw one."""
+        superobservations ahead of the analysis; the ``observed`` mask stays the raw one.  ``regions`` (dense mode): a label
+        map; ``info["regions"]`` then holds the regional means and their exact errors (``dense.OI_dense``)."""
         from . import dense
         from . import optimal_interpolation as oi_mod
         index, scale, curve, found = oi_mod.regularization_pick(Sa, So, reg_index)
@@ -286,7 +313,7 @@ class oisatgmi(object):
                     print("No correlation length could be fitted to the kept innovations; using 300 km")
         if mode == "dense":
             xb, inc, info = dense.OI_dense(xa, y, Sa, So, lat, lon, L, scale=scale, want_error=want_error, corr=corr,
-                                           nprobe=nprobe or 256, superob=superob)
+                                           nprobe=nprobe or 256, superob=superob, regions=regions)
             so = info.get("superob")
             if so is not None and so["box_deg"] * dense.KM_PER_DEG > 0.5 * L:      # (the knee_found convention: say so once)
                 print(f"The superobservation box of {so['box_deg']:g} degrees ({so['box_deg'] * dense.KM_PER_DEG:.0f} km) is wider "
@@ -323,6 +350,8 @@ class oisatgmi(object):
             out_info["qc"], out_info["qc_rejected"] = qc_info, qc_mask
         if info.get("superob") is not None:
             out_info["superob"] = info["superob"]
+        if info.get("regions") is not None:
+            out_info["regions"] = info["regions"]
         return (xb, ak, inc, err), out_info
 
     def scaling_factor(self):
