@@ -754,6 +754,21 @@ int oisat_functional_gather(oisat_ctx* h, const double* pxyz, const double* psig
 int oisat_rows_dot(oisat_ctx* h, const double* A, int64_t lda, int64_t na, const double* B, int64_t ldb, int64_t nb,
                    int64_t len, double* out);
 
+/* The likelihood of the innovations under the analysis' own model (csrc/dense_likelihood.hip):
+ * -2 ln p(d) = m ln 2 pi + log det S + d^T S^-1 d with S = H B H^T + R = L L^T.  chi^2 = d^T z and |d|^2 are oisat_rows_dot with
+ * na = nb = 1; the log-determinant is
+ *
+ * oisat_factor_logdet: out[0] = 2 sum_{a < m} log((double)L[a * ld + a]), out[1] = the smallest L[a * ld + a], a < m, as a double.
+ * L: dev float[>= m][ld], the factor any factorization of this library left in S (oisat_potrf, oisat_potrf_env,
+ * oisat_potrf_env_fwd, a member of a batch): they all keep the diagonal of L on the diagonal of S.  out: dev double[2].  Only
+ * the m diagonal entries are read -- not the identity padding m..roundup(m, 128), not a gutter beyond it.  If any of them is
+ * <= 0, infinite or NaN, out[0] is NaN (out[1] is still the smallest one that is a number, +inf if none is); nothing is added to the handle's
+ * status words.  Float64 throughout: the logarithm of the widened float, then a fixed tree -- one workgroup of 1024 threads,
+ * thread t takes a = t, t + 1024, .. into four partial sums by turn, joined (0 + 1) + (2 + 3); lanes by butterfly; the 16 waves
+ * pairwise, neighbours first -- which depends on m alone: same inputs, same bits on any device.  Asynchronous on the handle's
+ * stream, no workspace.  NULL h, L or out, m < 1 or ld < roundup(m, 128): OISAT_EINVAL, nothing launched, out untouched. */
+int oisat_factor_logdet(oisat_ctx* h, const float* L, int64_t m, int64_t ld, double* out);
+
 /* The ticket list of a task-graph launch over nsys systems of block_rows[s] block rows (largest first), as the library would
  * build it -- host only, no device: int32 quadruples (kind, system, i, j) with kind 0 = chain of `system` (i = first row of its
  * trace stamps), 1 = tile task T(i, j), 2 = SUB(j) (tile (j+1, j)), 3 = PRE(j) (tile (j, j)).  (The solve tasks of

@@ -142,6 +142,7 @@ SIGNATURES = {
     "oisat_functional_gather": (C.c_int, [_c_ctx, _ptr, _ptr, _ptr, _i64, _ptr, _ptr, _ptr, _i64, _ptr, _i64, _i64, C.c_double, _ptr,
                                           _i64]),
     "oisat_rows_dot": (C.c_int, [_c_ctx, _ptr, _i64, _i64, _ptr, _i64, _i64, _i64, _ptr]),
+    "oisat_factor_logdet": (C.c_int, [_c_ctx, _ptr, _i64, _i64, _ptr]),
     "oisat_apply_increment": (C.c_int, [_c_ctx, C.c_int, _ptr, _ptr, _i64, _ptr, _ptr, _ptr, _i64, C.c_double, _ptr,
                                         _ptr, _ptr, _ptr, _ptr]),
     "oisat_apply_increment_grid": (C.c_int, [_c_ctx, C.c_int, _ptr, _ptr, _i64, _i64, _ptr, _ptr, _ptr, _i64, C.c_double, _ptr,
@@ -177,8 +178,12 @@ SIGNATURES = {
 }
 
 
+ENOTPD = -4                    # include/oisat.h OISAT_ENOTPD: the Cholesky factorization met a non-positive pivot
+
+
 class OisatError(RuntimeError):
-    """A call into liboisat_hip.so returned an error code."""
+    """A call into liboisat_hip.so returned an error code (``code``; None where the error is not a call's return value)."""
+    code = None
 
 
 class OisatUnavailable(RuntimeError):
@@ -377,7 +382,9 @@ class Context:
     # ---- plumbing
     def check(self, rc: int):
         if rc != 0:
-            raise OisatError(f"liboisat_hip error {rc}: {self.lib.oisat_last_error().decode()}")
+            err = OisatError(f"liboisat_hip error {rc}: {self.lib.oisat_last_error().decode()}")
+            err.code = int(rc)
+            raise err
 
     def close(self):
         if self.h is not None:

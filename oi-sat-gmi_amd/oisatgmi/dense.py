@@ -26,6 +26,10 @@ cut-off of its own; the build does not re-zero what is zero, the factorization l
 csrc/superob.hip: ``oisat_superob``), so that a month denser than HBM allows still has a dense analysis.
 ``OI_dense(..., regions=labels)`` / ``DenseAnalysis.functional_covariance`` report the exact analysis error of regional means, error
 correlations between cells included (csrc/dense_functional.hip: ``oisat_functional_gather``, ``oisat_rows_dot``).
+``OI_dense(..., likelihood=True)`` / ``DenseAnalysis.log_likelihood`` report how consistent the innovations are with S itself: chi^2 =
+d^T S^-1 d, log det S from the factor's diagonal (csrc/dense_likelihood.hip: ``oisat_factor_logdet``) and -2 ln p(d);
+``OI_dense(..., fit_scale=)`` / ``DenseAnalysis.fit_error_scales`` estimate the amplitude of B -- and, on request, a common inflation of
+R -- by maximum likelihood (``set_error_scales``, ``profile_search``).
 """
 from __future__ import annotations
 
@@ -233,16 +237,54 @@ class DenseAnalysis:
         self._zero_dev = c.alloc((self.mp_max // NB) * 4) if self._owns_S else None
         self.m = 0
         self._direct_innovation = False
+        # the error scales (set_error_scales): host copies of the background sigma and of the sorted
+        # observations' sigma_b and variance AS LOADED, which the scaled ones on the device are made from
+        self._scales = (1.0, 1.0)
+        self._gsig0 = self._osig0 = self._ovar0 = None
+        self._lik_ready = False                                # the last run() was one that log_likelihood() may read
         # every internal workspace of the solve is sized here, so that run() never allocates (include/oisat.h)
         c.check(c.lib.oisat_dense_reserve(c.h, self.max_obs, int(diag_chunk_rows)))
 
     # ---- inputs
     def load_background(self, Xa, Sa, scale=1.0):
         c = self.ctx
+        self._reset_scales()
         c.upload_into(self.xb_ptr, np.ravel(Xa), dtype=self.dt)
         sig = np.sqrt(float(scale) * np.ravel(np.asarray(Sa, dtype=np.float64)))
-        self._gsig_host = sig
+        self._gsig0 = self._gsig_host = sig
         c.upload_into(self.gsig.ptr, sig, dtype=np.float64)
+
+    # ---- error scales
+    def set_error_scales(self, scale_b=1.0, scale_o=1.0):
+        """Analyse with ``scale_b`` times the background error variance and ``scale_o`` times the observation error variance
+        that were loaded: uploads ``gsig sqrt(scale_b)``, ``osig sqrt(scale_b)`` and ``ovar scale_o`` made from the host
+        copies of the loaded ones, and ``_gsig_host`` follows, so that ``posterior_error_mc`` and ``functional_covariance``
+        see the scaled variances.  The scales are absolute, not cumulative; every ``load_*`` resets them to 1.  Non-positive
+        or non-finite scales are a ``ValueError`` with nothing uploaded."""
+        try:
+            sb, so = float(scale_b), float(scale_o)
+        except (TypeError, ValueError):
+            raise ValueError(f"the error scales must be positive finite numbers, not {scale_b!r}, {scale_o!r}") from None
+        if not (0.0 < sb < np.inf and 0.0 < so < np.inf):
+            raise ValueError(f"the error scales must be positive finite numbers, not {scale_b!r}, {scale_o!r}")
+        c, rb = self.ctx, np.sqrt(sb)
+        if self._gsig0 is not None:
+            self._gsig_host = self._gsig0 * rb
+            c.upload_into(self.gsig.ptr, self._gsig_host, dtype=np.float64)
+        if self._osig0 is not None:
+            c.upload_into(self.osig.ptr, self._osig0 * rb, dtype=np.float64)
+            c.upload_into(self.ovar.ptr, self._ovar0 * so, dtype=np.float64)
+        self._scales = (sb, so)
+        self._lik_ready = False
+
+    def _reset_scales(self, obs=True):
+        """Back to the scales 1 ahead of a load; ``obs=False``: the observations are about to be replaced, only the
+        background's sigma is put back."""
+        if not obs:
+            self._osig0 = self._ovar0 = None
+        if self._scales != (1.0, 1.0):
+            self.set_error_scales(1.0, 1.0)
+        self._lik_ready = False
 
     def load_obs_direct(self, obs_lat, obs_lon, obs_sigma_b, obs_var, innovation):
         """Observations whose background value lives outside this plan's grid (tile halos): the caller
@@ -251,12 +293,15 @@ class DenseAnalysis:
         if m < 1 or m > self.max_obs:
             raise ValueError(f"{m} observations; this plan was sized for 1..{self.max_obs}")
         c = self.ctx
+        self._reset_scales(obs=False)
         self.m = m
         self.mp = -(-m // NB) * NB
         o = self._sort_by_latitude(obs_lat, obs_lon)
         c.upload_into(self.oxyz.ptr, unit_vectors(np.ravel(obs_lat)[o], np.ravel(obs_lon)[o]))
-        c.upload_into(self.osig.ptr, np.ravel(obs_sigma_b)[o], dtype=np.float64)
-        c.upload_into(self.ovar.ptr, np.ravel(obs_var)[o], dtype=np.float64)
+        self._osig0 = np.ascontiguousarray(np.ravel(obs_sigma_b)[o], dtype=np.float64)
+        self._ovar0 = np.ascontiguousarray(np.ravel(obs_var)[o], dtype=np.float64)
+        c.upload_into(self.osig.ptr, self._osig0)
+        c.upload_into(self.ovar.ptr, self._ovar0)
         c.upload_into(self.d.ptr, np.ravel(innovation)[o], dtype=np.float64)
         self._direct_innovation = True
 
@@ -277,18 +322,22 @@ class DenseAnalysis:
         self.ctx.upload_into(self.perm.ptr, morton_order(lat[self._order], lon))
         return self._order
 
-    def _envelope(self, g, kind=0):
+    def _envelope(self, g, kind=0, exact=False):
         """Host table ``first`` of this plan's observations at decay constant ``g`` under correlation model ``kind`` (the
         library's rule and the fp32 factor's cut-off: ``oisat_factor_envelope_corr``); its device copy ``first | last`` is in
         ``self.env``.  With it the far stretch of the factor's K-loops (``oisat_factor_far_corr``: the block columns of every
         row that run on the bf16 pipe), host only, in ``self._far_host``, and the middle stretch behind it (``oisat_factor_mid_corr``:
-        split bf16 products) in ``self._mid_host``.  All made once per (observations, L, model)."""
-        if self._env_host is None or self._env_key != (g, kind):
+        split bf16 products) in ``self._mid_host``.  All made once per (observations, L, model, ``exact``).  ``exact``: the table is
+        ``oisat_envelope_corr``'s, cut at 2^-52 -- the factor is then that of S itself, not of a truncated matrix, which is what a
+        log-determinant needs; the stretches are derived from it all the same."""
+        exact = bool(exact)
+        if self._env_host is None or self._env_key != (g, kind, exact):
             nb = self.mp // NB
             env = np.empty(2 * nb, dtype=np.int32)
             far = np.empty(nb, dtype=np.int32)
             mid = np.empty(nb, dtype=np.int32)
-            self.ctx.check(self.ctx.lib.oisat_factor_envelope_corr(kind, self._lat_sorted.ctypes.data, self.m, g, env.ctypes.data))
+            table = self.ctx.lib.oisat_envelope_corr if exact else self.ctx.lib.oisat_factor_envelope_corr
+            self.ctx.check(table(kind, self._lat_sorted.ctypes.data, self.m, g, env.ctypes.data))
             self.ctx.check(self.ctx.lib.oisat_factor_far_corr(kind, self._lat_sorted.ctypes.data, self.m, g, env.ctypes.data,
                                                               far.ctypes.data))
             self.ctx.check(self.ctx.lib.oisat_factor_mid_corr(kind, self._lat_sorted.ctypes.data, self.m, g, env.ctypes.data,
@@ -297,7 +346,7 @@ class DenseAnalysis:
             self.ctx.check(self.ctx.lib.oisat_factor_near_corr(kind, self._lat_sorted.ctypes.data, self.m, g, env.ctypes.data,
                                                                mid.ctypes.data, near.ctypes.data))
             self.ctx.upload_into(self.env.ptr, env)
-            self._env_host, self._env_key, self._far_host, self._mid_host, self._near_host = env, (g, kind), far, mid, near
+            self._env_host, self._env_key, self._far_host, self._mid_host, self._near_host = env, (g, kind, exact), far, mid, near
         return self._env_host
 
     def _unsort(self, per_obs):
@@ -311,23 +360,31 @@ class DenseAnalysis:
         if m < 1 or m > self.max_obs:
             raise ValueError(f"{m} observations; this plan was sized for 1..{self.max_obs}")
         c = self.ctx
+        self._reset_scales(obs=False)
         self.m = m
         self.mp = -(-m // NB) * NB
         o = self._sort_by_latitude(obs_lat, obs_lon)
         cell = np.ascontiguousarray(np.ravel(obs_cell)[o], dtype=np.int64)
         self._cell_sorted = cell                               # (posterior_error_mc: which cells carry exactly one observation)
         c.upload_into(self.oxyz.ptr, unit_vectors(np.ravel(obs_lat)[o], np.ravel(obs_lon)[o]))
-        c.upload_into(self.osig.ptr, self._gsig_host[cell], dtype=np.float64)
-        c.upload_into(self.ovar.ptr, np.ravel(obs_var)[o], dtype=np.float64)
+        self._osig0 = np.ascontiguousarray(self._gsig_host[cell], dtype=np.float64)
+        self._ovar0 = np.ascontiguousarray(np.ravel(obs_var)[o], dtype=np.float64)
+        c.upload_into(self.osig.ptr, self._osig0)
+        c.upload_into(self.ovar.ptr, self._ovar0)
         c.upload_into(self.ocell.ptr, cell)
         c.upload_into(self.oy.ptr, np.ravel(obs_y)[o], dtype=np.float64)
 
     # ---- the hot path: everything below runs on the device, enqueued on the handle's stream
-    def run(self, L_km: float, refine: int = 2, check_pd: bool = False, want_resid: bool = False, tol=None, corr="gaussian"):
+    def run(self, L_km: float, refine: int = 2, check_pd: bool = False, want_resid: bool = False, tol=None, corr="gaussian",
+            fields: bool = True, exact_factor: bool = False):
         """``refine``: the most refinement rounds the gain solve may take; it stops earlier once the float64 residual is
         below ``tol`` |d| (default: the handle's, 1e-6 -- ``oisat_set_refine_tol``; 0 runs every round).  ``corr``: the
-        correlation model, ``"gaussian"``, ``"gaspari_cohn"`` or ``"soar"`` (same L; module docstring)."""
+        correlation model, ``"gaussian"``, ``"gaspari_cohn"`` or ``"soar"`` (same L; module docstring).  ``fields=False``: stop
+        behind the gain solve, the increment is not spread (``z`` and the factor are all a likelihood needs).
+        ``exact_factor=True``: build and factor inside the 2^-52 envelope instead of the fp32 factor's own, narrower one, so that
+        the factor's log-determinant is that of S (``log_likelihood``)."""
         kind = self._kind = corr_kind(corr)
+        self._lik_ready = False
         c, lib, h = self.ctx, self.ctx.lib, self.ctx.h
         c.check(lib.oisat_set_refine_tol(h, REFINE_TOL if tol is None else float(tol)))      # per run: handles are shared
         c.check(lib.oisat_set_correlation(h, kind))                                          # ... and so is the model
@@ -339,7 +396,7 @@ class DenseAnalysis:
             c.check(lib.oisat_innovation(h, self.code, xb, self.ocell.ptr, self.oy.ptr, m, self.d.ptr))
         # this plan owns the latitude sort, so it may use the covariance's envelope: only the tiles inside it are evaluated
         # and factored, the sweeps of the gain solve walk inside it (OISAT_ENVELOPE=0: the dense path, in the library)
-        first = self._envelope(g, kind)
+        first = self._envelope(g, kind, exact_factor)
         # the build fills with zeros only what the last run's envelope left outside this one's (equal tables: nothing), the
         # factorization launch carries the first forward sweep of the gain solve (OISAT_FWD_IN_LAUNCH=0: it does not)
         claim, self._zero_claim = self._zero_claim, None       # (an exception below leaves no claim behind)
@@ -360,8 +417,10 @@ class DenseAnalysis:
         c.check(lib.oisat_set_obs_blocks(h, self.perm.ptr, m))                                  # per run: handles are shared
         c.check(lib.oisat_gain_solve(h, self.S.ptr, self.oxyz.ptr, self.osig.ptr, self.ovar.ptr, m, ld, g, self.d.ptr,
                                      int(refine), self.z.ptr, resid, self.olat.ptr))
-        c.check(lib.oisat_apply_increment_grid(h, self.code, self.gxyz.ptr, self.gsig.ptr, self._ny, self._nx, self.oxyz.ptr,
-                                               self.osig.ptr, self.z.ptr, m, g, xb, xa, inc, self.glat.ptr, self.olat.ptr))
+        if fields:
+            c.check(lib.oisat_apply_increment_grid(h, self.code, self.gxyz.ptr, self.gsig.ptr, self._ny, self._nx, self.oxyz.ptr,
+                                                   self.osig.ptr, self.z.ptr, m, g, xb, xa, inc, self.glat.ptr, self.olat.ptr))
+        self._lik_ready = bool(check_pd) and bool(exact_factor)
         if self._owns_S and enveloped.value == 1 and schedule.value in (SCHEDULE_ENV_DAG, SCHEDULE_ENV_DAG_FWD):
             nb = self.mp // NB
             if claim is None or not np.array_equal(claim[1], first[:nb]):
@@ -573,6 +632,99 @@ class DenseAnalysis:
         out = c.download(small.ptr, ((3 * K + 2) * K,), np.float64)
         prior, gy, ry = out[:3 * K * K].reshape(3, K, K)
         return assemble_functional_covariance(prior, gy, ry, out[3 * K * K:3 * K * K + K], out[3 * K * K + K:], ns)
+
+    # ---- the innovations' likelihood and the error scales it supports
+    def log_likelihood(self):
+        """-2 ln p(d) of the innovations under S = H B H^T + R as the last ``run(check_pd=True, exact_factor=True)`` analysed them
+        (anything else is a ``ValueError``: the narrower envelope's factor has the log-determinant of a truncated matrix).  One
+        diagonal reduction over the factor (``oisat_factor_logdet``) and two dot products (``oisat_rows_dot``).  Returns ``m``,
+        ``chi2`` (d^T S^-1 d from the refined z), ``chi2_per_obs``, ``logdet``, ``min_pivot`` (the factor's smallest diagonal
+        entry), ``neg2_log_likelihood`` (m ln 2 pi + logdet + chi2) and ``dd`` (|d|^2).  The mean of the innovations is not
+        estimated: a bias shows as chi2_per_obs > 1."""
+        if not self._lik_ready:
+            raise ValueError("log_likelihood() must follow run(check_pd=True, exact_factor=True)")
+        self.check()
+        c, lib, h, m = self.ctx, self.ctx.lib, self.ctx.h, self.m
+        out = self._functional_buffer("lik", 4 * 8)             # logdet | smallest pivot | d^T z | d^T d
+        c.check(lib.oisat_factor_logdet(h, self.S.ptr, m, self.mp, out.at(0)))
+        c.check(lib.oisat_rows_dot(h, self.d.ptr, m, 1, self.z.ptr, m, 1, m, out.at(16)))
+        c.check(lib.oisat_rows_dot(h, self.d.ptr, m, 1, self.d.ptr, m, 1, m, out.at(24)))
+        logdet, piv, chi2, dd = (float(v) for v in c.download(out.ptr, (4,), np.float64))
+        return {"m": m, "chi2": chi2, "chi2_per_obs": chi2 / m, "logdet": logdet, "min_pivot": piv,
+                "neg2_log_likelihood": m * float(np.log(2.0 * np.pi)) + logdet + chi2, "dd": dd}
+
+    def _likelihood_at(self, scale_b, scale_o, L_km, corr, refine, tol):
+        """One evaluation of the search: the likelihood dict at these scales with the solve's reported relative residual
+        beside it (``resid``), or None where the factorization met a non-positive pivot (``OISAT_ENOTPD``, or the status
+        words') or the solve ended above its tolerance -- a worse scale, not an error.  The status words are read and cleared
+        either way.  A time-out of the task graph or of a sweep says nothing about the scale: it raises ``OisatError``."""
+        c = self.ctx
+        self.set_error_scales(scale_b, scale_o)
+        try:
+            resid = self.run(L_km, refine=refine, check_pd=True, want_resid=True, tol=tol, corr=corr, fields=False, exact_factor=True)
+        except _hip.OisatError as e:
+            if e.code != _hip.ENOTPD:
+                raise
+            c.solve_status(clear=True)
+            return None
+        st = c.solve_status(clear=True)
+        if st.dag_timeouts or st.trsv_timeouts:
+            raise _hip.OisatError(f"fit_error_scales: {st.dag_timeouts} task-graph and {st.trsv_timeouts} triangular-solve time-out(s) "
+                                  f"at scale_b = {scale_b:g}, scale_o = {scale_o:g}")
+        if not st.clean:
+            return None
+        lik = self.log_likelihood()
+        lik["resid"] = float(resid[-1])
+        return lik if np.isfinite(lik["logdet"]) and np.isfinite(lik["chi2"]) and lik["chi2"] > 0.0 else None
+
+    def fit_error_scales(self, L_km, corr="gaussian", mode="background", bounds=(1e-2, 1e2), npts=9, wtol=0.01, refine=2, tol=None,
+                         want_se=True, fields=True):
+        """Maximum-likelihood scales of the loaded error variances.  With P = H B H^T at the loaded
+        scale and R = diag(So): ``mode="background"`` trusts R and minimises J_b(ln s) = log det(s P + R) + d^T (s P + R)^-1 d
+        -> ``scale_b`` = s, ``scale_o`` = 1; ``mode="both"`` takes S = a (rho P + R), where a = chi2(rho) / m in closed form, and
+        minimises the profile J_r(ln rho) = m ln(chi2(rho) / m) + log det(rho P + R) + m -> ``scale_o`` = a, ``scale_b`` = a rho
+        (the gain depends on rho alone; a scales the reported errors).  ``profile_search`` over ``bounds`` (``npts``, ``wtol``);
+        an evaluation is ``set_error_scales`` -> ``run(fields=False, exact_factor=True, check_pd=True)`` -> ``log_likelihood()``,
+        a failed one counts as +inf.  ``want_se``: two more evaluations for ``se_ln = sqrt(2 / J'')`` (``profile_se``; in "both"
+        mode that of ln rho).  Fewer than 32 observations, or no finite evaluation: ``found`` False, scales 1.  The call ends with
+        ``set_error_scales`` at the result and a run there (``fields``: with the increment spread), so that ``download()``, the
+        diagnostics and ``functional_covariance`` describe the ML analysis.  Returns ``mode``, ``scale_b``, ``scale_o``, ``ratio``
+        (scale_b / scale_o), ``se_ln``, ``found``, ``at_bound``, ``nevals``, ``evaluations`` ((ln s, J) in order, those of the
+        standard error included), ``residuals`` (per evaluation: the solve's reported relative residual, NaN where it failed) and
+        ``likelihood`` (``log_likelihood()`` at the result)."""
+        if mode not in FIT_SCALE_MODES:
+            raise ValueError(f"mode must be one of {FIT_SCALE_MODES}, not {mode!r}")
+        corr_kind(corr)
+        m, both = self.m, mode == "both"
+        out = {"mode": mode, "scale_b": 1.0, "scale_o": 1.0, "ratio": 1.0, "se_ln": float("inf"), "found": False, "at_bound": False,
+               "nevals": 0, "evaluations": [], "residuals": []}
+        liks, evals = {}, out["evaluations"]
+        self.check()                                           # (an earlier unchecked run's failure is not this search's)
+
+        def objective(x):
+            lik = liks[x] = self._likelihood_at(float(np.exp(x)), 1.0, L_km, corr, refine, tol)
+            J = float("inf")
+            if lik is not None:
+                J = m * float(np.log(lik["chi2"] / m)) + lik["logdet"] + m if both else lik["logdet"] + lik["chi2"]
+            evals.append((float(x), J))
+            out["residuals"].append(lik["resid"] if lik is not None else float("nan"))
+            return J
+
+        if m >= FIT_SCALE_MIN_OBS:
+            res = profile_search(objective, bounds=bounds, npts=npts, wtol=wtol)
+            if np.isfinite(res["J"]):
+                x = res["x"]
+                rho = float(np.exp(x))
+                a = liks[x]["chi2"] / m if both else 1.0
+                out.update(scale_b=a * rho, scale_o=a, ratio=rho, found=True, at_bound=res["at_bound"])
+                if want_se:
+                    out["se_ln"] = profile_se(objective, x, res["J"])
+            out["nevals"] = len(evals)
+        # the analysis at the result, checked as any other: a failure here raises
+        self.set_error_scales(out["scale_b"], out["scale_o"])
+        self.run(L_km, refine=refine, check_pd=True, tol=tol, corr=corr, fields=fields, exact_factor=True)
+        out["likelihood"] = self.log_likelihood()
+        return out
 
     # ---- outputs
     def check(self):
@@ -1250,7 +1402,7 @@ class MonthTileBatch:
 
 
 def OI_dense(Xa, Y, Sa, So, lat, lon, L_km, scale=1.0, refine=2, obs=None, dtype=None, want_error=False, tol=None,
-             corr="gaussian", nprobe=256, seed=0, superob=None, superob_rho=0.0, regions=None):
+             corr="gaussian", nprobe=256, seed=0, superob=None, superob_rho=0.0, regions=None, likelihood=False, fit_scale=None):
     """Dense-covariance analysis with the reference's gridded argument convention.
 
     ``Xa, Sa``: (ny, nx) background and its variance; ``Y, So``: (ny, nx) observations and their
@@ -1274,8 +1426,19 @@ def OI_dense(Xa, Y, Sa, So, lat, lon, L_km, scale=1.0, refine=2, obs=None, dtype
     background and the EXACT error of that mean before and after the analysis, ``prior_sd`` / ``posterior_sd``, with the full
     ``prior_cov`` / ``posterior_cov`` between the regions and the solves' ``resid`` (``DenseAnalysis.functional_covariance``;
     DESIGN.md section 4.2h).  The functionals are taken on whatever system the plan solved: ``obs=`` and ``superob=`` alike.
+    ``likelihood=True``: the analysis factors inside the 2^-52 envelope (``run(exact_factor=True)``) and ``info["likelihood"]``
+    holds ``DenseAnalysis.log_likelihood()``: chi2, chi2_per_obs, logdet, neg2_log_likelihood of the innovations under the
+    analysis' own S.  ``fit_scale``: None (default) | ``"background"`` | ``"both"``: the error scales are
+    first estimated by maximum likelihood on whatever system the plan holds -- with ``superob=`` the superobservations --
+    (``DenseAnalysis.fit_error_scales`` -> ``info["scale_fit"]``), and the analysis, ``want_error`` and ``regions`` are then those
+    of ``scale * scale_b`` and ``So * scale_o``: the very call ``OI_dense(..., scale=scale * scale_b, likelihood=True)`` (with
+    ``So * scale_o`` under ``"both"``) would make, with ``info["likelihood"]`` at the optimum.  Without a usable observation
+    ``scale_fit`` is ``{"found": False, "scale_b": 1.0, "scale_o": 1.0, ...}`` and ``likelihood`` is None.
     """
     corr_kind(corr)                                           # (ValueError before anything is touched)
+    if fit_scale is not None and fit_scale not in FIT_SCALE_MODES:
+        raise ValueError(f"fit_scale is None, 'background' or 'both', got {fit_scale!r}")
+    want_lik = bool(likelihood) or fit_scale is not None
     if regions is not None:                                   # (and so are a bad label map's)
         reg_ids, reg_W = region_weights(regions, lat, valid=np.isfinite(np.asarray(Xa)))
     mc = isinstance(want_error, str)
@@ -1299,16 +1462,22 @@ def OI_dense(Xa, Y, Sa, So, lat, lon, L_km, scale=1.0, refine=2, obs=None, dtype
     xa_f = np.where(np.isfinite(Xa), Xa, 0.0)
     sa_f = np.where(np.isfinite(Sa), Sa, 0.0)
     so = None
-    if so_box is not None and not (so_box == "auto" and cell.size <= so_max):
+
+    def merge(scale, ovar):
+        """The superobservations at this scale and these observation variances, and what ``info["superob"]`` says of them."""
         # innovations as the plain path forms them (oisat_innovation: y - x_b[cell] with x_b in the field dtype) and sigma_b
         # as load_obs takes it (sqrt(scale Sa) of the cell)
+        nonlocal so_box
         d_raw = np.asarray(oy, dtype=np.float64) - np.ravel(xa_f).astype(dt).astype(np.float64)[cell]
         sig_raw = np.sqrt(float(scale) * np.ravel(np.asarray(sa_f, dtype=np.float64)))[cell]
         if so_box == "auto":
             so_box = superob_auto_box(olat, olon, d_raw, sig_raw, ovar, so_max)
         so = _superob_fn(olat, olon, d_raw, sig_raw, ovar, so_box, rho=superob_rho)
-        so_info = {"box_deg": so["box_deg"], "rho": so["rho"], "nobs_raw": so["nobs_raw"], "nobs": so["nobs"],
-                   "count": so["count"], "spread": so["spread"], "index": so["index"]}
+        return so, {"box_deg": so["box_deg"], "rho": so["rho"], "nobs_raw": so["nobs_raw"], "nobs": so["nobs"],
+                    "count": so["count"], "spread": so["spread"], "index": so["index"]}
+
+    if so_box is not None and not (so_box == "auto" and cell.size <= so_max):
+        so, so_info = merge(scale, ovar)
     if cell.size == 0 or (so is not None and so["nobs"] == 0):
         # a month without a single usable observation: nothing to spread, x_a = x_b
         _hip.context()                 # (still no CPU path: fail here if the library or the GPU is missing)
@@ -1321,6 +1490,11 @@ def OI_dense(Xa, Y, Sa, So, lat, lon, L_km, scale=1.0, refine=2, obs=None, dtype
                              error_method="mc", nprobe=int(nprobe))
         if so is not None:
             extra["superob"] = so_info
+        if want_lik:
+            extra["likelihood"] = None
+        if fit_scale is not None:
+            extra["scale_fit"] = {"mode": fit_scale, "scale_b": 1.0, "scale_o": 1.0, "ratio": 1.0, "se_ln": float("inf"), "found": False,
+                                  "at_bound": False, "nevals": 0, "evaluations": [], "residuals": [], "likelihood": None}
         if regions is not None:        # nothing observed: the error of a regional mean stays the background's
             plan = DenseAnalysis(lat, lon, max_obs=1, dtype=dt)
             plan.load_background(xa_f, sa_f, scale=scale)
@@ -1331,14 +1505,33 @@ def OI_dense(Xa, Y, Sa, So, lat, lon, L_km, scale=1.0, refine=2, obs=None, dtype
                 {"nobs": 0, "residuals": [], "cells": cell, "z": np.empty(0), **extra})
     plan = DenseAnalysis(lat, lon, max_obs=int(cell.size if so is None else so["nobs"]), dtype=dt,
                          diag_chunk_rows=4096 if want_error and not mc else 0)
-    plan.load_background(xa_f, sa_f, scale=scale)
-    if so is None:
-        plan.load_obs(olat, olon, cell, oy, ovar)
-    else:                              # one row per superobservation: a point observation at the members' weighted centroid
-        plan.load_obs_direct(so["lat"], so["lon"], so["sigma_b"], so["var"], so["d"])
-    resid = plan.run(L_km, refine=refine, check_pd=True, want_resid=True, tol=tol, corr=corr)
-    xb, inc = plan.download()
+
+    def load():
+        plan.load_background(xa_f, sa_f, scale=scale)
+        if so is None:
+            plan.load_obs(olat, olon, cell, oy, ovar)
+        else:                          # one row per superobservation: a point observation at the members' weighted centroid
+            plan.load_obs_direct(so["lat"], so["lon"], so["sigma_b"], so["var"], so["d"])
+
+    load()
     extra = {}
+    if fit_scale is not None:
+        # the search runs on the plan as loaded; the analysis at its result is then loaded the way a caller who passes
+        # scale * scale_b (and So * scale_o) would load it, so that the two agree to the bit
+        fit = extra["scale_fit"] = plan.fit_error_scales(L_km, corr=corr, mode=fit_scale, refine=refine, tol=tol, fields=False)
+        if fit["found"]:
+            scale = float(scale) * fit["scale_b"]
+            if fit["scale_o"] != 1.0:
+                ovar = np.asarray(ovar, dtype=np.float64) * fit["scale_o"]
+            if so is not None:
+                so, so_info = merge(scale, ovar)
+                if so["nobs"] != plan.m:
+                    raise RuntimeError("the superobservations changed with the error scales")
+            load()
+    resid = plan.run(L_km, refine=refine, check_pd=True, want_resid=True, tol=tol, corr=corr, exact_factor=want_lik)
+    xb, inc = plan.download()
+    if want_lik:
+        extra["likelihood"] = plan.log_likelihood()
     if want_error:                     # the other two members of OI's 4-tuple: averaging kernel and sqrt(Sb)
         # diag(K H) at a cell = sum over the observations INSIDE that cell of diag(H K) at the observation
         # ((B H^T S^-1)[cell(a), a] = (H B H^T S^-1)[a, a]); with one observation per cell -- the reference's
@@ -1354,7 +1547,7 @@ def OI_dense(Xa, Y, Sa, So, lat, lon, L_km, scale=1.0, refine=2, obs=None, dtype
             np.add.at(ak_sum, cell[mem], ak_obs[si] * (1.0 / np.asarray(ovar, dtype=np.float64)[mem]) / so["W"][si])
         ak = np.full(Xa.size, np.nan)
         ak[cell] = ak_sum[cell]
-        extra = {"ak": ak.reshape(np.shape(Xa)), "err": est["err"] if mc else plan.posterior_error(), "ak_obs": ak_obs}
+        extra.update(ak=ak.reshape(np.shape(Xa)), err=est["err"] if mc else plan.posterior_error(), ak_obs=ak_obs)
         if mc:
             extra.update(err_se=est["err_se"], ak_obs_se=est["ak_obs_se"], error_method="mc", nprobe=est["nprobe"])
     if regions is not None:
@@ -1539,6 +1732,62 @@ def fit_correlation(cg, corr="gaussian", L_bounds=None, min_count=30):
     out.update(L_km=L, scale=s, rms=float(np.sqrt(J / np.sum(n))), found=bool(s > 0.0),
                at_bound=bool(abs(x - grid[0]) <= 1e-6 or abs(x - grid[-1]) <= 1e-6))
     return out
+
+
+# ---- maximum-likelihood error scales: the one-dimensional search -----------------------------------
+FIT_SCALE_MODES = ("background", "both")
+FIT_SCALE_MIN_OBS = 32                               # fewer observations: no fit is made
+PROFILE_SE_STEP = 0.25                               # the second difference of the profile is taken at ln s +- this
+
+
+def profile_search(objective, bounds=(1e-2, 1e2), npts=9, wtol=0.01, max_evals=32):
+    """Minimise ``objective(ln s)`` over ``bounds`` on s, host only: ``npts`` log-spaced points, then a golden-section search on
+    ln s between the best point's neighbours until the bracket is below ``wtol`` (the scheme of ``fit_correlation``) or
+    ``max_evals`` evaluations are spent.  An objective of +inf (a factorization that met a non-positive pivot, a solve that did
+    not converge) is simply worse than any finite one.  -> dict ``x`` (ln of the minimiser: the best point EVALUATED, NaN if none
+    was finite), ``J`` (the objective there), ``evaluations`` (every (ln s, J) in order), ``nevals`` and ``at_bound`` (the minimum
+    is within ``wtol`` of an end of ``bounds``).  With the defaults: 21 to 23 evaluations."""
+    lo, hi = float(bounds[0]), float(bounds[1])
+    if not (0.0 < lo < hi and np.isfinite(hi)):
+        raise ValueError(f"bounds must be 0 < low < high, not {bounds!r}")
+    npts, max_evals = int(npts), int(max_evals)
+    if npts < 3 or max_evals < npts + 2 or not wtol > 0.0:
+        raise ValueError(f"profile_search needs npts >= 3, max_evals >= npts + 2 and wtol > 0, not {npts}, {max_evals}, {wtol!r}")
+    evals = []
+
+    def J_at(x):
+        J = float(objective(float(x)))
+        evals.append((float(x), J if J == J else float("inf")))         # (a NaN counts as a failed evaluation)
+        return evals[-1][1]
+
+    grid = np.linspace(np.log(lo), np.log(hi), npts)
+    Jg = [J_at(x) for x in grid]
+    i = int(np.argmin(Jg))
+    a, b = float(grid[max(i - 1, 0)]), float(grid[min(i + 1, npts - 1)])
+    inv_phi = 0.5 * (5.0 ** 0.5 - 1.0)
+    x1, x2 = b - inv_phi * (b - a), a + inv_phi * (b - a)
+    J1, J2 = J_at(x1), J_at(x2)
+    while b - a > wtol and len(evals) < max_evals:
+        if J1 <= J2:
+            b, x2, J2 = x2, x1, J1
+            x1 = b - inv_phi * (b - a)
+            J1 = J_at(x1)
+        else:
+            a, x1, J1 = x1, x2, J2
+            x2 = a + inv_phi * (b - a)
+            J2 = J_at(x2)
+    x, J = min(evals, key=lambda e: e[1])
+    if not np.isfinite(J):
+        x = float("nan")
+    return {"x": x, "J": J, "evaluations": evals, "nevals": len(evals),
+            "at_bound": bool(abs(x - grid[0]) <= wtol or abs(x - grid[-1]) <= wtol)}
+
+
+def profile_se(objective, x, Jx, h=PROFILE_SE_STEP):
+    """Standard error of the minimiser ``x`` of a -2 ln likelihood profile: sqrt(2 / J'') with J'' the central second
+    difference (J(x + h) - 2 J(x) + J(x - h)) / h^2, two more evaluations.  J'' <= 0, or a failed evaluation: +inf."""
+    d2 = (float(objective(x + h)) - 2.0 * float(Jx) + float(objective(x - h))) / (h * h)
+    return float(np.sqrt(2.0 / d2)) if np.isfinite(d2) and d2 > 0.0 else float("inf")
 
 
 def estimate_corr_length(Xa, Y, Sa, So, lat, lon, scale=1.0, corr="gaussian", **kw):

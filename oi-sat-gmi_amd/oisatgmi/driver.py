@@ -115,6 +115,13 @@ class oisatgmi(object):
     #               after and the EXACT error of that mean, error correlations between cells included, with the covariances
     #               between the regions (dense.DenseAnalysis.functional_covariance); region_OI,
     #               oi_info["regions"]
+    #   scale       attribute `oi_scale`       | env OISAT_OI_SCALE       knee (default) | ml | ml:both  (dense only; diag, tiled:
+    #               ValueError): knee = the regularisation factor of the reference's knee sweep, as before.  ml: that factor is
+    #               the starting point, and the amplitude of B is then estimated by maximum likelihood of the month's innovations
+    #               under S = s H B H^T + R itself (dense.DenseAnalysis.fit_error_scales); ml:both also
+    #               estimates a common inflation of the observation errors (the masks of error_OI / ak_OI keep So as given).
+    #               The knee still feeds the `auto` length and the QC, which come first.  oi_info["scale"] = knee x scale_b,
+    #               oi_info["scale_knee"], oi_info["scale_fit"], oi_info["likelihood"]
     def _oi_setting(self, attr, env, default, cast=str):
         v = getattr(self, attr, None)
         if v is None:
@@ -170,6 +177,16 @@ class oisatgmi(object):
         return {"k_buddy": k}
 
     @staticmethod
+    def _scale_setting(v):
+        """``OISAT_OI_SCALE`` / ``oi_scale`` -> ``None`` for ``knee``, ``"background"`` for ``ml``, ``"both"`` for ``ml:both`` (the
+        ``fit_scale`` of ``dense.OI_dense``); anything else is a ``ValueError``."""
+        modes = {"knee": None, "ml": "background", "ml:both": "both"}
+        try:
+            return modes[str(v).strip().lower()]
+        except KeyError:
+            raise ValueError(f"OISAT_OI_SCALE / oi_scale: expected knee, ml or ml:both, not {v!r}") from None
+
+    @staticmethod
     def _superob_setting(v):
         """``OISAT_OI_SUPEROB`` / ``oi_superob`` -> ``None`` for ``off``, the box size in degrees (a float in (0, 180]) for
         ``<deg>``, ``"auto:<max_obs>"`` for ``auto`` (max_obs = 100 000) / ``auto:<max_obs>`` (a positive integer); anything else
@@ -222,6 +239,10 @@ class oisatgmi(object):
         if regions is not None and mode in ("diag", "tiled"):
             raise ValueError("OISAT_OI_REGIONS / oi_regions belongs to the dense mode; the error of a regional mean needs the error "
                              "correlations between cells, and regions cross tiles (off)")
+        fit_scale = self._oi_setting("oi_scale", "OISAT_OI_SCALE", "knee", self._scale_setting)
+        if fit_scale is not None and mode in ("diag", "tiled"):
+            raise ValueError("OISAT_OI_SCALE / oi_scale = ml belongs to the dense mode; the tiles share the observations of their "
+                             "halos, so their likelihoods do not add (knee)")
         if mode == "diag":
             self.ctm_averaged_vcd_corrected, self.ak_OI, self.increment_OI, self.error_OI = OI(
                 xa, y, Sa, So, regularization_on=True, reg_index=reg_index)
@@ -260,7 +281,7 @@ class oisatgmi(object):
             sl = (slice(None), slice(None)) + tail
             res, info = self._oi_spatial(mode, xa[sl], y[sl], np.asarray(Sa)[sl], np.asarray(So)[sl], lat, lon, L, tile,
                                          unobserved, reg_index, want_error, corr=corr, nprobe=nprobe, qc=qc,
-                                         superob=superob, regions=regions)
+                                         superob=superob, regions=regions, fit_scale=fit_scale)
             for o, r in zip(outs, res):
                 o[sl] = r
             infos.append(info)
@@ -271,12 +292,14 @@ class oisatgmi(object):
 
     @staticmethod
     def _oi_spatial(mode, xa, y, Sa, So, lat, lon, L, tile, unobserved, reg_index, want_error, corr="gaussian", nprobe=256,
-                    qc=None, superob=None, regions=None):
+                    qc=None, superob=None, regions=None, fit_scale=None):
         """One (ny, nx) Gaussian-B analysis -> ((Xb, AK, increment, error), info) in the reference's attribute order.  ``qc``
         (``_qc_setting``): not None = the innovations are checked first and the rejected cells analysed as unobserved, on a
         copy of ``y``.  ``superob`` (``_superob_setting``, dense mode): not None = the kept observations are merged into
         superobservations ahead of the analysis; the ``observed`` mask stays the raw one.  ``regions`` (dense mode): a label
-        map; ``info["regions"]`` then holds the regional means and their exact errors (``dense.OI_dense``)."""
+        map; ``info["regions"]`` then holds the regional means and their exact errors (``dense.OI_dense``).  ``fit_scale``
+        (``_scale_setting``, dense mode): not None = the knee scale is only the starting point of a maximum-likelihood fit of the
+        error scales; ``info["scale"]`` is then knee x scale_b, beside ``scale_knee``, ``scale_fit`` and ``likelihood``."""
         from . import dense
         from . import optimal_interpolation as oi_mod
         index, scale, curve, found = oi_mod.regularization_pick(Sa, So, reg_index)
@@ -313,7 +336,11 @@ class oisatgmi(object):
                     print("No correlation length could be fitted to the kept innovations; using 300 km")
         if mode == "dense":
             xb, inc, info = dense.OI_dense(xa, y, Sa, So, lat, lon, L, scale=scale, want_error=want_error, corr=corr,
-                                           nprobe=nprobe or 256, superob=superob, regions=regions)
+                                           nprobe=nprobe or 256, superob=superob, regions=regions, fit_scale=fit_scale)
+            if fit_scale is not None:
+                fit = info["scale_fit"]
+                print(f"The maximum-likelihood error scales are {fit['scale_b']:g} (background) and {fit['scale_o']:g} (observations)"
+                      + ("" if fit["found"] else "; no fit was made"))
             so = info.get("superob")
             if so is not None and so["box_deg"] * dense.KM_PER_DEG > 0.5 * L:      # (the knee_found convention: say so once)
                 print(f"The superobservation box of {so['box_deg']:g} degrees ({so['box_deg'] * dense.KM_PER_DEG:.0f} km) is wider "
@@ -329,6 +356,9 @@ class oisatgmi(object):
         # the dense analysis simply does not use such an observation, and AK = 0 as in the reference; Sa*reg = 0 makes the
         # reference's AK = 1 - Sb/(Sa*reg) a 0/0 (optimal_interpolation.py:31): mirrored.
         observed = np.isfinite(y) & ~np.isnan(So) & np.isfinite(xa) & np.isfinite(Sa)
+        scale_knee = scale
+        if fit_scale is not None:                               # from here on the scale is the analysis' own
+            scale = scale * info["scale_fit"]["scale_b"]
         if want_error:
             ak[observed & np.isinf(So)] = 0.0
             ak[observed & (Sa * scale == 0)] = np.nan
@@ -352,6 +382,8 @@ class oisatgmi(object):
             out_info["superob"] = info["superob"]
         if info.get("regions") is not None:
             out_info["regions"] = info["regions"]
+        if fit_scale is not None:
+            out_info.update(scale_knee=scale_knee, scale_fit=info["scale_fit"], likelihood=info["likelihood"])
         return (xb, ak, inc, err), out_info
 
     def scaling_factor(self):
