@@ -754,6 +754,39 @@ int oisat_functional_gather(oisat_ctx* h, const double* pxyz, const double* psig
 int oisat_rows_dot(oisat_ctx* h, const double* A, int64_t lda, int64_t na, const double* B, int64_t ldb, int64_t nb,
                    int64_t len, double* out);
 
+/* ---- posterior ensembles by Matheron's rule (csrc/dense_ensemble.hip) -----------------------------
+ * A member is a draw from N(x_a, A), A = B - B H^T S^-1 H B:
+ *   delta_k = xi_k - B H^T S^-1 (H xi_k + eps_k),   xi_k ~ N(0, B),  eps_k ~ N(0, R),
+ * with the prior draw a random-feature field of F frequencies from the correlation's spectral measure in R^3.  The library
+ * draws nothing: frequencies, phases and noise are arguments (oisatgmi/dense.py: ensemble_draws, posterior_ensemble), and the
+ * solve in the middle is oisat_trsm_rows then oisat_trsm_rows_bwd on the panel.  Both calls are asynchronous on the handle's
+ * stream and use no workspace; no workgroup waits for another; same inputs, same bits.
+ *
+ * oisat_field_sample: out[k][p] = scale_p sqrt(2 / F) sum_{f < F} cos 2 pi (omega_kf . x_p + phi_kf) + sqrt(nscale_p) noise[k][p],
+ * k < nmember, p < npts.  pxyz: dev double[3 * npts], unit vectors x | y | z; omega: dev double[nmember][3][nfeature] -- per
+ * member the x components of its F frequencies, then y, then z -- in TURNS per unit chord (angular frequency / 2 pi); phase: dev
+ * double[nmember][nfeature] in turns; scale: dev double[npts] or NULL (= 1); noise: dev float[nmember][ld] with nscale: dev
+ * double[npts], both given or both NULL (no second term); out: dev float[nmember][ld], ld >= npts, the columns npts..ld are
+ * written as exact zeros (the row sweeps pass them through).  Per point and feature the phase is formed in double (three fused
+ * multiply-adds onto phi, x first) and reduced by its nearest integer in double; the remainder is narrowed to float, its
+ * cosine is an fp32 one and the F cosines are added in fp32 in the order of f; the closing expression is double, rounded
+ * once.  nfeature >= 1, 1 <= nmember <= 65535, npts >= 1, anything else is OISAT_EINVAL with nothing launched.
+ *
+ * oisat_member_spread: P[k][i] <- P[k][i] - gsig_i sum_a C(i,a) osig_a U[k][a] in place, under the handle's correlation model,
+ * P: dev float[nmember][ldp] (ldp >= the number of cells), U: dev float[nmember][ldu] (ldu >= m); sum2_out[i] (+)= sum_k P[k][i]^2
+ * and sum4_out[i] (+)= sum_k P[k][i]^4 of the UPDATED values, dev double[n]; accumulate = 0 overwrites.  oisat_probe_spread with
+ * the per-vector sum stored instead of squared -- one kernel, csrc/dense_spread.inc -- hence its patches (nx > 0: 32 x 8; nx = 0:
+ * runs of 256), its latitude window and cull (glat / olat_sorted, both or the pair counts as NULL), its number formats (the sum
+ * over a in fp32; the subtraction in double, rounded once to the float that is stored and squared) and its rule for nmember: a
+ * multiple of 32 with 32 <= nmember <= 4096, anything else is OISAT_EINVAL. */
+int oisat_field_sample(oisat_ctx* h, const double* pxyz, int64_t npts, const double* scale, const double* omega,
+                       const double* phase, int64_t nfeature, int64_t nmember, const float* noise, const double* nscale,
+                       float* out, int64_t ld);
+int oisat_member_spread(oisat_ctx* h, const double* gxyz, const double* gsig, int64_t ny, int64_t nx, const double* oxyz,
+                        const double* osig, const float* U, int64_t nmember, int64_t ldu, int64_t m, double g,
+                        const double* glat, const double* olat_sorted, float* P, int64_t ldp, int accumulate,
+                        double* sum2_out, double* sum4_out);
+
 /* The likelihood of the innovations under the analysis' own model (csrc/dense_likelihood.hip):
  * -2 ln p(d) = m ln 2 pi + log det S + d^T S^-1 d with S = H B H^T + R = L L^T.  chi^2 = d^T z and |d|^2 are oisat_rows_dot with
  * na = nb = 1; the log-determinant is

@@ -15,7 +15,7 @@ namespace {
 #include "dense_solve_dev.inc"
 
 // ---- out[k][p] = psig_p sum_j C(p, j) ssig_j W[k][j] for a group of G functionals at once (oisat_functional_gather) ---------
-// probe_spread_kernel (dense_cov.hip) with the roles named anew and double sums: thread = one target, 256 consecutive targets
+// probe_spread_kernel (dense_spread.inc) with the roles named anew and double sums: thread = one target, 256 consecutive targets
 // per workgroup, the latitude window of the block's span and the bounding-sphere cull (block_sphere<1>), the surviving sources
 // staged in LDS as double coordinates + index in candidate order.  Per group of G functionals the staged sources pass in
 // sub-chunks of 64 whose weights ssig_j W[k][j] are gathered into an LDS image ([64][G] doubles, read back as wave-uniform

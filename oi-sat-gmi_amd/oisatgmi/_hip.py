@@ -142,6 +142,9 @@ SIGNATURES = {
     "oisat_functional_gather": (C.c_int, [_c_ctx, _ptr, _ptr, _ptr, _i64, _ptr, _ptr, _ptr, _i64, _ptr, _i64, _i64, C.c_double, _ptr,
                                           _i64]),
     "oisat_rows_dot": (C.c_int, [_c_ctx, _ptr, _i64, _i64, _ptr, _i64, _i64, _i64, _ptr]),
+    "oisat_field_sample": (C.c_int, [_c_ctx, _ptr, _i64, _ptr, _ptr, _ptr, _i64, _i64, _ptr, _ptr, _ptr, _i64]),
+    "oisat_member_spread": (C.c_int, [_c_ctx, _ptr, _ptr, _i64, _i64, _ptr, _ptr, _ptr, _i64, _i64, _i64, C.c_double, _ptr, _ptr,
+                                      _ptr, _i64, C.c_int, _ptr, _ptr]),
     "oisat_factor_logdet": (C.c_int, [_c_ctx, _ptr, _i64, _i64, _ptr]),
     "oisat_apply_increment": (C.c_int, [_c_ctx, C.c_int, _ptr, _ptr, _i64, _ptr, _ptr, _ptr, _i64, C.c_double, _ptr,
                                         _ptr, _ptr, _ptr, _ptr]),

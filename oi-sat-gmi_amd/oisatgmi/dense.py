@@ -30,6 +30,9 @@ correlations between cells included (csrc/dense_functional.hip: ``oisat_function
 d^T S^-1 d, log det S from the factor's diagonal (csrc/dense_likelihood.hip: ``oisat_factor_logdet``) and -2 ln p(d);
 ``OI_dense(..., fit_scale=)`` / ``DenseAnalysis.fit_error_scales`` estimate the amplitude of B -- and, on request, a common inflation of
 R -- by maximum likelihood (``set_error_scales``, ``profile_search``).
+``OI_dense(..., ensemble=K)`` / ``DenseAnalysis.posterior_ensemble`` draw K members from the analysis' own error distribution
+N(x_a, A) by Matheron's rule, with random-feature prior draws (``ensemble_draws``; csrc/dense_ensemble.hip: ``oisat_field_sample``,
+``oisat_member_spread``).
 """
 from __future__ import annotations
 
@@ -85,6 +88,59 @@ def combine_error_estimates(sig2, q, q_var, obs_cell, R, s, s_var):
         A_var[ci[take]] = v2[take]
         hi[ci] = np.minimum(hi[ci], R[single])
     return np.clip(A, 0.0, hi), A_var
+
+
+def _ensemble_sizes(nmember, nfeature):
+    """``(K, F)`` of a posterior ensemble as ints: K a positive multiple of 32 (the member spread's groups), F >= 1;
+    anything else is a ``ValueError``."""
+    try:
+        K, F = int(nmember), int(nfeature)
+        if K != nmember or F != nfeature:
+            raise ValueError
+    except (TypeError, ValueError):
+        raise ValueError(f"nmember and nfeature must be integers, not {nmember!r}, {nfeature!r}") from None
+    if K < 32 or K % 32:
+        raise ValueError(f"nmember must be a positive multiple of 32, got {nmember}")
+    if F < 1:
+        raise ValueError(f"nfeature must be at least 1, got {nfeature}")
+    return K, F
+
+
+def ensemble_draws(corr, L_km, members, nfeature, m, seed):
+    """The random numbers of the posterior ensemble, pure NumPy: for every member number k of
+    ``members`` (a range or a list) the ``nfeature`` frequencies and phases of its random-feature prior draw and the ``m``
+    unit normals of its observation noise -> ``omega`` (K, F, 3), ``phase`` (K, F), ``eps`` (K, m), all float64.
+
+    Member k draws from ``np.random.Generator(np.random.Philox(key=[seed, k]))`` in the fixed order omega, phase, eps, so it is
+    the same member whatever the ensemble's size and whichever panel it lands in.  ``omega`` is in TURNS per unit chord
+    (angular frequency / 2 pi), from the spectral measure of the correlation in R^3 with a = R_earth / L and n ~ N(0, I_3):
+    ``gaussian`` a n; ``soar`` a n / sqrt(w . w) with an independent w ~ N(0, I_3) -- the trivariate Student t of 3 degrees of
+    freedom, the spectral measure of (1 + r/L) exp(-r/L).  ``phase`` is uniform on [0, 1), in turns; ``eps`` belongs to the
+    observations in the device's order (ascending latitude).  ``gaspari_cohn`` is a ``ValueError``."""
+    kind = corr_kind(corr)
+    if kind == CORRELATIONS["gaspari_cohn"]:
+        raise ValueError("the spectral measure of gaspari_cohn has no closed-form sampler: the posterior ensemble supports "
+                         "gaussian and soar")
+    F, m = int(nfeature), int(m)
+    if F < 1 or m < 0:
+        raise ValueError(f"nfeature must be at least 1 and m non-negative, got {nfeature}, {m}")
+    members = [int(k) for k in members]
+    if any(k < 0 for k in members):
+        raise ValueError("member numbers are non-negative")
+    a = EARTH_RADIUS_KM / float(L_km) / (2.0 * np.pi)
+    omega = np.empty((len(members), F, 3))
+    phase = np.empty((len(members), F))
+    eps = np.empty((len(members), m))
+    for i, k in enumerate(members):
+        rng = np.random.Generator(np.random.Philox(key=[int(seed) & (2 ** 64 - 1), k]))
+        n = rng.standard_normal((F, 3))
+        if kind == CORRELATIONS["soar"]:
+            w = rng.standard_normal((F, 3))
+            n /= np.sqrt((w * w).sum(axis=1))[:, None]
+        omega[i] = a * n
+        phase[i] = rng.random(F)
+        eps[i] = rng.standard_normal(m)
+    return omega, phase, eps
 
 
 def unit_vectors(lat_deg, lon_deg) -> np.ndarray:
@@ -147,6 +203,11 @@ def latitude_order(lat_deg) -> np.ndarray:
 def decay_constant(L_km: float) -> float:
     """g in C = exp(-g * chord^2) for a correlation length L (km)."""
     return 0.5 * (EARTH_RADIUS_KM / float(L_km)) ** 2
+
+
+def corr_length_of(g: float) -> float:
+    """The correlation length (km) of a decay constant: the inverse of ``decay_constant``."""
+    return EARTH_RADIUS_KM / float(np.sqrt(2.0 * float(g)))
 
 
 def regular_grid_cell(lat2, lon2, obs_lat, obs_lon):
@@ -522,6 +583,104 @@ class DenseAnalysis:
                 "ak_obs": self._unsort(1.0 - R * s), "ak_obs_se": self._unsort(R * np.sqrt(s_var)), "nprobe": K,
                 "q": q.reshape(self.shape), "q_se": np.sqrt(q_var).reshape(self.shape),
                 "s": self._unsort(s), "s_se": self._unsort(np.sqrt(s_var))}
+
+    # ---- posterior ensembles by Matheron's rule
+    def _ensemble_panels(self, K, F, seed, keep, L_km, corr, solve):
+        """The panel loop of ``posterior_ensemble`` (``solve``: the whole rule) and ``prior_ensemble`` (step 4 alone) ->
+        ``(sum2, sum4, deviations or None)`` with the per-cell sums of squares and fourth powers over the K members in float64."""
+        c, lib, h = self.ctx, self.ctx.lib, self.ctx.h
+        n, ny, nx = self.n, self._ny, self._nx
+        m, mp = (self.m, self.mp) if solve else (0, 0)
+        rows_max = min(K, PROBE_PANEL)
+        P = self._functional_buffer("ens_P", rows_max * n * 4)                 # one panel of members on the grid
+        feat = self._functional_buffer("ens_feat", rows_max * 4 * F * 8)       # omega [rows][3][F] | phase [rows][F]
+        sums = self._functional_buffer("ens_sums", 2 * n * 8)
+        if solve:
+            X = self._functional_buffer("ens_X", PROBE_PANEL * self.mp_max * 4)    # the panel at the observations
+            noise = self._functional_buffer("ens_noise", PROBE_PANEL * self.mp_max * 4)
+            c.check(lib.oisat_set_correlation(h, self._kind))                  # (the model of the run that left the factor)
+        dev = np.empty((K, n), dtype=np.float32) if keep else None
+        s2, s4 = np.zeros(n), np.zeros(n)
+        for p0 in range(0, K, PROBE_PANEL):
+            rows = min(PROBE_PANEL, K - p0)                                    # live rows: a multiple of 32
+            omega, phase, eps = ensemble_draws(corr, L_km, range(p0, p0 + rows), F, m, seed)
+            c.upload_into(feat.ptr, np.ascontiguousarray(omega.transpose(0, 2, 1)), dtype=np.float64)
+            c.upload_into(feat.at(rows * 3 * F * 8), phase, dtype=np.float64)
+            om, ph = feat.ptr, feat.at(rows * 3 * F * 8)
+            c.check(lib.oisat_field_sample(h, self.gxyz.ptr, n, self.gsig.ptr, om, ph, F, rows, None, None, P.ptr, n))
+            if not solve:
+                got = c.download(P.ptr, (rows, n), np.float32)
+                d64 = got.astype(np.float64) ** 2
+                s2 += d64.sum(axis=0)
+                s4 += (d64 * d64).sum(axis=0)
+            else:
+                # the sweeps want 128 rows.  oisat_field_sample writes every one of the mp columns of the live rows (zeros from m
+                # on), so only a short panel needs the memset: it makes the rows behind the live ones zero rows
+                if rows < PROBE_PANEL:
+                    c.check(lib.oisat_memset(h, X.ptr, 0, PROBE_PANEL * mp * 4))
+                e32 = np.zeros((rows, mp), dtype=np.float32)
+                e32[:, :m] = eps
+                c.upload_into(noise.ptr, e32, dtype=np.float32)
+                c.check(lib.oisat_field_sample(h, self.oxyz.ptr, m, self.osig.ptr, om, ph, F, rows, noise.ptr, self.ovar.ptr, X.ptr, mp))
+                c.check(lib.oisat_trsm_rows(h, self.S.ptr, m, mp, X.ptr, PROBE_PANEL, mp))
+                c.check(lib.oisat_trsm_rows_bwd(h, self.S.ptr, m, mp, X.ptr, PROBE_PANEL, mp))
+                c.check(lib.oisat_member_spread(h, self.gxyz.ptr, self.gsig.ptr, ny, nx, self.oxyz.ptr, self.osig.ptr, X.ptr, rows, mp, m,
+                                                self._g, self.glat.ptr, self.olat.ptr, P.ptr, n, 1 if p0 else 0, sums.at(0), sums.at(n * 8)))
+                if keep:
+                    got = c.download(P.ptr, (rows, n), np.float32)
+            if keep:
+                dev[p0:p0 + rows] = got
+        if solve:
+            self.check()
+            s2, s4 = c.download(sums.ptr, (2, n), np.float64)
+        return s2, s4, dev
+
+    def _ensemble_result(self, A, A_var, dev, K, F, seed):
+        err = np.sqrt(A)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            err_se = np.where(err > 0, np.sqrt(A_var) / (2.0 * err), 0.0)
+        return {"err": err.reshape(self.shape).astype(np.float32), "err_se": err_se.reshape(self.shape),
+                "deviations": None if dev is None else dev.reshape((K,) + tuple(self.shape)), "nmember": K, "nfeature": F,
+                "seed": int(seed)}
+
+    def posterior_ensemble(self, nmember: int = 32, nfeature: int = 256, seed: int = 0, keep: bool = True):
+        """``nmember`` draws from N(x_a, A), A = B - B H^T S^-1 H B, by Matheron's rule through the factor that ``run()`` left in
+        HBM: delta_k = xi_k - B H^T S^-1 (H xi_k + eps_k) with xi_k ~ N(0, B) a random-feature field
+        of ``nfeature`` frequencies (``ensemble_draws``; ``gaussian`` and ``soar``, ``gaspari_cohn`` is a ``ValueError``) and
+        eps_k ~ N(0, R).  Panels of 128 members (the last one padded with zero rows): the draws are made on the host and
+        uploaded, ``oisat_field_sample`` at the observations with the noise added, ``oisat_trsm_rows`` and
+        ``oisat_trsm_rows_bwd``, ``oisat_field_sample`` on the grid with the same frequencies, ``oisat_member_spread``.  The
+        solve is the fp32 factor's, UNREFINED -- the grade of solve ``posterior_error_mc`` uses -- so a member carries the
+        factor's own cut (its envelope, fp32 rounding) beside its sampling noise.  The device copies of the sigmas and
+        variances are used, so ``set_error_scales`` is honoured.
+        Returns ``err`` (grid shape, float32: the root of the members' mean square -- the mean is known to be zero, K degrees
+        of freedom), ``err_se`` (from the fourth moments; 0 where err is 0), ``deviations`` ((K, ny, nx) float32, add x_a for
+        members of the analysis; None with ``keep=False``), ``nmember``, ``nfeature``, ``seed``.  The relative standard error
+        of err^2 is sqrt(2 / K) of ITSELF, however well a cell is observed.  A cell whose background sigma is 0 has deviation
+        0.  Member k is the same for every ``nmember``; same seed, same bits."""
+        if not self.m or self._g is None:
+            raise ValueError("posterior_ensemble() must follow run(): it reads the factor that run() leaves behind")
+        K, F = _ensemble_sizes(nmember, nfeature)
+        corr = {v: k for k, v in CORRELATIONS.items()}[self._kind]
+        L_km = corr_length_of(self._g)
+        ensemble_draws(corr, L_km, [], F, 0, seed)              # (gaspari_cohn: ValueError before any device call)
+        s2, s4, dev = self._ensemble_panels(K, F, seed, keep, L_km, corr, solve=True)
+        A, A_var = _mean_and_var(s2, s4, K)
+        return self._ensemble_result(A, A_var, dev, K, F, seed)
+
+    def prior_ensemble(self, L_km, corr="gaussian", nmember: int = 32, nfeature: int = 256, seed: int = 0, keep: bool = True):
+        """The ensemble where nothing was observed: ``nmember`` draws from N(0, B) -- ``oisat_field_sample`` on the grid alone
+        -- in the dictionary of ``posterior_ensemble``.  Needs the background only.  Unlike ``posterior_ensemble``, whose ``err`` is
+        the members' own root mean square, ``err`` here is NOT a sample statistic: it is the background sigma that was loaded,
+        which is known exactly.  Only ``err_se`` comes from the sample (the variance of its squares, summed on the host from the
+        fields as they are read back, over 2 err): it says how far a sample of this size would scatter about that value."""
+        K, F = _ensemble_sizes(nmember, nfeature)
+        ensemble_draws(corr, L_km, [], F, 0, seed)              # (ValueError before any device call)
+        if getattr(self, "_gsig_host", None) is None:
+            raise ValueError("load_background() first: the prior draws are scaled by the background error")
+        s2, s4, dev = self._ensemble_panels(K, F, seed, keep, float(L_km), corr, solve=False)
+        _, A_var = _mean_and_var(s2, s4, K)
+        return self._ensemble_result(np.asarray(self._gsig_host, dtype=np.float64) ** 2, A_var, dev, K, F, seed)
 
     # ---- analysis error of linear functionals: regional means (DESIGN.md section 4.2h)
     def _functional_buffer(self, name, nbytes):
@@ -1401,8 +1560,17 @@ class MonthTileBatch:
         self.pool.close()
 
 
+def _ensemble_mask(ens, Xa):
+    """``info["ensemble"]``: the deviations are NaN where the background is not finite, as ``xb`` is."""
+    bad = ~np.isfinite(np.asarray(Xa))
+    if bad.any() and ens["deviations"] is not None:
+        ens["deviations"][:, bad] = np.nan
+    return ens
+
+
 def OI_dense(Xa, Y, Sa, So, lat, lon, L_km, scale=1.0, refine=2, obs=None, dtype=None, want_error=False, tol=None,
-             corr="gaussian", nprobe=256, seed=0, superob=None, superob_rho=0.0, regions=None, likelihood=False, fit_scale=None):
+             corr="gaussian", nprobe=256, seed=0, superob=None, superob_rho=0.0, regions=None, likelihood=False, fit_scale=None,
+             ensemble=None, ensemble_features=256):
     """Dense-covariance analysis with the reference's gridded argument convention.
 
     ``Xa, Sa``: (ny, nx) background and its variance; ``Y, So``: (ny, nx) observations and their
@@ -1434,8 +1602,17 @@ def OI_dense(Xa, Y, Sa, So, lat, lon, L_km, scale=1.0, refine=2, obs=None, dtype
     of ``scale * scale_b`` and ``So * scale_o``: the very call ``OI_dense(..., scale=scale * scale_b, likelihood=True)`` (with
     ``So * scale_o`` under ``"both"``) would make, with ``info["likelihood"]`` at the optimum.  Without a usable observation
     ``scale_fit`` is ``{"found": False, "scale_b": 1.0, "scale_o": 1.0, ...}`` and ``likelihood`` is None.
+    ``ensemble``: None (default) | K, a positive multiple of 32: ``info["ensemble"]`` holds K draws from the analysis' own error
+    distribution N(0, A) as ``deviations`` (K, ny, nx), NaN where the background is not finite, with the ``err`` / ``err_se``
+    they imply, from ``ensemble_features`` random features per member and the seed ``seed``
+    (``DenseAnalysis.posterior_ensemble``; ``gaussian`` and ``soar`` only).  The ensemble is that of
+    whatever system the plan solved -- ``obs=``, ``superob=`` and ``fit_scale=`` alike; without a usable observation the
+    members are prior draws (``DenseAnalysis.prior_ensemble``).
     """
     corr_kind(corr)                                           # (ValueError before anything is touched)
+    if ensemble is not None:
+        ens_K, ens_F = _ensemble_sizes(ensemble, ensemble_features)
+        ensemble_draws(corr, L_km, [], ens_F, 0, seed)        # (gaspari_cohn: ValueError)
     if fit_scale is not None and fit_scale not in FIT_SCALE_MODES:
         raise ValueError(f"fit_scale is None, 'background' or 'both', got {fit_scale!r}")
     want_lik = bool(likelihood) or fit_scale is not None
@@ -1501,6 +1678,10 @@ def OI_dense(Xa, Y, Sa, So, lat, lon, L_km, scale=1.0, refine=2, obs=None, dtype
             prior = plan.functional_prior(reg_W, L_km=L_km, corr=corr)
             fc = {"prior": prior, "posterior": prior.copy(), "resid": np.zeros(len(reg_ids))}
             extra["regions"] = _region_info(reg_ids, reg_W, Xa, xa_f, fc)
+        if ensemble is not None:       # nothing observed: the members are prior draws
+            plan = DenseAnalysis(lat, lon, max_obs=1, dtype=dt)
+            plan.load_background(xa_f, sa_f, scale=scale)
+            extra["ensemble"] = _ensemble_mask(plan.prior_ensemble(L_km, corr=corr, nmember=ens_K, nfeature=ens_F, seed=seed), Xa)
         return (np.array(Xa, dtype=dt), np.zeros(np.shape(Xa), dtype=dt),
                 {"nobs": 0, "residuals": [], "cells": cell, "z": np.empty(0), **extra})
     plan = DenseAnalysis(lat, lon, max_obs=int(cell.size if so is None else so["nobs"]), dtype=dt,
@@ -1552,6 +1733,8 @@ def OI_dense(Xa, Y, Sa, So, lat, lon, L_km, scale=1.0, refine=2, obs=None, dtype
             extra.update(err_se=est["err_se"], ak_obs_se=est["ak_obs_se"], error_method="mc", nprobe=est["nprobe"])
     if regions is not None:
         extra["regions"] = _region_info(reg_ids, reg_W, Xa, xb, plan.functional_covariance(reg_W, refine=refine, tol=tol))
+    if ensemble is not None:
+        extra["ensemble"] = _ensemble_mask(plan.posterior_ensemble(nmember=ens_K, nfeature=ens_F, seed=seed), Xa)
     bad = ~np.isfinite(Xa)
     if bad.any():
         xb = xb.copy()

@@ -122,6 +122,12 @@ class oisatgmi(object):
     #               estimates a common inflation of the observation errors (the masks of error_OI / ak_OI keep So as given).
     #               The knee still feeds the `auto` length and the QC, which come first.  oi_info["scale"] = knee x scale_b,
     #               oi_info["scale_knee"], oi_info["scale_fit"], oi_info["likelihood"]
+    #   ensemble    attribute `oi_ensemble`    | env OISAT_OI_ENSEMBLE    off (default) | <K> | <K>:<F>  (dense only; diag, tiled:
+    #               ValueError): K draws (a positive multiple of 32) from the analysis' own error distribution N(0, A) by
+    #               Matheron's rule, each from F random features (default 256), through the factor the analysis leaves behind
+    #               (dense.DenseAnalysis.posterior_ensemble; gaussian and soar); oi_info["ensemble"]:
+    #               deviations (K, ny, nx), NaN where the background is, and the err / err_se they imply.  error_OI / ak_OI
+    #               and OISAT_OI_ERROR are untouched
     def _oi_setting(self, attr, env, default, cast=str):
         v = getattr(self, attr, None)
         if v is None:
@@ -187,6 +193,23 @@ class oisatgmi(object):
             raise ValueError(f"OISAT_OI_SCALE / oi_scale: expected knee, ml or ml:both, not {v!r}") from None
 
     @staticmethod
+    def _ensemble_setting(v):
+        """``OISAT_OI_ENSEMBLE`` / ``oi_ensemble`` -> ``None`` for ``off``, ``(K, F)`` for ``<K>`` (F = 256) / ``<K>:<F>`` (K a
+        positive multiple of 32, F >= 1); anything else is a ``ValueError``."""
+        from . import dense
+        t = str(v).strip().lower()
+        if t == "off":
+            return None
+        try:
+            parts = t.split(":")
+            if len(parts) > 2:
+                raise ValueError
+            return dense._ensemble_sizes(int(parts[0]), int(parts[1]) if len(parts) == 2 else 256)
+        except ValueError:
+            raise ValueError(f"OISAT_OI_ENSEMBLE / oi_ensemble: expected off, <members> or <members>:<features> (members a positive "
+                             f"multiple of 32, features at least 1), not {v!r}") from None
+
+    @staticmethod
     def _superob_setting(v):
         """``OISAT_OI_SUPEROB`` / ``oi_superob`` -> ``None`` for ``off``, the box size in degrees (a float in (0, 180]) for
         ``<deg>``, ``"auto:<max_obs>"`` for ``auto`` (max_obs = 100 000) / ``auto:<max_obs>`` (a positive integer); anything else
@@ -243,6 +266,10 @@ class oisatgmi(object):
         if fit_scale is not None and mode in ("diag", "tiled"):
             raise ValueError("OISAT_OI_SCALE / oi_scale = ml belongs to the dense mode; the tiles share the observations of their "
                              "halos, so their likelihoods do not add (knee)")
+        ensemble = self._oi_setting("oi_ensemble", "OISAT_OI_ENSEMBLE", "off", self._ensemble_setting)
+        if ensemble is not None and mode in ("diag", "tiled"):
+            raise ValueError("OISAT_OI_ENSEMBLE / oi_ensemble belongs to the dense mode; the members are drawn through the one factor "
+                             "of the whole system, and a tile has none of its neighbours' (off)")
         if mode == "diag":
             self.ctm_averaged_vcd_corrected, self.ak_OI, self.increment_OI, self.error_OI = OI(
                 xa, y, Sa, So, regularization_on=True, reg_index=reg_index)
@@ -281,7 +308,7 @@ class oisatgmi(object):
             sl = (slice(None), slice(None)) + tail
             res, info = self._oi_spatial(mode, xa[sl], y[sl], np.asarray(Sa)[sl], np.asarray(So)[sl], lat, lon, L, tile,
                                          unobserved, reg_index, want_error, corr=corr, nprobe=nprobe, qc=qc,
-                                         superob=superob, regions=regions, fit_scale=fit_scale)
+                                         superob=superob, regions=regions, fit_scale=fit_scale, ensemble=ensemble)
             for o, r in zip(outs, res):
                 o[sl] = r
             infos.append(info)
@@ -292,14 +319,15 @@ class oisatgmi(object):
 
     @staticmethod
     def _oi_spatial(mode, xa, y, Sa, So, lat, lon, L, tile, unobserved, reg_index, want_error, corr="gaussian", nprobe=256,
-                    qc=None, superob=None, regions=None, fit_scale=None):
+                    qc=None, superob=None, regions=None, fit_scale=None, ensemble=None):
         """One (ny, nx) Gaussian-B analysis -> ((Xb, AK, increment, error), info) in the reference's attribute order.  ``qc``
         (``_qc_setting``): not None = the innovations are checked first and the rejected cells analysed as unobserved, on a
         copy of ``y``.  ``superob`` (``_superob_setting``, dense mode): not None = the kept observations are merged into
         superobservations ahead of the analysis; the ``observed`` mask stays the raw one.  ``regions`` (dense mode): a label
         map; ``info["regions"]`` then holds the regional means and their exact errors (``dense.OI_dense``).  ``fit_scale``
         (``_scale_setting``, dense mode): not None = the knee scale is only the starting point of a maximum-likelihood fit of the
-        error scales; ``info["scale"]`` is then knee x scale_b, beside ``scale_knee``, ``scale_fit`` and ``likelihood``."""
+        error scales; ``info["scale"]`` is then knee x scale_b, beside ``scale_knee``, ``scale_fit`` and ``likelihood``.
+        ``ensemble`` (``_ensemble_setting``, dense mode): not None = ``(K, F)``, and ``info["ensemble"]`` holds K posterior draws."""
         from . import dense
         from . import optimal_interpolation as oi_mod
         index, scale, curve, found = oi_mod.regularization_pick(Sa, So, reg_index)
@@ -336,7 +364,8 @@ class oisatgmi(object):
                     print("No correlation length could be fitted to the kept innovations; using 300 km")
         if mode == "dense":
             xb, inc, info = dense.OI_dense(xa, y, Sa, So, lat, lon, L, scale=scale, want_error=want_error, corr=corr,
-                                           nprobe=nprobe or 256, superob=superob, regions=regions, fit_scale=fit_scale)
+                                           nprobe=nprobe or 256, superob=superob, regions=regions, fit_scale=fit_scale,
+                                           **({} if ensemble is None else {"ensemble": ensemble[0], "ensemble_features": ensemble[1]}))
             if fit_scale is not None:
                 fit = info["scale_fit"]
                 print(f"The maximum-likelihood error scales are {fit['scale_b']:g} (background) and {fit['scale_o']:g} (observations)"
@@ -382,6 +411,8 @@ class oisatgmi(object):
             out_info["superob"] = info["superob"]
         if info.get("regions") is not None:
             out_info["regions"] = info["regions"]
+        if info.get("ensemble") is not None:
+            out_info["ensemble"] = info["ensemble"]
         if fit_scale is not None:
             out_info.update(scale_knee=scale_knee, scale_fit=info["scale_fit"], likelihood=info["likelihood"])
         return (xb, ak, inc, err), out_info
