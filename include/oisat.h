@@ -802,6 +802,70 @@ int oisat_member_spread(oisat_ctx* h, const double* gxyz, const double* gsig, in
  * stream, no workspace.  NULL h, L or out, m < 1 or ld < roundup(m, 128): OISAT_EINVAL, nothing launched, out untouched. */
 int oisat_factor_logdet(oisat_ctx* h, const float* L, int64_t m, int64_t ld, double* out);
 
+/* ---- a drift of the innovations: universal kriging (csrc/dense_drift.hip) -------------------------
+ * d = F beta + e, e ~ N(0, S), S = H B H^T + R, beta unknown with a flat prior, F = p smooth basis functions at the observations:
+ *   beta = M^-1 F^T S^-1 d,  M = F^T S^-1 F,  z' = S^-1 (d - F beta),  x_a = x_b + B H^T z' + f(x)^T beta,
+ * and the unknown beta adds q^T M^-1 q to a cell's analysis error variance, q = f(x) - F^T S^-1 H B e_x.  The library evaluates the
+ * basis, solves S [z_d, Y_F] = [d, F] as ONE block through the factor a run left behind, and applies beta; the p x p system is
+ * the caller's (oisatgmi/dense.py: DenseAnalysis.run(drift=...)), with M and b = F^T z_d from oisat_rows_dot.  All five calls are
+ * asynchronous on the handle's stream (oisat_gain_solve_multi: unless resid_host is given) and no workgroup waits for another.
+ *
+ * oisat_drift_basis: out[j][i] = f_j(p_i), j < p = (degree + 1)^2, i < npts; pxyz: dev double[3 * npts], unit vectors x | y | z;
+ * out: dev double[p][ld], ld >= npts, the columns npts..ld are written as zeros.  degree = 0 .. 3.  The functions are the real
+ * harmonics up to `degree` as polynomials of (x, y, z), unnormalised, in this order and evaluated exactly as written -- float64,
+ * one rounding per operation, no fused multiply-add, with xx = x*x, yy = y*y, zz = z*z, xy = x*y, t = 5*zz formed once:
+ *   degree 0:  1
+ *   degree 1:  x,  y,  z
+ *   degree 2:  xy,  y*z,  z*x,  xx - yy,  3*zz - 1
+ *   degree 3:  z*(t - 3),  x*(t - 1),  y*(t - 1),  z*(xx - yy),  xy*z,  x*(xx - 3*yy),  y*(3*xx - yy)
+ * so the same inputs give the same bits, on the device and in a NumPy restatement.  NULL h, pxyz or out, degree outside 0..3,
+ * npts < 1 or ld < npts: OISAT_EINVAL with nothing launched.
+ *
+ * oisat_cov_residual_multi: R[k] = D[k] - (C.*sig sig^T + diag(var)) Z[k] for k < nrhs, 1 <= nrhs <= 17, in float64 from the
+ * coordinates under the handle's correlation model (all three), in ONE pass over the pairs: each correlation value is formed
+ * once and enters nrhs fused multiply-adds.  D, Z, R_out: dev double[nrhs][ld], ld >= m, the columns m..ld are neither read nor
+ * written.  olat_sorted: as for oisat_cov_residual (the same latitude window); the one-shot block list of oisat_set_obs_blocks is
+ * taken as oisat_cov_residual takes it (used where that call would use it: a window exists and the compact blocks pay), the cull
+ * then being per block of 64 rows at the 2^-52 chord -- the terms left out are below 2^-52 of a full term.  A row's sum runs over
+ * the candidates in latitude order, four column phases (every fourth surviving candidate of each run of 64) joined as
+ * ((0 + 1) + 2) + 3: same inputs, same bits; the columns do not influence each other.  No fp32 tier.  R_out must not overlap D
+ * or Z; that, nrhs outside 1..17, m < 1, m >= 2^31, ld < m or a NULL pointer is OISAT_EINVAL with nothing launched.
+ *
+ * oisat_gain_solve_multi: oisat_gain_solve for a block of right-hand sides D (dev double[nrhs][ld]) into Z_out (same shape;
+ * must not overlap D): Z[k] = M^-1 d_k, then at most `refine` (0..8) rounds of { R = D - S Z by oisat_cov_residual_multi; a
+ * column with |r_k| <= tol |d_k| is converged (tol: oisat_set_refine_tol) and takes ZERO corrections from then on; Z += M^-1 R }.
+ * M^-1 is oisat_trsm_rows then oisat_trsm_rows_bwd on an fp32 panel of 128 rows (the rows nrhs..128 are zeros), i.e. GEMMs on
+ * the matrix cores over the whole lower triangle of the factor; Z is accumulated in double.  Narrowing to fp32 needs a scale per
+ * column: every right-hand side and every residual is divided by |d_k| on the way into the panel and the correction multiplied
+ * by |d_k| on the way out, so a column of norm 1e-25 or 1e+45 (both tested) neither underflows nor overflows, and a column of zeros gives
+ * zeros.  The test runs on the device.  A column still above tol behind the last allowed correction adds one to
+ * OISAT_STATUS_UNCONVERGED, as a single solve does; refine = 0 forms no residual (unless resid_host asks) and flags nothing.
+ * resid_host (may be NULL): (refine + 1) x nrhs relative norms |r_k| / |d_k|, [round][column]; rounds a column did not run repeat
+ * its last value.  Without resid_host the call enqueues every round and returns; with it the call synchronises after each
+ * check and stops enqueuing once every column has converged (the results are the same bits either way: a converged column's
+ * corrections are exact zeros).  L, m, ldl: the factor of the last factorization on this handle, as for oisat_gain_solve; the
+ * block list of oisat_set_obs_blocks is taken once and serves every round.  Workspace: the handle's, (128 x roundup(m, 128))
+ * floats + nrhs x ld doubles, grown on first use (not sized by oisat_dense_reserve).
+ *
+ * oisat_drift_apply: x_i += sum_j beta_j f_j(x_i) and inc_i += the same, i < n; gxyz: dev double[3 * n]; beta: dev double[p];
+ * x_inout, inc_inout: dev `dtype`[n], either may be NULL (not both).  The sum is formed in double (fused multiply-adds in the
+ * order of j), added to the widened value in double and rounded once to `dtype`.
+ *
+ * oisat_drift_quadform: var_out[i] = q_i^T Minv q_i, q_i[j] = f_j(x_i) - Q[j][i], i < n; Q: dev double[p][ldq], ldq >= n; Minv:
+ * dev double[p][p], row-major; var_out: dev double[n].  The basis is evaluated inside the kernel by the expressions above;
+ * t_j = sum_k Minv[j][k] q_k then sum_j q_j t_j, fused multiply-adds in ascending order. */
+int oisat_drift_basis(oisat_ctx* h, const double* pxyz, int64_t npts, int degree, double* out, int64_t ld);
+int oisat_cov_residual_multi(oisat_ctx* h, const double* oxyz, const double* osig, const double* ovar, int64_t m, double g,
+                             const double* D, const double* Z, double* R_out, int64_t nrhs, int64_t ld,
+                             const double* olat_sorted);
+int oisat_gain_solve_multi(oisat_ctx* h, const float* L, const double* oxyz, const double* osig, const double* ovar,
+                           int64_t m, int64_t ldl, double g, const double* D, int64_t nrhs, int64_t ld, int refine,
+                           double* Z_out, double* resid_host, const double* olat_sorted);
+int oisat_drift_apply(oisat_ctx* h, int dtype, const double* gxyz, int64_t n, int degree, const double* beta,
+                      void* x_inout, void* inc_inout);
+int oisat_drift_quadform(oisat_ctx* h, const double* gxyz, int64_t n, int degree, const double* Q, int64_t ldq,
+                         const double* Minv, double* var_out);
+
 /* The ticket list of a task-graph launch over nsys systems of block_rows[s] block rows (largest first), as the library would
  * build it -- host only, no device: int32 quadruples (kind, system, i, j) with kind 0 = chain of `system` (i = first row of its
  * trace stamps), 1 = tile task T(i, j), 2 = SUB(j) (tile (j+1, j)), 3 = PRE(j) (tile (j, j)).  (The solve tasks of

@@ -127,8 +127,8 @@ struct oisat_ctx {
     std::vector<ProfPending> pending;
     std::vector<hipEvent_t> free_events;
     // grow-only device workspaces (never freed/reallocated inside a timed region once warm)
-    void* ws[13] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    size_t ws_bytes[13] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    void* ws[14] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    size_t ws_bytes[14] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
     // last scaling sweep uploaded into workspace slot 0 (oi_diag.hip)
     double scales_host[OISAT_MAX_SCALES] = {0};
     int scales_n = 0;

@@ -146,6 +146,12 @@ SIGNATURES = {
     "oisat_member_spread": (C.c_int, [_c_ctx, _ptr, _ptr, _i64, _i64, _ptr, _ptr, _ptr, _i64, _i64, _i64, C.c_double, _ptr, _ptr,
                                       _ptr, _i64, C.c_int, _ptr, _ptr]),
     "oisat_factor_logdet": (C.c_int, [_c_ctx, _ptr, _i64, _i64, _ptr]),
+    "oisat_drift_basis": (C.c_int, [_c_ctx, _ptr, _i64, C.c_int, _ptr, _i64]),
+    "oisat_cov_residual_multi": (C.c_int, [_c_ctx, _ptr, _ptr, _ptr, _i64, C.c_double, _ptr, _ptr, _ptr, _i64, _i64, _ptr]),
+    "oisat_gain_solve_multi": (C.c_int, [_c_ctx, _ptr, _ptr, _ptr, _ptr, _i64, _i64, C.c_double, _ptr, _i64, _i64, C.c_int, _ptr,
+                                         C.POINTER(C.c_double), _ptr]),
+    "oisat_drift_apply": (C.c_int, [_c_ctx, C.c_int, _ptr, _i64, C.c_int, _ptr, _ptr, _ptr]),
+    "oisat_drift_quadform": (C.c_int, [_c_ctx, _ptr, _i64, C.c_int, _ptr, _i64, _ptr, _ptr]),
     "oisat_apply_increment": (C.c_int, [_c_ctx, C.c_int, _ptr, _ptr, _i64, _ptr, _ptr, _ptr, _i64, C.c_double, _ptr,
                                         _ptr, _ptr, _ptr, _ptr]),
     "oisat_apply_increment_grid": (C.c_int, [_c_ctx, C.c_int, _ptr, _ptr, _i64, _i64, _ptr, _ptr, _ptr, _i64, C.c_double, _ptr,

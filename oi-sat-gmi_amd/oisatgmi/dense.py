@@ -195,6 +195,51 @@ def corr_kind(corr) -> int:
         raise ValueError(f"corr must be one of {sorted(CORRELATIONS)}, not {corr!r}") from None
 
 
+DRIFT_MAX_DEGREE = 3                                          # include/oisat.h: oisat_drift_basis
+
+
+def drift_degree(drift):
+    """``drift`` of ``DenseAnalysis.run`` / ``OI_dense``: None (no drift) or the degree 0..3 of the harmonics whose
+    coefficients are estimated with the analysis; anything else is a ``ValueError``."""
+    if drift is None:
+        return None
+    if isinstance(drift, (bool, np.bool_)) or not isinstance(drift, (int, np.integer)) or not 0 <= int(drift) <= DRIFT_MAX_DEGREE:
+        raise ValueError(f"drift is None or a degree 0..{DRIFT_MAX_DEGREE}, not {drift!r}")
+    return int(drift)
+
+
+def drift_coefficients(M, b, tol):
+    """The p x p system of universal kriging on the host, float64: ``M`` (symmetrised here) is scaled to unit diagonal,
+    factored by Cholesky, and ``beta = M^-1 b``, ``cov beta = M^-1``.  ``ValueError("drift not identifiable ...")`` when the
+    Cholesky fails or the 2-norm condition number of the scaled ``M`` exceeds ``1 / tol``: the solves behind ``M`` and ``b`` carry
+    a relative error of ``tol``, so beyond that ``beta`` has no correct digit.  Returns ``beta``, ``beta_cov``, ``beta_se``,
+    ``cond`` and ``logdet_M``."""
+    M = np.asarray(M, dtype=np.float64)
+    M = 0.5 * (M + M.T)
+    b = np.asarray(b, dtype=np.float64)
+    dg = np.diag(M)
+    if not (np.all(np.isfinite(M)) and np.all(np.isfinite(b)) and np.all(dg > 0.0)):
+        raise ValueError("drift not identifiable: F^T S^-1 F has a non-positive or non-finite diagonal")
+    s = 1.0 / np.sqrt(dg)
+    Ms = M * s[:, None] * s[None, :]
+    ev = np.linalg.eigvalsh(Ms)
+    cond = float(ev[-1] / ev[0]) if ev[0] > 0.0 else float("inf")
+    limit = 1.0 / max(float(tol), np.finfo(np.float64).eps)
+    try:
+        if not cond <= limit:
+            raise np.linalg.LinAlgError
+        Lc = np.linalg.cholesky(Ms)
+    except np.linalg.LinAlgError:
+        raise ValueError(f"drift not identifiable: the scaled F^T S^-1 F has condition number {cond:.3g}, the solves' tolerance "
+                         f"allows {limit:.3g}; lower the degree") from None
+    Li = np.linalg.inv(Lc)
+    Msi = Li.T @ Li
+    beta = s * (Msi @ (s * b))
+    cov = Msi * s[:, None] * s[None, :]
+    logdet = 2.0 * float(np.sum(np.log(np.diag(Lc)))) - 2.0 * float(np.sum(np.log(s)))
+    return {"beta": beta, "beta_cov": cov, "beta_se": np.sqrt(np.diag(cov)), "cond": cond, "logdet_M": logdet}
+
+
 def latitude_order(lat_deg) -> np.ndarray:
     """The permutation into ascending latitude (stable) that every latitude window of the library assumes."""
     return np.argsort(np.ravel(np.asarray(lat_deg, dtype=np.float64)), kind="stable")
@@ -303,6 +348,7 @@ class DenseAnalysis:
         self._scales = (1.0, 1.0)
         self._gsig0 = self._osig0 = self._ovar0 = None
         self._lik_ready = False                                # the last run() was one that log_likelihood() may read
+        self._drift = None                                     # what the last run(drift=...) estimated (drift_estimate())
         # every internal workspace of the solve is sized here, so that run() never allocates (include/oisat.h)
         c.check(c.lib.oisat_dense_reserve(c.h, self.max_obs, int(diag_chunk_rows)))
 
@@ -346,6 +392,7 @@ class DenseAnalysis:
         if self._scales != (1.0, 1.0):
             self.set_error_scales(1.0, 1.0)
         self._lik_ready = False
+        self._drift = None
 
     def load_obs_direct(self, obs_lat, obs_lon, obs_sigma_b, obs_var, innovation):
         """Observations whose background value lives outside this plan's grid (tile halos): the caller
@@ -437,15 +484,27 @@ class DenseAnalysis:
 
     # ---- the hot path: everything below runs on the device, enqueued on the handle's stream
     def run(self, L_km: float, refine: int = 2, check_pd: bool = False, want_resid: bool = False, tol=None, corr="gaussian",
-            fields: bool = True, exact_factor: bool = False):
+            fields: bool = True, exact_factor: bool = False, drift=None):
         """``refine``: the most refinement rounds the gain solve may take; it stops earlier once the float64 residual is
         below ``tol`` |d| (default: the handle's, 1e-6 -- ``oisat_set_refine_tol``; 0 runs every round).  ``corr``: the
         correlation model, ``"gaussian"``, ``"gaspari_cohn"`` or ``"soar"`` (same L; module docstring).  ``fields=False``: stop
         behind the gain solve, the increment is not spread (``z`` and the factor are all a likelihood needs).
         ``exact_factor=True``: build and factor inside the 2^-52 envelope instead of the fp32 factor's own, narrower one, so that
-        the factor's log-determinant is that of S (``log_likelihood``)."""
+        the factor's log-determinant is that of S (``log_likelihood``).
+        ``drift``: None (default: the path and the bits of a run without it) or a degree 0..3: the innovations are modelled as
+        d = F beta + e with F the (degree + 1)^2 real harmonics up to that degree at the observations and beta unknown with a flat
+        prior (universal kriging).  One block solve S [z_d, Y_F] = [d, F] (``oisat_gain_solve_multi``),
+        beta = M^-1 b from M = F^T Y_F and b = F^T z_d on the host (``drift_coefficients``), z' = z_d - Y_F beta -- what
+        ``download_z()`` then returns -- and the increment is B H^T z' plus the drift itself (``oisat_drift_apply``);
+        ``drift_estimate()``, ``drift_variance()`` and ``log_likelihood()`` describe the result.  ``ValueError("drift not
+        identifiable ...")`` with fewer observations than coefficients, or where M cannot be inverted to the solves' tolerance.
+        This one synchronises (the p x p system is solved on the host); ``want_resid`` then reports the innovation's column."""
+        deg = drift_degree(drift)
+        if deg is not None and self.m < (deg + 1) ** 2:
+            raise ValueError(f"drift not identifiable: {self.m} observations for {(deg + 1) ** 2} coefficients")
         kind = self._kind = corr_kind(corr)
         self._lik_ready = False
+        self._drift = None
         c, lib, h = self.ctx, self.ctx.lib, self.ctx.h
         c.check(lib.oisat_set_refine_tol(h, REFINE_TOL if tol is None else float(tol)))      # per run: handles are shared
         c.check(lib.oisat_set_correlation(h, kind))                                          # ... and so is the model
@@ -476,11 +535,19 @@ class DenseAnalysis:
         self.last_schedule = schedule.value                    # (SCHEDULE_*: which factorization ran, for tests and profiles)
         resid = (C.c_double * (refine + 1))() if want_resid else None
         c.check(lib.oisat_set_obs_blocks(h, self.perm.ptr, m))                                  # per run: handles are shared
-        c.check(lib.oisat_gain_solve(h, self.S.ptr, self.oxyz.ptr, self.osig.ptr, self.ovar.ptr, m, ld, g, self.d.ptr,
-                                     int(refine), self.z.ptr, resid, self.olat.ptr))
+        if deg is None:
+            c.check(lib.oisat_gain_solve(h, self.S.ptr, self.oxyz.ptr, self.osig.ptr, self.ovar.ptr, m, ld, g, self.d.ptr,
+                                         int(refine), self.z.ptr, resid, self.olat.ptr))
+        else:
+            col0 = self._drift_solve(deg, int(refine), REFINE_TOL if tol is None else float(tol))
+            if want_resid:
+                resid = col0
         if fields:
             c.check(lib.oisat_apply_increment_grid(h, self.code, self.gxyz.ptr, self.gsig.ptr, self._ny, self._nx, self.oxyz.ptr,
                                                    self.osig.ptr, self.z.ptr, m, g, xb, xa, inc, self.glat.ptr, self.olat.ptr))
+            if deg is not None:
+                c.check(lib.oisat_drift_apply(h, self.code, self.gxyz.ptr, self.n, deg, self._functional_buffer("drift_beta", 16 * 8).ptr,
+                                              xa, inc))
         self._lik_ready = bool(check_pd) and bool(exact_factor)
         if self._owns_S and enveloped.value == 1 and schedule.value in (SCHEDULE_ENV_DAG, SCHEDULE_ENV_DAG_FWD):
             nb = self.mp // NB
@@ -792,6 +859,67 @@ class DenseAnalysis:
         prior, gy, ry = out[:3 * K * K].reshape(3, K, K)
         return assemble_functional_covariance(prior, gy, ry, out[3 * K * K:3 * K * K + K], out[3 * K * K + K:], ns)
 
+    # ---- a drift of the innovations
+    def _drift_solve(self, deg, refine, tol):
+        """Behind the factorization of ``run(drift=deg)``: the basis at the observations in their stored order, the block solve,
+        the p x p system on the host and z' -> ``self.z``; beta -> the device buffer ``drift_beta``.  Returns the innovation
+        column's relative residuals (refine + 1)."""
+        c, lib, h = self.ctx, self.ctx.lib, self.ctx.h
+        m, ld, g = self.m, self.mp, self._g
+        p = (deg + 1) ** 2
+        nr = p + 1
+        blk = self._functional_buffer("drift", (2 * nr * self.mp_max + nr * nr) * 8)      # [d | F] | [z_d | Y_F] | their products
+        D, Z, small = blk.at(0), blk.at(nr * ld * 8), blk.at(2 * nr * ld * 8)
+        c.check(lib.oisat_affine(h, _hip.dtype_code(np.dtype(np.float64)), self.d.ptr, m, 0.0, 1.0, D))      # a copy of d: (d - 0) / 1
+        c.check(lib.oisat_drift_basis(h, self.oxyz.ptr, m, deg, D + ld * 8, ld))
+        resid = (C.c_double * ((refine + 1) * nr))()
+        c.check(lib.oisat_gain_solve_multi(h, self.S.ptr, self.oxyz.ptr, self.osig.ptr, self.ovar.ptr, m, ld, g, D, nr, ld, refine, Z,
+                                           resid, self.olat.ptr))
+        c.check(lib.oisat_rows_dot(h, D, ld, nr, Z, ld, nr, m, small))                      # [d | F]^T [z_d | Y_F]
+        G = c.download(small, (nr, nr), np.float64)
+        est = drift_coefficients(G[1:, 1:], G[1:, 0], tol)
+        beta = est["beta"]
+        Dh = c.download(D, (nr, ld), np.float64)[:, :m]
+        Zh = c.download(Z, (nr, ld), np.float64)[:, :m]
+        zp = Zh[0] - beta @ Zh[1:]
+        c.upload_into(self.z.ptr, zp, dtype=np.float64)
+        c.upload_into(self._functional_buffer("drift_beta", 16 * 8).ptr, beta, dtype=np.float64)
+        res = np.array(resid, dtype=np.float64).reshape(refine + 1, nr)
+        self._drift = {"degree": deg, "beta": beta, "beta_cov": est["beta_cov"], "beta_se": est["beta_se"], "cond": est["cond"],
+                       "resid": res[-1].copy(), "chi2": float((Dh[0] - beta @ Dh[1:]) @ zp), "logdet_M": est["logdet_M"]}
+        return [float(v) for v in res[:, 0]]
+
+    def drift_estimate(self):
+        """What the last ``run(drift=degree)`` estimated: ``degree``, ``beta`` ((degree + 1)^2 coefficients in the order of
+        ``oisat_drift_basis``), ``beta_cov`` = (F^T S^-1 F)^-1, ``beta_se``, ``cond`` (of the unit-diagonal F^T S^-1 F), ``resid``
+        (relative residual of each column of the block solve, the innovation first) and ``chi2`` = (d - F beta)^T z'."""
+        if self._drift is None:
+            raise ValueError("drift_estimate() must follow run(drift=degree)")
+        self.check()
+        return {k: (v.copy() if isinstance(v, np.ndarray) else v) for k, v in self._drift.items() if k != "logdet_M"}
+
+    def drift_variance(self):
+        """(ny, nx) float64: the variance that the unknown drift adds to the analysis error of every cell, q^T M^-1 q with
+        q = f(x) - Q(x), Q[j] = B H^T Y_F[:, j] -- p float64 increments (``oisat_apply_increment_grid``) and one
+        ``oisat_drift_quadform``.  Needs the block solve of the last ``run(drift=degree)``."""
+        if self._drift is None:
+            raise ValueError("drift_variance() must follow run(drift=degree)")
+        c, lib, h = self.ctx, self.ctx.lib, self.ctx.h
+        m, ld, g, n, deg = self.m, self.mp, self._g, self.n, self._drift["degree"]
+        p = (deg + 1) ** 2
+        Y = self._functional_buffer("drift", 0).at((p + 1) * ld * 8 + ld * 8)             # Y_F: behind z_d in the solution block
+        Q = self._functional_buffer("drift_Q", (p + 1) * n * 8)                            # Q | the variance
+        Mi = self._functional_buffer("drift_Minv", 16 * 16 * 8)
+        c.upload_into(Mi.ptr, np.ascontiguousarray(self._drift["beta_cov"]), dtype=np.float64)
+        c.check(lib.oisat_set_correlation(h, self._kind))       # (the model of the run that left the factor)
+        f64 = _hip.dtype_code(np.dtype(np.float64))
+        for j in range(p):
+            c.check(lib.oisat_apply_increment_grid(h, f64, self.gxyz.ptr, self.gsig.ptr, self._ny, self._nx, self.oxyz.ptr, self.osig.ptr,
+                                                   Y + j * ld * 8, m, g, None, None, Q.at(j * n * 8), self.glat.ptr, self.olat.ptr))
+        c.check(lib.oisat_drift_quadform(h, self.gxyz.ptr, n, deg, Q.ptr, n, Mi.ptr, Q.at(p * n * 8)))
+        self.check()
+        return c.download(Q.at(p * n * 8), tuple(self.shape), np.float64)
+
     # ---- the innovations' likelihood and the error scales it supports (DESIGN.md section 4.2i)
     def log_likelihood(self):
         """-2 ln p(d) of the innovations under S = H B H^T + R as the last ``run(check_pd=True, exact_factor=True)`` analysed them
@@ -799,7 +927,11 @@ class DenseAnalysis:
         diagonal reduction over the factor (``oisat_factor_logdet``) and two dot products (``oisat_rows_dot``).  Returns ``m``,
         ``chi2`` (d^T S^-1 d from the refined z), ``chi2_per_obs``, ``logdet``, ``min_pivot`` (the factor's smallest diagonal
         entry), ``neg2_log_likelihood`` (m ln 2 pi + logdet + chi2) and ``dd`` (|d|^2).  The mean of the innovations is not
-        estimated: a bias shows as chi2_per_obs > 1."""
+        estimated: a bias shows as chi2_per_obs > 1 -- unless the run was one with ``drift=degree``: ``chi2`` is then
+        (d - F beta)^T z', the value with the drift removed, and three entries are added: ``p``, ``logdet_M`` = log det F^T S^-1 F
+        and ``neg2_restricted_log_likelihood`` = (m - p) ln 2 pi + logdet + logdet_M + chi2.
+        ``neg2_log_likelihood`` keeps its formula, m ln 2 pi + logdet + chi2, and is then the likelihood of d AT beta-hat (the
+        profile over beta: the drift-removed chi2 under the unrestricted normalisation), not the restricted one."""
         if not self._lik_ready:
             raise ValueError("log_likelihood() must follow run(check_pd=True, exact_factor=True)")
         self.check()
@@ -809,8 +941,14 @@ class DenseAnalysis:
         c.check(lib.oisat_rows_dot(h, self.d.ptr, m, 1, self.z.ptr, m, 1, m, out.at(16)))
         c.check(lib.oisat_rows_dot(h, self.d.ptr, m, 1, self.d.ptr, m, 1, m, out.at(24)))
         logdet, piv, chi2, dd = (float(v) for v in c.download(out.ptr, (4,), np.float64))
-        return {"m": m, "chi2": chi2, "chi2_per_obs": chi2 / m, "logdet": logdet, "min_pivot": piv,
-                "neg2_log_likelihood": m * float(np.log(2.0 * np.pi)) + logdet + chi2, "dd": dd}
+        if self._drift is not None:
+            chi2 = self._drift["chi2"]
+        lik = {"m": m, "chi2": chi2, "chi2_per_obs": chi2 / m, "logdet": logdet, "min_pivot": piv,
+               "neg2_log_likelihood": m * float(np.log(2.0 * np.pi)) + logdet + chi2, "dd": dd}
+        if self._drift is not None:
+            p, ldm = int(self._drift["beta"].size), self._drift["logdet_M"]
+            lik.update(p=p, logdet_M=ldm, neg2_restricted_log_likelihood=(m - p) * float(np.log(2.0 * np.pi)) + logdet + ldm + chi2)
+        return lik
 
     def _likelihood_at(self, scale_b, scale_o, L_km, corr, refine, tol):
         """One evaluation of the search: the likelihood dict at these scales with the solve's reported relative residual
@@ -1570,7 +1708,7 @@ def _ensemble_mask(ens, Xa):
 
 def OI_dense(Xa, Y, Sa, So, lat, lon, L_km, scale=1.0, refine=2, obs=None, dtype=None, want_error=False, tol=None,
              corr="gaussian", nprobe=256, seed=0, superob=None, superob_rho=0.0, regions=None, likelihood=False, fit_scale=None,
-             ensemble=None, ensemble_features=256):
+             ensemble=None, ensemble_features=256, drift=None):
     """Dense-covariance analysis with the reference's gridded argument convention.
 
     ``Xa, Sa``: (ny, nx) background and its variance; ``Y, So``: (ny, nx) observations and their
@@ -1608,8 +1746,20 @@ def OI_dense(Xa, Y, Sa, So, lat, lon, L_km, scale=1.0, refine=2, obs=None, dtype
     (``DenseAnalysis.posterior_ensemble``; ``gaussian`` and ``soar`` only).  The ensemble is that of
     whatever system the plan solved -- ``obs=``, ``superob=`` and ``fit_scale=`` alike; without a usable observation the
     members are prior draws (``DenseAnalysis.prior_ensemble``).
+    ``drift``: None (default) | a degree 0..3: a large-scale mean of the innovations -- the (degree + 1)^2 real harmonics up to
+    that degree -- is estimated together with the analysis (universal kriging, ``DenseAnalysis.run(drift=...)``; DESIGN.md
+    section 4.2k).  ``xb`` and ``inc`` then include the drift, ``info["drift"]`` is ``DenseAnalysis.drift_estimate()`` with
+    ``found`` True, and with ``want_error`` ``info["drift"]["var"]`` is ``DenseAnalysis.drift_variance()`` and ``info["err"]`` is
+    sqrt(err^2 + var).  The basis is evaluated where the plan's rows are: ``obs=`` and ``superob=`` alike (a superobservation is
+    a point at its centroid).  Without a usable observation ``info["drift"]`` is ``{"degree": ..., "found": False}`` and the
+    fields are untouched.  ``drift`` with ``fit_scale``, ``ensemble`` or ``regions`` is a ``ValueError`` (not combined yet).
     """
     corr_kind(corr)                                           # (ValueError before anything is touched)
+    drift = drift_degree(drift)
+    if drift is not None:
+        for name, v in (("fit_scale", fit_scale), ("ensemble", ensemble), ("regions", regions)):
+            if v is not None:
+                raise ValueError(f"drift cannot be combined with {name} yet")
     if ensemble is not None:
         ens_K, ens_F = _ensemble_sizes(ensemble, ensemble_features)
         ensemble_draws(corr, L_km, [], ens_F, 0, seed)        # (gaspari_cohn: ValueError)
@@ -1669,6 +1819,8 @@ def OI_dense(Xa, Y, Sa, So, lat, lon, L_km, scale=1.0, refine=2, obs=None, dtype
             extra["superob"] = so_info
         if want_lik:
             extra["likelihood"] = None
+        if drift is not None:
+            extra["drift"] = {"degree": drift, "found": False}
         if fit_scale is not None:
             extra["scale_fit"] = {"mode": fit_scale, "scale_b": 1.0, "scale_o": 1.0, "ratio": 1.0, "se_ln": float("inf"), "found": False,
                                   "at_bound": False, "nevals": 0, "evaluations": [], "residuals": [], "likelihood": None}
@@ -1709,7 +1861,11 @@ def OI_dense(Xa, Y, Sa, So, lat, lon, L_km, scale=1.0, refine=2, obs=None, dtype
                 if so["nobs"] != plan.m:
                     raise RuntimeError("the superobservations changed with the error scales")
             load()
-    resid = plan.run(L_km, refine=refine, check_pd=True, want_resid=True, tol=tol, corr=corr, exact_factor=want_lik)
+    if drift is None:
+        resid = plan.run(L_km, refine=refine, check_pd=True, want_resid=True, tol=tol, corr=corr, exact_factor=want_lik)
+    else:
+        resid = plan.run(L_km, refine=refine, check_pd=True, want_resid=True, tol=tol, corr=corr, exact_factor=want_lik, drift=drift)
+        extra["drift"] = {**plan.drift_estimate(), "found": True}
     xb, inc = plan.download()
     if want_lik:
         extra["likelihood"] = plan.log_likelihood()
@@ -1731,6 +1887,10 @@ def OI_dense(Xa, Y, Sa, So, lat, lon, L_km, scale=1.0, refine=2, obs=None, dtype
         extra.update(ak=ak.reshape(np.shape(Xa)), err=est["err"] if mc else plan.posterior_error(), ak_obs=ak_obs)
         if mc:
             extra.update(err_se=est["err_se"], ak_obs_se=est["ak_obs_se"], error_method="mc", nprobe=est["nprobe"])
+        if drift is not None:          # the unknown drift's share of the analysis error
+            var = extra["drift"]["var"] = plan.drift_variance()
+            err = np.asarray(extra["err"])
+            extra["err"] = np.sqrt(err.astype(np.float64) ** 2 + var).astype(err.dtype)
     if regions is not None:
         extra["regions"] = _region_info(reg_ids, reg_W, Xa, xb, plan.functional_covariance(reg_W, refine=refine, tol=tol))
     if ensemble is not None:

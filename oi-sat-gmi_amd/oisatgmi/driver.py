@@ -128,6 +128,12 @@ class oisatgmi(object):
     #               (dense.DenseAnalysis.posterior_ensemble; gaussian and soar); oi_info["ensemble"]:
     #               deviations (K, ny, nx), NaN where the background is, and the err / err_se they imply.  error_OI / ak_OI
     #               and OISAT_OI_ERROR are untouched
+    #   drift       attribute `oi_drift`       | env OISAT_OI_DRIFT       off (default) | <degree> 0..3  (dense only; diag, tiled:
+    #               ValueError): a large-scale mean of the innovations -- the (degree + 1)^2 real harmonics up to that degree,
+    #               e.g. a model that runs low over a hemisphere -- is estimated together with the analysis (universal kriging,
+    #               dense.DenseAnalysis.run(drift=...)) instead of being spread as a correlated anomaly;
+    #               the four attributes include it (error_OI with the variance the unknown drift adds), oi_info["drift"]: beta,
+    #               beta_se, cond, chi2, var.  Not combined with oi_scale = ml, oi_ensemble or oi_regions yet (ValueError)
     def _oi_setting(self, attr, env, default, cast=str):
         v = getattr(self, attr, None)
         if v is None:
@@ -210,6 +216,19 @@ class oisatgmi(object):
                              f"multiple of 32, features at least 1), not {v!r}") from None
 
     @staticmethod
+    def _drift_setting(v):
+        """``OISAT_OI_DRIFT`` / ``oi_drift`` -> ``None`` for ``off``, the degree 0..3 for ``<degree>``; anything else is a
+        ``ValueError``."""
+        from . import dense
+        t = str(v).strip().lower()
+        if t == "off":
+            return None
+        try:
+            return dense.drift_degree(int(t))
+        except ValueError:
+            raise ValueError(f"OISAT_OI_DRIFT / oi_drift: expected off or a degree 0..{dense.DRIFT_MAX_DEGREE}, not {v!r}") from None
+
+    @staticmethod
     def _superob_setting(v):
         """``OISAT_OI_SUPEROB`` / ``oi_superob`` -> ``None`` for ``off``, the box size in degrees (a float in (0, 180]) for
         ``<deg>``, ``"auto:<max_obs>"`` for ``auto`` (max_obs = 100 000) / ``auto:<max_obs>`` (a positive integer); anything else
@@ -270,6 +289,15 @@ class oisatgmi(object):
         if ensemble is not None and mode in ("diag", "tiled"):
             raise ValueError("OISAT_OI_ENSEMBLE / oi_ensemble belongs to the dense mode; the members are drawn through the one factor "
                              "of the whole system, and a tile has none of its neighbours' (off)")
+        drift = self._oi_setting("oi_drift", "OISAT_OI_DRIFT", "off", self._drift_setting)
+        if drift is not None and mode in ("diag", "tiled"):
+            raise ValueError("OISAT_OI_DRIFT / oi_drift belongs to the dense mode; the drift is one set of coefficients for the whole "
+                             "system, and a tile sees a part of it (off)")
+        if drift is not None:
+            for name, v in (("OISAT_OI_SCALE / oi_scale = ml", fit_scale), ("OISAT_OI_ENSEMBLE / oi_ensemble", ensemble),
+                            ("OISAT_OI_REGIONS / oi_regions", regions)):
+                if v is not None:
+                    raise ValueError(f"OISAT_OI_DRIFT / oi_drift cannot be combined with {name} yet (off)")
         if mode == "diag":
             self.ctm_averaged_vcd_corrected, self.ak_OI, self.increment_OI, self.error_OI = OI(
                 xa, y, Sa, So, regularization_on=True, reg_index=reg_index)
@@ -308,7 +336,7 @@ class oisatgmi(object):
             sl = (slice(None), slice(None)) + tail
             res, info = self._oi_spatial(mode, xa[sl], y[sl], np.asarray(Sa)[sl], np.asarray(So)[sl], lat, lon, L, tile,
                                          unobserved, reg_index, want_error, corr=corr, nprobe=nprobe, qc=qc,
-                                         superob=superob, regions=regions, fit_scale=fit_scale, ensemble=ensemble)
+                                         superob=superob, regions=regions, fit_scale=fit_scale, ensemble=ensemble, drift=drift)
             for o, r in zip(outs, res):
                 o[sl] = r
             infos.append(info)
@@ -319,7 +347,7 @@ class oisatgmi(object):
 
     @staticmethod
     def _oi_spatial(mode, xa, y, Sa, So, lat, lon, L, tile, unobserved, reg_index, want_error, corr="gaussian", nprobe=256,
-                    qc=None, superob=None, regions=None, fit_scale=None, ensemble=None):
+                    qc=None, superob=None, regions=None, fit_scale=None, ensemble=None, drift=None):
         """One (ny, nx) Gaussian-B analysis -> ((Xb, AK, increment, error), info) in the reference's attribute order.  ``qc``
         (``_qc_setting``): not None = the innovations are checked first and the rejected cells analysed as unobserved, on a
         copy of ``y``.  ``superob`` (``_superob_setting``, dense mode): not None = the kept observations are merged into
@@ -327,7 +355,8 @@ class oisatgmi(object):
         map; ``info["regions"]`` then holds the regional means and their exact errors (``dense.OI_dense``).  ``fit_scale``
         (``_scale_setting``, dense mode): not None = the knee scale is only the starting point of a maximum-likelihood fit of the
         error scales; ``info["scale"]`` is then knee x scale_b, beside ``scale_knee``, ``scale_fit`` and ``likelihood``.
-        ``ensemble`` (``_ensemble_setting``, dense mode): not None = ``(K, F)``, and ``info["ensemble"]`` holds K posterior draws."""
+        ``ensemble`` (``_ensemble_setting``, dense mode): not None = ``(K, F)``, and ``info["ensemble"]`` holds K posterior draws.
+        ``drift`` (``_drift_setting``, dense mode): not None = the degree of the drift estimated with the analysis; ``info["drift"]``."""
         from . import dense
         from . import optimal_interpolation as oi_mod
         index, scale, curve, found = oi_mod.regularization_pick(Sa, So, reg_index)
@@ -365,7 +394,8 @@ class oisatgmi(object):
         if mode == "dense":
             xb, inc, info = dense.OI_dense(xa, y, Sa, So, lat, lon, L, scale=scale, want_error=want_error, corr=corr,
                                            nprobe=nprobe or 256, superob=superob, regions=regions, fit_scale=fit_scale,
-                                           **({} if ensemble is None else {"ensemble": ensemble[0], "ensemble_features": ensemble[1]}))
+                                           **({} if ensemble is None else {"ensemble": ensemble[0], "ensemble_features": ensemble[1]}),
+                                           **({} if drift is None else {"drift": drift}))
             if fit_scale is not None:
                 fit = info["scale_fit"]
                 print(f"The maximum-likelihood error scales are {fit['scale_b']:g} (background) and {fit['scale_o']:g} (observations)"
@@ -413,6 +443,8 @@ class oisatgmi(object):
             out_info["regions"] = info["regions"]
         if info.get("ensemble") is not None:
             out_info["ensemble"] = info["ensemble"]
+        if info.get("drift") is not None:
+            out_info["drift"] = info["drift"]
         if fit_scale is not None:
             out_info.update(scale_knee=scale_knee, scale_fit=info["scale_fit"], likelihood=info["likelihood"])
         return (xb, ak, inc, err), out_info
