@@ -655,6 +655,44 @@ int oisat_apply_increment_grid(oisat_ctx* h, int dtype, const double* gxyz, cons
                                const double* oxyz, const double* osig, const double* z, int64_t m, double g,
                                const void* xb, void* xa, void* inc, const double* glat, const double* olat_sorted);
 
+/* oisat_gain_solve followed by oisat_apply_increment_grid of its z, as ONE call that takes the increment off the end of the solve.
+ * The increment is linear in z: behind the first solve the call snapshots z0 and runs its float64 increment inc0 into a double
+ * scratch field on a stream of the handle's own (lowest priority; waits and is waited for by events), underneath the first
+ * residual and the correction's sweeps, which are bound by their hand-overs and leave the vector units idle.  Behind the last
+ * round the fields are written once: T(inc0 + delta), T(xb + inc0 + delta) with delta = B H^T (z - z0) as oisat_increment_update
+ * forms it, one rounding to T.  Where the refinement converged at the first residual (z = z0) nothing is summed: the bits of
+ * oisat_apply_increment_grid.  GUARD, on the device: delta in fp32 is only as good as z - z0 is small, so the update form applies
+ * where |r_0| <= OISAT_INC_UPDATE_T |d| (2^-15: the largest power of two t with e t <= 2^-27 for e = 1.69e-4, the largest relative
+ * max-norm error of delta measured on four 100 000-observation months); a solve above that gets the float64 increment of its final z,
+ * the arithmetic and bits of oisat_apply_increment_grid (of the two launches one returns at once).  z_out and resid_host are oisat_gain_solve's, bit for bit.
+ * Gaussian only, 1 <= refine <= 8; OISAT_EINVAL otherwise.  While the side launch is in flight the correction's sweeps take the
+ * shape of oisat_trsv_plan_overlap.  With profiling on (oisat_prof_enable) the side launch runs on the handle's stream instead:
+ * same kernels, serial, same bits.  The call returns with the side stream joined (no host synchronisation): everything it leaves
+ * is ordered behind the handle's stream.  oisat_set_obs_blocks and the forward vector of oisat_potrf_env_fwd are taken as by
+ * oisat_gain_solve. */
+#define OISAT_INC_UPDATE_T (1.0 / 32768.0)
+int oisat_gain_solve_fields(oisat_ctx* h, const float* L, const double* oxyz, const double* osig, const double* ovar,
+                            int64_t m, int64_t ld, double g, const double* d, int refine, double* z_out,
+                            double* resid_host, const double* olat_sorted, int dtype, const double* gxyz, const double* gsig,
+                            int64_t ny, int64_t nx, const void* xb, void* xa, void* inc, const double* glat);
+
+/* The update alone: inc = T(inc0 + delta), xa = T(xb + inc0 + delta), delta_i = sig_i sum_a C(i,a) osig_a (z - z0)_a over the
+ * ny x nx grid (row-major).  inc0: dev double[ny * nx] (the float64 increment of z0); z - z0 is taken in double, every pair in
+ * packed fp32 (coordinates, exponential, partial sums of 16 terms joined in double), pairs below 2^-20 left out: delta is good
+ * to about four digits of its largest entry.  Gaussian only.  Same inputs, same bits. */
+int oisat_increment_update(oisat_ctx* h, int dtype, const double* gxyz, const double* gsig, int64_t ny, int64_t nx,
+                           const double* oxyz, const double* osig, const double* z, const double* z0, int64_t m, double g,
+                           const void* xb, void* xa, void* inc, const double* inc0, const double* glat, const double* olat_sorted);
+
+/* Host only.  oisat_trsv_plan_overlap: the sweeps' shape while the side stream's increment is in flight -- oisat_trsv_plan's, with
+ * a two-tile sweep over a band of at most 128 block rows capped at 128 workgroups (one such workgroup leaves a CU room for one
+ * increment workgroup instead of five).  oisat_inc_overlap_plan: *use_out = 1 where DenseAnalysis.run takes
+ * oisat_gain_solve_fields: one system, Gaussian, refine >= 1, fields wanted, no drift, and at least 256 block rows (the two hidden
+ * sweeps must outlast the update's cost); OISAT_INC_OVERLAP=0 in the environment (read at every call): nowhere, =1: wherever it
+ * is legal whatever the size; anything else is OISAT_EINVAL. */
+int oisat_trsv_plan_overlap(int64_t nb, int band, int cu_count, int32_t* two_tiles_out, int32_t* grid_out);
+int oisat_inc_overlap_plan(int64_t nb, int nsys, int corr_kind, int refine, int fields, int drift, int32_t* use_out);
+
 /* perm: dev int32[m], a permutation of 0 .. m-1 that lists the observations (indices into the ascending-latitude order
  * they are stored in) along a space-filling curve, so that 64 consecutive entries are neighbours in space.  The float64
  * residual of the gain solves that follow on this handle for systems of exactly m observations (oisat_gain_solve,

@@ -215,6 +215,45 @@ __global__ __launch_bounds__(256) void apply_increment_kernel(const double* __re
     increment_patch<KIND, T, CELLS>(gxyz, gsig, n, oxyz, osig, z, m, g2, xb, xa, inc, glat, olat, win_deg, nx, cut_chord, far_chord, (int64_t)blockIdx.x, W);
 }
 
+// ---- the increment behind a correction as an update of the first solve's (dense_inc_update.inc; oisat_gain_solve_fields) --------
+#include "dense_inc_update.inc"
+
+// The guard of the update form, on the device: it applies where the first residual is small against the innovation, |r_0| <= t |d|
+// (t2 = t^2; SolveState of the solve that has just run).  A NaN norm fails it.  Of the two launches behind a solve -- the update
+// and the float64 increment of the final z -- exactly one does work and the other returns at once, in the manner of st->conv.
+__device__ __forceinline__ bool inc_update_applies(const SolveState* __restrict__ st, double t2) { return st->norm[0] <= t2 * st->dd; }
+
+template <typename T, int CELLS>
+__global__ __launch_bounds__(256) void increment_update_kernel(const double* __restrict__ gxyz, const double* __restrict__ gsig, int64_t n,
+                                                                const double* __restrict__ oxyz, const double* __restrict__ osig,
+                                                                const double* __restrict__ z, const double* __restrict__ z0, int64_t m,
+                                                                double g2, const T* __restrict__ xb, T* __restrict__ xa, T* __restrict__ inc,
+                                                                const double* __restrict__ inc0, const double* __restrict__ glat,
+                                                                const double* __restrict__ olat, double win_deg, int nx, double cut_chord,
+                                                                const SolveState* __restrict__ st, double t2) {
+    SOLVE_LDS(W);
+    if (st != nullptr && !inc_update_applies(st, t2)) return;  // the float64 increment of the final z writes the fields (block-uniform)
+    const bool skip = st != nullptr && st->conv != 0 && st->computed == 1;      // converged at r_0: z = z0
+    increment_update_patch<T, CELLS>(gxyz, gsig, n, oxyz, osig, z, z0, m, g2, xb, xa, inc, inc0, glat, olat, win_deg, nx, cut_chord, skip,
+                                     (int64_t)blockIdx.x, W);
+}
+
+// the parent's float64 increment (Gaussian), for the solves the guard keeps off the update form
+template <typename T, int CELLS>
+__global__ __launch_bounds__(256) void apply_increment_guarded_kernel(const double* __restrict__ gxyz, const double* __restrict__ gsig,
+                                                                       int64_t n, const double* __restrict__ oxyz,
+                                                                       const double* __restrict__ osig, const double* __restrict__ z,
+                                                                       int64_t m, double g2, const T* __restrict__ xb, T* __restrict__ xa,
+                                                                       T* __restrict__ inc, const double* __restrict__ glat,
+                                                                       const double* __restrict__ olat, double win_deg, int nx,
+                                                                       double cut_chord, double far_chord,
+                                                                       const SolveState* __restrict__ st, double t2) {
+    SOLVE_LDS(W);
+    if (inc_update_applies(st, t2)) return;                    // the update has written the fields (block-uniform)
+    increment_patch<OISAT_CORR_GAUSSIAN, T, CELLS>(gxyz, gsig, n, oxyz, osig, z, m, g2, xb, xa, inc, glat, olat, win_deg, nx, cut_chord,
+                                                   far_chord, (int64_t)blockIdx.x, W);
+}
+
 // ---- probe spread (oisat_probe_spread): the kernel is dense_spread.inc, shared with the ensemble's oisat_member_spread --------
 #include "dense_spread.inc"
 
@@ -505,6 +544,77 @@ extern "C" int oisat_apply_increment_grid(oisat_ctx* h, int dtype, const double*
                                           const void* xb, void* xa, void* inc, const double* glat, const double* olat_sorted) {
     ARG_CHECK(ny > 0 && nx > 0);
     return apply_increment_impl(h, dtype, gxyz, gsig, ny * nx, nx, oxyz, osig, z, m, g, xb, xa, inc, glat, olat_sorted);
+}
+
+// ---- the three launches of oisat_gain_solve_fields (dense_solve.hip) behind its sweeps ------------------------------------------
+// inc0 = the float64 increment of z0 into a double scratch field: apply_increment_kernel<double> with neither xb nor xa
+int oisat_increment_scratch(oisat_ctx* h, const double* gxyz, const double* gsig, int64_t ny, int64_t nx, const double* oxyz,
+                            const double* osig, const double* z0, int64_t m, double g, double* inc0, const double* glat,
+                            const double* olat_sorted) {
+    return apply_increment_impl(h, OISAT_F64, gxyz, gsig, ny * nx, nx, oxyz, osig, z0, m, g, nullptr, nullptr, inc0, glat, olat_sorted);
+}
+
+template <typename T, int CELLS>
+static int increment_update_launch(oisat_ctx* h, unsigned gx, const double* gxyz, const double* gsig, int64_t n, int nx, const double* oxyz,
+                                   const double* osig, const double* z, const double* z0, int64_t m, double g, const void* xb, void* xa,
+                                   void* inc, const double* inc0, const double* glat, const double* olat, const SolveState* st, double t) {
+    OISAT_LAUNCH(h, "increment_update", (increment_update_kernel<T, CELLS>), dim3(gx), dim3(256), 0, gxyz, gsig, n, oxyz, osig, z, z0, m,
+                 corr_scale2_f64(OISAT_CORR_GAUSSIAN, g), (const T*)xb, (T*)xa, (T*)inc, inc0, glat, olat,
+                 lat_window_deg(OISAT_CORR_GAUSSIAN, g, kIncUpdateCutBits), nx, cut_chord(OISAT_CORR_GAUSSIAN, g, kIncUpdateCutBits), st, t * t);
+    return OISAT_OK;
+}
+
+template <typename T, int CELLS>
+static int increment_guarded_launch(oisat_ctx* h, unsigned gx, const double* gxyz, const double* gsig, int64_t n, int nx, const double* oxyz,
+                                    const double* osig, const double* z, int64_t m, double g, const void* xb, void* xa, void* inc,
+                                    const double* glat, const double* olat, const SolveState* st, double t) {
+    double far_chord;
+    ARG_CHECK(far_chord_of(OISAT_CORR_GAUSSIAN, g, &far_chord));
+    OISAT_LAUNCH(h, "apply_increment", (apply_increment_guarded_kernel<T, CELLS>), dim3(gx), dim3(256), 0, gxyz, gsig, n, oxyz, osig, z, m,
+                 corr_scale2_f64(OISAT_CORR_GAUSSIAN, g), (const T*)xb, (T*)xa, (T*)inc, glat, olat, lat_window_deg(OISAT_CORR_GAUSSIAN, g), nx,
+                 cut_chord_of(OISAT_CORR_GAUSSIAN, g), far_chord, st, t * t);
+    return OISAT_OK;
+}
+
+double oisat_inc_update_t() { return kIncUpdateT; }
+
+// fields = T(inc0 + delta) (increment_update_kernel) where the guard lets the update form apply, and the float64 increment of the
+// final z (apply_increment_guarded_kernel: the arithmetic of oisat_apply_increment_grid) where it does not; st = nullptr: the
+// update alone, unguarded (oisat_increment_update: the kernel at the ABI).  Patches and cells per thread: apply_increment_impl's.
+int oisat_increment_update_if(oisat_ctx* h, int dtype, const double* gxyz, const double* gsig, int64_t ny, int64_t nx, const double* oxyz,
+                              const double* osig, const double* z, const double* z0, int64_t m, double g, const void* xb, void* xa,
+                              void* inc, const double* inc0, const double* glat, const double* olat_sorted, const SolveState* st, double t) {
+    ARG_CHECK(h && gxyz && gsig && oxyz && osig && z && z0 && inc0 && ny > 0 && nx > 0 && m > 0 && (xa || inc) && g >= 0.0);
+    ARG_CHECK(!xa || xb);
+    ARG_CHECK(dtype == OISAT_F32 || dtype == OISAT_F64);
+    ARG_CHECK(h->corr == OISAT_CORR_GAUSSIAN && nx < (int64_t)INT32_MAX);
+    const int64_t n = ny * nx;
+    const double win = lat_window_deg(OISAT_CORR_GAUSSIAN, g);
+    if (!(win < 180.0) || !glat || !olat_sorted) { glat = nullptr; olat_sorted = nullptr; }       // (the rule of apply_increment_impl)
+    const int cells = increment_cells(h->cu_count, n, 1);
+    const int64_t gx = increment_blocks(n, nx, cells);
+    ARG_CHECK(gx < (int64_t)INT32_MAX);
+    const unsigned ux = (unsigned)gx;
+    int rc;
+    if (dtype == OISAT_F32)
+        rc = cells == 1 ? increment_update_launch<float, 1>(h, ux, gxyz, gsig, n, (int)nx, oxyz, osig, z, z0, m, g, xb, xa, inc, inc0, glat, olat_sorted, st, t)
+                        : increment_update_launch<float, 2>(h, ux, gxyz, gsig, n, (int)nx, oxyz, osig, z, z0, m, g, xb, xa, inc, inc0, glat, olat_sorted, st, t);
+    else
+        rc = cells == 1 ? increment_update_launch<double, 1>(h, ux, gxyz, gsig, n, (int)nx, oxyz, osig, z, z0, m, g, xb, xa, inc, inc0, glat, olat_sorted, st, t)
+                        : increment_update_launch<double, 2>(h, ux, gxyz, gsig, n, (int)nx, oxyz, osig, z, z0, m, g, xb, xa, inc, inc0, glat, olat_sorted, st, t);
+    if (rc || st == nullptr) return rc;
+    if (dtype == OISAT_F32)
+        return cells == 1 ? increment_guarded_launch<float, 1>(h, ux, gxyz, gsig, n, (int)nx, oxyz, osig, z, m, g, xb, xa, inc, glat, olat_sorted, st, t)
+                          : increment_guarded_launch<float, 2>(h, ux, gxyz, gsig, n, (int)nx, oxyz, osig, z, m, g, xb, xa, inc, glat, olat_sorted, st, t);
+    return cells == 1 ? increment_guarded_launch<double, 1>(h, ux, gxyz, gsig, n, (int)nx, oxyz, osig, z, m, g, xb, xa, inc, glat, olat_sorted, st, t)
+                      : increment_guarded_launch<double, 2>(h, ux, gxyz, gsig, n, (int)nx, oxyz, osig, z, m, g, xb, xa, inc, glat, olat_sorted, st, t);
+}
+
+extern "C" int oisat_increment_update(oisat_ctx* h, int dtype, const double* gxyz, const double* gsig, int64_t ny, int64_t nx,
+                                      const double* oxyz, const double* osig, const double* z, const double* z0, int64_t m, double g,
+                                      const void* xb, void* xa, void* inc, const double* inc0, const double* glat,
+                                      const double* olat_sorted) {
+    return oisat_increment_update_if(h, dtype, gxyz, gsig, ny, nx, oxyz, osig, z, z0, m, g, xb, xa, inc, inc0, glat, olat_sorted, nullptr, 0.0);
 }
 
 extern "C" int oisat_probe_spread(oisat_ctx* h, const double* gxyz, const double* gsig, int64_t ny, int64_t nx, const double* oxyz,

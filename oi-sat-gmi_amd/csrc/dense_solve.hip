@@ -1,5 +1,6 @@
 // The solve unit of the dense solver: the triangular sweeps (trsv_pipe_kernel, and trsv_batched_kernel over many systems; their
-// rows are dense_trsv.inc), the gain solve with its float64 refinement (oisat_gain_solve; the residual itself is dense_cov.hip's),
+// rows are dense_trsv.inc), the gain solve with its float64 refinement (oisat_gain_solve; the residual itself is dense_cov.hip's) and
+// the same solve with the fields written underneath and behind it (oisat_gain_solve_fields; the increment kernels are dense_cov.hip's),
 // oisat_potrs, the handle's status words, and the oisat_batch_* API, whose solve phase launches the same sweep kernels.
 #include "dense_internal.h"
 
@@ -103,6 +104,9 @@ __global__ __launch_bounds__(1024) void resid_check_kernel(const double* __restr
                                                             double* __restrict__ keep) {
     __shared__ double sr[1024], sd[1024];
     if (st->conv != 0) return;
+    // one workgroup on the critical path: its waves go first where they share a SIMD with another stream's (the side stream's
+    // increment of oisat_gain_solve_fields held this kernel for 0.72 ms instead of 0.06)
+    __builtin_amdgcn_s_setprio(3);
     double a = 0.0, b = 0.0;
     for (int64_t i = threadIdx.x; i < m; i += 1024) {
         if (keep != nullptr) keep[i] = r[i];
@@ -290,6 +294,42 @@ extern "C" int oisat_trsv_plan(int64_t nb, int band, int cu_count, int32_t* two_
     return OISAT_OK;
 }
 
+// The sweeps' shape while another stream's increment shares the GPU with them (oisat_gain_solve_fields; host only).  A two-tile
+// sweep workgroup holds 2 * 128 * TLD floats of LDS (134 160 B with the kernel's static words) of a CU's 160 KiB: beside it exactly
+// ONE increment workgroup fits (kSolveLdsBytes = 26 848 B), against five on a CU without one.  The sweeps are bound by their
+// hand-overs, not by CUs: a grid of kIncOverlapSweepWgs = 128 was measured as no slower for a band of at most 128 block rows
+// (profiles/EXPERIMENTS.md, "T_b ahead of the hand-over": the band's rows are all that can make progress), so such a sweep is
+// capped there and the increment gets the other CUs at full occupancy.  One tile per workgroup (a dense system, 67 KB) or a wider
+// band: the shape of oisat_trsv_plan, unchanged.
+constexpr int kIncOverlapSweepWgs = 128;
+extern "C" int oisat_trsv_plan_overlap(int64_t nb, int band, int cu_count, int32_t* two_tiles_out, int32_t* grid_out) {
+    int32_t two = 0, grid = 0;
+    if (int rc = oisat_trsv_plan(nb, band, cu_count, &two, &grid)) return rc;
+    if (two && band > 0 && band <= kIncOverlapSweepWgs && grid > kIncOverlapSweepWgs) grid = kIncOverlapSweepWgs;
+    if (two_tiles_out) *two_tiles_out = two;
+    if (grid_out) *grid_out = grid;
+    return OISAT_OK;
+}
+
+// Where DenseAnalysis.run takes oisat_gain_solve_fields instead of oisat_gain_solve + oisat_apply_increment_grid (host only).
+// Legal: one system, the Gaussian (the update is its packed-fp32 form), at least one refinement round (the guard reads the first
+// residual), fields wanted, no drift (its increment is another vector's).  Worth it: the update costs 0.7 ms at the headline's grid
+// and nothing is hidden but the two sweeps of the first correction, 2 x 3.3 us per block row -- so at least kIncOverlapMinRows = 256
+// block rows (1.7 ms of sweeps; the headline has 782, BASELINE's config 2 has 79 and keeps the two calls).  The bound is reasoned;
+// measured is the headline alone: 1.0 ms of 63 (profiles/EXPERIMENTS.md, "The increment under the correction's sweeps").
+// OISAT_INC_OVERLAP=0: nowhere; 1: wherever it is legal, whatever the size (tests); unset: kIncOverlapDefault decides whether the
+// rule is in force at all.
+constexpr int kIncOverlapMinRows = 256;
+constexpr bool kIncOverlapDefault = true;
+extern "C" int oisat_inc_overlap_plan(int64_t nb, int nsys, int corr_kind, int refine, int fields, int drift, int32_t* use_out) {
+    ARG_CHECK(nb >= 1 && nsys >= 1 && refine >= 0 && use_out != nullptr);
+    const int mode = inc_overlap_mode();
+    ARG_CHECK(mode != -2 && "OISAT_INC_OVERLAP is 0 or 1");
+    const bool legal = nsys == 1 && corr_kind == OISAT_CORR_GAUSSIAN && refine > 0 && fields != 0 && drift == 0;
+    *use_out = legal && mode != 0 && (mode == 1 || (kIncOverlapDefault && nb >= kIncOverlapMinRows)) ? 1 : 0;
+    return OISAT_OK;
+}
+
 // OISAT_TRSV_TWO_TILES=0|1 forces the choice of oisat_trsv_plan, OISAT_TRSV_MAX_WGS=<n >= 1> caps the sweeps' grid (A/B runs,
 // tests: a few workgroups serving many rows each at a small size); read at every call, like OISAT_ENVELOPE.  Forcing two tiles
 // is always legal: a row waits only for lower tickets, and every claimed ticket is held by a running workgroup.
@@ -302,6 +342,9 @@ static int trsv_launch_shape(const oisat_ctx* h, const ChFactor& f, int nb, int*
         two = forced;
         grid = two && h->cu_count > 0 ? std::min(nb, h->cu_count) : nb;
     }
+    // while the side stream's increment is in flight (oisat_gain_solve_fields) the two-tile sweeps leave it half the CUs
+    if (h->inc_in_flight && forced < 0)
+        if (int rc = oisat_trsv_plan_overlap(nb, f.env != nullptr ? f.band : 0, h->cu_count, &two, &grid)) return rc;
     long cap = 0;
     const int capped = trsv_max_wgs(&cap);
     ARG_CHECK(capped >= 0 && "OISAT_TRSV_MAX_WGS is an integer >= 1");
@@ -418,9 +461,35 @@ extern "C" int oisat_potrs(oisat_ctx* h, const float* L, int64_t m, int64_t ld, 
 // test runs on the device: resid_check_kernel sets a flag and the launches of the rounds that follow return at once, so
 // nothing waits for the host.  Launches: prep, 2 sweeps, then per round residual (written straight into the padded right-
 // hand side), check, 2 sweeps (the backward one adds its solution to z): no fills, no copies.
-extern "C" int oisat_gain_solve(oisat_ctx* h, const float* L, const double* oxyz, const double* osig, const double* ovar, int64_t m,
-                                int64_t ld, double g, const double* d, int refine, double* z_out, double* resid_host,
-                                const double* olat_sorted) {
+// fo (or nullptr: oisat_gain_solve): the fields of oisat_gain_solve_fields, below, which the same body writes
+namespace {
+struct IncFields {                                              // the grid and the fields of oisat_gain_solve_fields
+    int dtype;
+    const double *gxyz, *gsig;
+    int64_t ny, nx;
+    const void* xb;
+    void *xa, *inc;
+    const double* glat;
+};
+// the side stream's launch is joined on every way out of the solve: the main stream waits for its event, so the handle's buffers
+// stay ordered behind the owning stream whatever the call returns
+struct IncSideJoin {
+    oisat_ctx* h;
+    bool forked = false;
+    int join() {
+        h->inc_in_flight = false;
+        if (!forked) return OISAT_OK;
+        forked = false;
+        HIP_TRY(hipStreamWaitEvent(h->stream, h->inc_join, 0));
+        return OISAT_OK;
+    }
+    ~IncSideJoin() { (void)join(); }
+};
+}  // namespace
+
+static int gain_solve_impl(oisat_ctx* h, const float* L, const double* oxyz, const double* osig, const double* ovar, int64_t m,
+                           int64_t ld, double g, const double* d, int refine, double* z_out, double* resid_host,
+                           const double* olat_sorted, const IncFields* fo) {
     ARG_CHECK(h != nullptr);
     const int* perm = oisat_take_obs_perm(h, m);               // one-shot, whatever this call's outcome
     // the forward vector of this very d, left by oisat_potrf_env_fwd's launch: consumed once, whatever this call's outcome
@@ -442,6 +511,42 @@ extern "C" int oisat_gain_solve(oisat_ctx* h, const float* L, const double* oxyz
     }
     int rc = trsv_solve(h, h->factor, rhs, fwd, nullptr, z_out, 0, fwd_done);
     if (rc) return rc;
+    // The fields of the first solve's z0, underneath what follows (oisat_gain_solve_fields): z0 is snapshot on the main stream -- the
+    // backward sweeps of the corrections add into z_out while the side stream reads -- and the side stream, behind an event, runs
+    // the float64 increment of the snapshot into a double scratch field.  Profiling (HIP events on the launch stream cannot time
+    // another stream's kernel): the same launch on the main stream, serial, same bits.
+    IncSideJoin side{h};
+    double *inc0 = nullptr, *z0 = nullptr;
+    if (fo != nullptr) {
+        const int64_t n = fo->ny * fo->nx;
+        inc0 = (double*)oisat_ws(h, 14, sizeof(double) * (size_t)(n + m + 2));
+        if (!inc0) return OISAT_ENOMEM;
+        z0 = inc0 + ((n + 1) & ~(int64_t)1);
+        HIP_TRY(hipMemcpyAsync(z0, z_out, sizeof(double) * m, hipMemcpyDeviceToDevice, h->stream));
+        if (!h->prof) {
+            if (!h->inc_stream) {
+                int prio_low = 0, prio_high = 0;
+                HIP_TRY(hipDeviceGetStreamPriorityRange(&prio_low, &prio_high));
+                HIP_TRY(hipStreamCreateWithPriority(&h->inc_stream, hipStreamNonBlocking, prio_low));   // the sweeps come first
+                HIP_TRY(hipEventCreateWithFlags(&h->inc_fork, hipEventDisableTiming));
+                HIP_TRY(hipEventCreateWithFlags(&h->inc_join, hipEventDisableTiming));
+            }
+            hipStream_t main_stream = h->stream;
+            HIP_TRY(hipEventRecord(h->inc_fork, main_stream));
+            HIP_TRY(hipStreamWaitEvent(h->inc_stream, h->inc_fork, 0));
+            h->stream = h->inc_stream;                           // (the launch goes to the side stream)
+            rc = oisat_increment_scratch(h, fo->gxyz, fo->gsig, fo->ny, fo->nx, oxyz, osig, z0, m, g, inc0, fo->glat, olat_sorted);
+            const hipError_t er = rc == OISAT_OK ? hipEventRecord(h->inc_join, h->inc_stream) : hipSuccess;
+            h->stream = main_stream;
+            if (rc) return rc;
+            HIP_TRY(er);
+            side.forked = true;
+            h->inc_in_flight = true;                             // the sweeps launched from here to the join leave it CUs
+        } else {
+            rc = oisat_increment_scratch(h, fo->gxyz, fo->gsig, fo->ny, fo->nx, oxyz, osig, z0, m, g, inc0, fo->glat, olat_sorted);
+            if (rc) return rc;
+        }
+    }
     // the residual is evaluated once more behind the last allowed correction: a converged solve skips it (no-op launches), one
     // that is still above the tolerance there is recorded in the handle's status (oisat_solve_status_ex)
     int* info_dev = nullptr;
@@ -470,6 +575,14 @@ extern "C" int oisat_gain_solve(oisat_ctx* h, const float* L, const double* oxyz
         rc = trsv_solve(h, h->factor, rhs, fwd, st, z_out, 1);
         if (rc) return rc;
     }
+    if (fo != nullptr) {
+        // join, then the fields: T(inc0 + B H^T (z - z0)) where the guard lets the fp32 update apply, the float64 increment of the
+        // final z where it does not -- one of the two launches returns at once
+        if (int rj = side.join()) return rj;
+        rc = oisat_increment_update_if(h, fo->dtype, fo->gxyz, fo->gsig, fo->ny, fo->nx, oxyz, osig, z_out, z0, m, g, fo->xb, fo->xa, fo->inc,
+                                       inc0, fo->glat, olat_sorted, st, oisat_inc_update_t());
+        if (rc) return rc;
+    }
     if (resid_host) {
         char* pin = (char*)oisat_pinned(h, 512);
         if (!pin) return OISAT_ENOMEM;
@@ -490,6 +603,31 @@ extern "C" int oisat_gain_solve(oisat_ctx* h, const float* L, const double* oxyz
         }
     }
     return OISAT_OK;
+}
+
+extern "C" int oisat_gain_solve(oisat_ctx* h, const float* L, const double* oxyz, const double* osig, const double* ovar, int64_t m,
+                                int64_t ld, double g, const double* d, int refine, double* z_out, double* resid_host,
+                                const double* olat_sorted) {
+    return gain_solve_impl(h, L, oxyz, osig, ovar, m, ld, g, d, refine, z_out, resid_host, olat_sorted, nullptr);
+}
+
+// oisat_gain_solve followed by oisat_apply_increment_grid, with the increment of the FIRST solve's z0 on the handle's side stream
+// underneath the correction's residual and sweeps, and what the correction adds to it as a packed-fp32 update behind them
+// (dense_inc_update.inc).  Gaussian, refine >= 1.  All ordering is by events; the call returns with the side stream joined.
+extern "C" int oisat_gain_solve_fields(oisat_ctx* h, const float* L, const double* oxyz, const double* osig, const double* ovar, int64_t m,
+                                       int64_t ld, double g, const double* d, int refine, double* z_out, double* resid_host,
+                                       const double* olat_sorted, int dtype, const double* gxyz, const double* gsig, int64_t ny, int64_t nx,
+                                       const void* xb, void* xa, void* inc, const double* glat) {
+    ARG_CHECK(h != nullptr);
+    if (!(h->corr == OISAT_CORR_GAUSSIAN && refine >= 1 && refine <= 8 && gxyz && gsig && ny > 0 && nx > 0 && nx < (int64_t)INT32_MAX &&
+          (xa || inc) && (!xa || xb) && (dtype == OISAT_F32 || dtype == OISAT_F64) && z_out && m > 0)) {
+        (void)oisat_take_obs_perm(h, m);                        // one-shot, whatever this call's outcome
+        h->factor.fwd_d = nullptr;
+        oisat_set_error("oisat_gain_solve_fields: Gaussian correlation, 1 <= refine <= 8, a grid and its fields are required");
+        return OISAT_EINVAL;
+    }
+    const IncFields fo{dtype, gxyz, gsig, ny, nx, xb, xa, inc, glat};
+    return gain_solve_impl(h, L, oxyz, osig, ovar, m, ld, g, d, refine, z_out, resid_host, olat_sorted, &fo);
 }
 
 // words of oisat_solve_status_ex (include/oisat.h: OISAT_STATUS_*)

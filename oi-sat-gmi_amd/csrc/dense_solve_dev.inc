@@ -615,6 +615,13 @@ constexpr int kUpdStage = (int)(2 * sizeof(double2) * kStage / (4 * sizeof(float
 // on the protocol's months and the tests' geometries, rounded up to a power of two: profiles/EXPERIMENTS.md, "The verification
 // residual as an update"); the stopping test charges that bound (resid_update_check_kernel, dense_solve.hip)
 constexpr double kResidUpdateC = OISAT_RESID_UPDATE_C;         // (include/oisat.h documents it to callers)
+// The same argument for the INCREMENT behind a correction (dense_inc_update.inc; oisat_gain_solve_fields): delta = B H^T (z - z0) in
+// packed fp32 is e |delta| (max-norm) from its float64 value, and |delta| <= |r_0| / |d| of the field's scale (|K| <= 1), so the
+// fields move by e t of their largest value where |r_0| <= t |d|.  kIncUpdateT is the largest power of two t with e t <= 2^-27, a
+// quarter ulp of the largest fp32 field value, for the largest e measured on the protocol's four months (profiles/EXPERIMENTS.md,
+// "The increment under the correction's sweeps": e = 1.69e-4 on NO2 seed 3003, so t = 2^-15 = 3.05e-5 against first residuals of
+// 3.1e-6 .. 2.6e-5); a solve whose first residual is above it takes the float64 increment of its final z.
+constexpr double kIncUpdateT = OISAT_INC_UPDATE_T;             // (include/oisat.h documents it to callers)
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ void resid_update_block(const double* __restrict__ oxyz, const double* __restrict__ osig,
                                                    const double* __restrict__ ovar, int64_t m, double g,

@@ -21,6 +21,7 @@
 //   OISAT_TRSV_TWO_TILES       0 | 1                                trsv_launch_shape (dense_solve.hip)           test_gpu_sweep_tiles
 //   OISAT_TRSV_MAX_WGS         <integer >= 1>                       trsv_launch_shape (dense_solve.hip)           test_gpu_sweep_tiles
 //   OISAT_RESID_UPDATE         0 | 1                                oisat_gain_solve (dense_solve.hip)            test_gpu_resid_update
+//   OISAT_INC_OVERLAP          0 | 1                                oisat_inc_overlap_plan (dense_solve.hip)      test_inc_overlap_cpu, test_gpu_inc_overlap
 //   OISAT_SOLVE_FAR_BITS       <number in [0, 52]>                  far_chord_of (dense_solve_dev.inc)            test_solve_tiers_cpu, test_gpu_solve_tiers
 //   OISAT_PROF_DETAIL          0 | 1 (atoi), read once              launch_gemm(_batched) (dense_gemm.hip)        - (profiling aid)
 #pragma once
@@ -133,6 +134,15 @@ inline int resid_update_mode() {
     const char* e = getenv("OISAT_RESID_UPDATE");
     if (!e || !*e) return 1;
     return ((e[0] == '0' || e[0] == '1') && e[1] == '\0') ? e[0] - '0' : -1;
+}
+
+// OISAT_INC_OVERLAP=0: DenseAnalysis.run keeps oisat_gain_solve + oisat_apply_increment_grid, the launches and bits of the code
+// before oisat_gain_solve_fields; 1: the new entry wherever it is legal, whatever the system's size (tests).  Unset or empty: -1,
+// the rule of oisat_inc_overlap_plan decides; anything else: -2.
+inline int inc_overlap_mode() {
+    const char* e = getenv("OISAT_INC_OVERLAP");
+    if (!e || !*e) return -1;
+    return ((e[0] == '0' || e[0] == '1') && e[1] == '\0') ? e[0] - '0' : -2;
 }
 
 }  // namespace oisat_dense

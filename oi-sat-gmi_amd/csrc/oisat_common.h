@@ -127,8 +127,8 @@ struct oisat_ctx {
     std::vector<ProfPending> pending;
     std::vector<hipEvent_t> free_events;
     // grow-only device workspaces (never freed/reallocated inside a timed region once warm)
-    void* ws[14] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    size_t ws_bytes[14] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    void* ws[15] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    size_t ws_bytes[15] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
     // last scaling sweep uploaded into workspace slot 0 (oi_diag.hip)
     double scales_host[OISAT_MAX_SCALES] = {0};
     int scales_n = 0;
@@ -143,6 +143,11 @@ struct oisat_ctx {
     hipStream_t own_stream = nullptr;   // created by oisat_stream_create, destroyed at shutdown
     hipStream_t aux_stream = nullptr;   // look-ahead Cholesky: trailing updates run here, the panel chain on `stream`
     std::vector<hipEvent_t> sync_events;
+    // oisat_gain_solve_fields: the increment of the first solve runs here underneath the correction's sweeps (lowest priority,
+    // created on first use); fork = z0 and its snapshot are out (main), join = the scratch field is written (side)
+    hipStream_t inc_stream = nullptr;
+    hipEvent_t inc_fork = nullptr, inc_join = nullptr;
+    bool inc_in_flight = false;         // ... a side launch is in flight: the sweeps launched meanwhile leave it CUs (trsv_launch_shape)
     void* comm = nullptr;               // RCCL communicator (oisat_comm_init), opaque here
     int comm_rank = 0, comm_size = 1;
     hipEvent_t signal_event = nullptr;  // oisat_wait_for: recorded on this handle's stream, waited on by another handle's
@@ -201,6 +206,15 @@ double oisat_resid_update_c();
 int oisat_cov_residual_batched(oisat_ctx* h, const SolveMember* mem_dev, const std::vector<SolveMember>& mem_host, int64_t max_m, double g);
 int oisat_apply_increment_batched(oisat_ctx* h, int dtype, const SolveMember* mem_dev, const std::vector<SolveMember>& mem_host, int64_t max_n,
                                   double g);
+// ... and the launches of oisat_gain_solve_fields behind its sweeps: the float64 increment of z0 into a double scratch field, and
+// the update of it (guarded by st; the float64 increment of the final z where the guard fails)
+int oisat_increment_scratch(oisat_ctx* h, const double* gxyz, const double* gsig, int64_t ny, int64_t nx, const double* oxyz,
+                            const double* osig, const double* z0, int64_t m, double g, double* inc0, const double* glat,
+                            const double* olat_sorted);
+int oisat_increment_update_if(oisat_ctx* h, int dtype, const double* gxyz, const double* gsig, int64_t ny, int64_t nx, const double* oxyz,
+                              const double* osig, const double* z, const double* z0, int64_t m, double g, const void* xb, void* xa,
+                              void* inc, const double* inc0, const double* glat, const double* olat_sorted, const SolveState* st, double t);
+double oisat_inc_update_t();
 
 int oisat_prof_begin(oisat_ctx* h, const char* name);   // returns pending index or -1
 void oisat_prof_end(oisat_ctx* h, int pending);

@@ -57,6 +57,9 @@ extern "C" void oisat_shutdown(oisat_ctx* h) {
     if (h->pinned) (void)hipHostFree(h->pinned);
     if (h->own_stream) (void)hipStreamDestroy(h->own_stream);
     if (h->aux_stream) (void)hipStreamDestroy(h->aux_stream);
+    if (h->inc_stream) (void)hipStreamDestroy(h->inc_stream);
+    if (h->inc_fork) (void)hipEventDestroy(h->inc_fork);
+    if (h->inc_join) (void)hipEventDestroy(h->inc_join);
     for (hipStream_t& xs : h->xfer_streams)
         if (xs) (void)hipStreamDestroy(xs);
     for (auto ev : h->sync_events) (void)hipEventDestroy(ev);

@@ -156,6 +156,12 @@ SIGNATURES = {
                                         _ptr, _ptr, _ptr, _ptr]),
     "oisat_apply_increment_grid": (C.c_int, [_c_ctx, C.c_int, _ptr, _ptr, _i64, _i64, _ptr, _ptr, _ptr, _i64, C.c_double, _ptr,
                                              _ptr, _ptr, _ptr, _ptr]),
+    "oisat_gain_solve_fields": (C.c_int, [_c_ctx, _ptr, _ptr, _ptr, _ptr, _i64, _i64, C.c_double, _ptr, C.c_int, _ptr,
+                                          C.POINTER(C.c_double), _ptr, C.c_int, _ptr, _ptr, _i64, _i64, _ptr, _ptr, _ptr, _ptr]),
+    "oisat_increment_update": (C.c_int, [_c_ctx, C.c_int, _ptr, _ptr, _i64, _i64, _ptr, _ptr, _ptr, _ptr, _i64, C.c_double, _ptr,
+                                         _ptr, _ptr, _ptr, _ptr, _ptr]),
+    "oisat_trsv_plan_overlap": (C.c_int, [_i64, C.c_int, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "oisat_inc_overlap_plan": (C.c_int, [_i64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32)]),
     "oisat_batch_create": (C.c_int, [_c_ctx, C.c_int, C.POINTER(_ptr), C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_ptr),
                                      C.POINTER(C.c_int)]),
     "oisat_batch_potrf": (C.c_int, [_c_ctx, C.c_int, C.POINTER(C.c_int)]),

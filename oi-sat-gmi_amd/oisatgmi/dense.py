@@ -349,6 +349,7 @@ class DenseAnalysis:
         self._gsig0 = self._osig0 = self._ovar0 = None
         self._lik_ready = False                                # the last run() was one that log_likelihood() may read
         self._drift = None                                     # what the last run(drift=...) estimated (drift_estimate())
+        self.last_inc_overlap = False                          # the last run() took oisat_gain_solve_fields
         # every internal workspace of the solve is sized here, so that run() never allocates (include/oisat.h)
         c.check(c.lib.oisat_dense_reserve(c.h, self.max_obs, int(diag_chunk_rows)))
 
@@ -535,14 +536,24 @@ class DenseAnalysis:
         self.last_schedule = schedule.value                    # (SCHEDULE_*: which factorization ran, for tests and profiles)
         resid = (C.c_double * (refine + 1))() if want_resid else None
         c.check(lib.oisat_set_obs_blocks(h, self.perm.ptr, m))                                  # per run: handles are shared
-        if deg is None:
+        # the solve and the fields as ONE call where the library's rule allows (oisat_inc_overlap_plan; OISAT_INC_OVERLAP): the
+        # increment of the first solve then runs underneath the correction's sweeps (include/oisat.h: oisat_gain_solve_fields)
+        overlap = C.c_int32(0)
+        c.check(lib.oisat_inc_overlap_plan(self.mp // NB, 1, kind, int(refine), int(bool(fields)), int(deg is not None),
+                                           C.byref(overlap)))
+        self.last_inc_overlap = bool(overlap.value)            # (for tests and profiles)
+        if overlap.value:
+            c.check(lib.oisat_gain_solve_fields(h, self.S.ptr, self.oxyz.ptr, self.osig.ptr, self.ovar.ptr, m, ld, g, self.d.ptr,
+                                                int(refine), self.z.ptr, resid, self.olat.ptr, self.code, self.gxyz.ptr,
+                                                self.gsig.ptr, self._ny, self._nx, xb, xa, inc, self.glat.ptr))
+        elif deg is None:
             c.check(lib.oisat_gain_solve(h, self.S.ptr, self.oxyz.ptr, self.osig.ptr, self.ovar.ptr, m, ld, g, self.d.ptr,
                                          int(refine), self.z.ptr, resid, self.olat.ptr))
         else:
             col0 = self._drift_solve(deg, int(refine), REFINE_TOL if tol is None else float(tol))
             if want_resid:
                 resid = col0
-        if fields:
+        if fields and not overlap.value:
             c.check(lib.oisat_apply_increment_grid(h, self.code, self.gxyz.ptr, self.gsig.ptr, self._ny, self._nx, self.oxyz.ptr,
                                                    self.osig.ptr, self.z.ptr, m, g, xb, xa, inc, self.glat.ptr, self.olat.ptr))
             if deg is not None:
